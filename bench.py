@@ -18,6 +18,10 @@
                   (64, G, 16) x 3 or 5 feedback rounds, batch_size 5 000, p = 0.05 / 0.07 (n882.py:13,39,56-66, n1270.py:57-70); timed on one
                   stream (`value`) and with consecutive batches alternating between two HIP streams (`two_streams`) in the same run.
 `--cn-type` / `--factor` set the check-node rule and normalization factor of every decoder (default: the configuration's).
+`--dump-outputs DIR` writes what the last timed step of rank 0 computed to DIR/<name>.npy (float32 / float64, at most 64 MB): `flags`
+(per sample: bit 0 flagged, bit 1 block error), `counts` (the timed region's counters), and `noise_x`, `noise_z`, `x_hat`, `z_hat`
+(c5: also `llr`) for a fixed seeded sample of the batch's rows whose global sample indices are `sample_index`.  The samples are Philox
+draws at fixed indices, so the same arguments give the same inputs on every run and two builds can be compared output for output.
 
 One "step" = one Monte-Carlo batch through the whole hot path, everything on device: Philox depolarizing noise -> syndromes -> decoder
 (c3 / c4: BP4 -> flag update -> feedback GNN (trained weights) -> BP4 -> masked merge; c5: GNN_BP4) -> residual check -> counters, at
@@ -219,6 +223,35 @@ def sharding_report(step_ranges, rank_rows, W, K, world, B, reduced_counts):
     return rep, bool(tiles and adds_up)
 
 
+DUMP_BYTES = 64_000_000  # --dump-outputs: the .npy files of one run take at most this many bytes
+DUMP_ROW_ARRAYS = ("noise_x", "noise_z", "x_hat", "z_hat", "llr")  # per-sample arrays, sampled by row when the batch is too large
+
+
+def dump_outputs(path, kept, counts, first_sample, seed):
+    """Write the last timed step's arrays (`kept`: device tensors of that step) and the timed region's counters to path/<name>.npy.
+    `flags` (bit 0 = flagged, bit 1 = block error) and `counts` are written whole; the per-sample arrays are written for a sorted
+    sample of rows drawn by a generator seeded with `seed`, as many as fit DUMP_BYTES, and `sample_index` holds the global Philox
+    sample index of each of those rows.  Same arguments, same rows, same inputs.  Returns {name: shape}."""
+    import numpy as np
+    import torch
+    B = int(kept["flags"].shape[0])
+    row_arrays = [k for k in DUMP_ROW_ARRAYS if kept.get(k) is not None]
+    row_bytes = sum(4 * kept[k][0].numel() for k in row_arrays) + 8  # float32 per element, + one float64 sample_index
+    fixed_bytes = 4 * B + 8 * 3 + 128 * (3 + len(row_arrays))  # flags (float32), counts (float64), one .npy header per file
+    R = min(B, (DUMP_BYTES - fixed_bytes) // row_bytes)
+    rows = np.arange(B) if R == B else np.sort(np.random.default_rng(seed).choice(B, size=R, replace=False))
+    idx = torch.as_tensor(rows, dtype=torch.int64, device=kept["flags"].device)
+    arrays = {"counts": np.asarray(counts, dtype=np.float64),
+              "flags": kept["flags"].cpu().numpy().astype(np.float32),
+              "sample_index": (first_sample + rows).astype(np.float64)}
+    for k in row_arrays:
+        arrays[k] = kept[k].index_select(0, idx).cpu().numpy().astype(np.float32)
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    return {k: list(a.shape) for k, a in arrays.items()}
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -261,7 +294,15 @@ def parse_args(argv=None):
     ap.add_argument("--require-roofline", action="store_true",
                     help="exit non-zero (after printing the line) when roofline.frac is null: no offline PMC counts for this shape, "
                          "or counts measured on other kernel sources")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step of rank 0 computed as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB: a fixed seeded sample of the batch's rows), so that two builds can be compared output for output "
+                         "(bench_outputs/ is kept out of git)")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.warmup < 0:
+        ap.error("--warmup must be >= 0")
     cfg = CONFIGS[args.config]
     args.batch = cfg["batch"] if args.batch is None else args.batch
     args.code = cfg["code"] if args.code is None else args.code
@@ -286,7 +327,16 @@ def build_once(no_build):
         if not os.path.exists(_lib.LIB_PATH):
             raise SystemExit(f"--no-build: {_lib.LIB_PATH} is missing")
         return
-    with open(os.path.join(ROOT, ".bench_build.lock"), "w") as lock:
+    try:
+        lock = open(os.path.join(ROOT, ".bench_build.lock"), "a")
+    except OSError:
+        # a checkout this user may not write to (built beforehand by another account): the lock only has to be shared by the ranks of
+        # this run, which are all this user's processes on this host, so it lives in the temporary directory, one per user and checkout
+        import hashlib
+        import tempfile
+        tag = hashlib.sha256(ROOT.encode()).hexdigest()[:16]
+        lock = open(os.path.join(tempfile.gettempdir(), f"fgnn_bench_build_{os.getuid()}_{tag}.lock"), "a")
+    with lock:
         fcntl.flock(lock, fcntl.LOCK_EX)
         try:
             entry.build()
@@ -899,6 +949,7 @@ def main():
 
     B, K, W = args.batch, args.steps, args.warmup
     sample_log = []  # [first, last) of the global Philox sample range of every step this rank has run, in order
+    kept = {} if args.dump_outputs else None  # --dump-outputs: the device arrays of the latest step (references only, no copy)
     if is_c5:
         from feedback_gnn_amd.graph import TannerGraph
         g = TannerGraph(code)
@@ -912,6 +963,8 @@ def main():
             sx, sz = g.syndrome(ex, ez)
             o = g.gnn_bp4_decode(wdev, sx, sz, iters[0], return_logits=False, workspace=ws)
             o["noise_x"], o["noise_z"] = ex, ez
+            if kept is not None:
+                kept["llr"] = o["llr"]
             return o
 
         def step(counts):
@@ -954,6 +1007,16 @@ def main():
     # Headline = the reference's fixed dataflow: every exp/log of every iteration is evaluated.  The product
     # default (exact wave-uniform shortcut for saturated nodes, same bits) is timed separately under `extras`.
     g.set_saturation_shortcut(False)
+    if kept is not None:
+        # every step ends in one residual check of the noise against the decisions (Sandwich_BP_GNN_Evaluation_Model.mc_step / step
+        # above): keep that call's arrays, freshly allocated by the step, so that the last timed step's are at hand after the timed region
+        residual = g.residual
+
+        def residual_kept(ex, ez, x_hat, z_hat, want_arrays=True):
+            r = residual(ex, ez, x_hat, z_hat, want_arrays=want_arrays)
+            kept.update(noise_x=ex, noise_z=ez, x_hat=x_hat, z_hat=z_hat, flags=r[2])
+            return r
+        g.residual = residual_kept
 
     def sync():
         if dist is not None:
@@ -1012,6 +1075,11 @@ def main():
             counts = allreduce(counts, dist.ReduceOp.SUM)
         else:
             step_ranges = [[list(r) for r in timed_ranges]]
+        dumped = None
+        if kept is not None:
+            del g.residual  # the steps timed after this point keep nothing
+            if rank == 0:
+                dumped = dump_outputs(args.dump_outputs, kept, counts.cpu().numpy(), timed_ranges[-1][0], SEED)
         # ---- the same step under the OTHER forms (single-GPU runs): the opt-in re-associations when the headline is the library
         # default, the literal forms when an A/B run made the re-associated ones the headline; same bracket, same sample stream ----
         other_forms = None
@@ -1133,6 +1201,10 @@ def main():
             if r.get("gnn"):
                 r["gnn"]["frac"] = r["gnn"]["achieved"] = None
         out.update(cpu_out)
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped, "first_sample": timed_ranges[-1][0],
+                                   "what": "rank 0's last timed step: flags and the timed region's counts whole, the per-sample arrays for "
+                                           "the rows in sample_index"}
         out["dist"] = dist_info
         if other_streams is not None:
             out["two_streams" if other_streams["streams"] == 2 else "one_stream"] = other_streams

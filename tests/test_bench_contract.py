@@ -476,3 +476,84 @@ def test_bench_under_the_drivers_torchrun_line():
         d = json.loads(lines[0])
         assert d["n_gpus"] == n and len(d["per_rank_ms"]) == n and d["config"]["global_batch"] == n * 2048
         assert d["counts"]["samples"] == 2 * n * 2048 and d["scaling"] == "weak"
+
+
+def test_bench_refuses_zero_timed_steps():
+    """`--steps` is the number of timed steps: there is no timed region of zero steps to take a time per step from."""
+    import bench
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+    assert bench.parse_args(["--steps", "5", "--warmup", "0"]).steps == 5
+
+
+def test_dump_outputs_is_bounded_seeded_and_float(tmp_path, monkeypatch):
+    """bench.dump_outputs on host tensors: every file float32 / float64, the files together within DUMP_BYTES, the same rows on every
+    call, and each dumped row the row of the batch that sample_index names."""
+    import numpy as np
+    import torch
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BYTES", 1_000_000)
+    B, n, first = 4096, 882, 7 * 4096
+    gen = torch.Generator().manual_seed(1)
+    kept = {k: torch.randint(0, 2, (B, n), dtype=torch.uint8, generator=gen) for k in ("noise_x", "noise_z", "x_hat", "z_hat")}
+    kept["flags"] = torch.randint(0, 4, (B,), dtype=torch.uint8, generator=gen)
+    shapes = bench.dump_outputs(str(tmp_path / "a"), kept, np.array([5, 3, 4096]), first, 0x5EED)
+    bench.dump_outputs(str(tmp_path / "b"), kept, np.array([5, 3, 4096]), first, 0x5EED)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(k + ".npy" for k in shapes) == sorted(["counts.npy", "flags.npy", "sample_index.npy", "noise_x.npy",
+                                                                    "noise_z.npy", "x_hat.npy", "z_hat.npy"])
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 1_000_000
+    R = shapes["x_hat"][0]
+    assert 0 < R < B and shapes["sample_index"] == [R] and shapes["flags"] == [B] and shapes["counts"] == [3]
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), f
+    rows = np.load(tmp_path / "a" / "sample_index.npy").astype(np.int64) - first
+    assert np.all(np.diff(rows) > 0) and rows[0] >= 0 and rows[-1] < B
+    for k in ("noise_x", "noise_z", "x_hat", "z_hat"):
+        assert np.array_equal(np.load(tmp_path / "a" / f"{k}.npy"), kept[k].numpy()[rows].astype(np.float32))
+    assert np.array_equal(np.load(tmp_path / "a" / "flags.npy"), kept["flags"].numpy().astype(np.float32))
+    assert np.load(tmp_path / "a" / "counts.npy").tolist() == [5.0, 3.0, 4096.0]
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_are_the_last_timed_step_and_repeat(tmp_path):
+    """`--dump-outputs DIR`: two runs with the same arguments write the same arrays; they are the last of `--steps` timed steps (its
+    sample range, the timed region's counters); every file is float32 / float64 and all of them fit 64 MB; c5 adds the marginals."""
+    import numpy as np
+    runs = {}
+    for name, cfg, B in (("a", "c3", 2048), ("b", "c3", 2048), ("c", "c5", 512)):
+        res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", cfg, "--steps", "3", "--warmup", "1",
+                              "--batch", str(B), "--cpu-sample", "0", "--no-extras", "--no-literal", "--dump-outputs", str(tmp_path / name)],
+                             stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900, cwd=ROOT)
+        assert res.returncode == 0, res.stderr[-2000:]
+        d = json.loads([l for l in res.stdout.splitlines() if l.strip()][0])
+        assert d["steps"] == 3 and d["counts"]["samples"] == 3 * B and d["dump_outputs"]["first_sample"] == 3 * B
+        files = os.listdir(tmp_path / name)
+        assert sorted(files) == sorted(k + ".npy" for k in d["dump_outputs"]["arrays"])
+        assert sum(os.path.getsize(tmp_path / name / f) for f in files) <= 64_000_000
+        runs[name] = {f[:-4]: np.load(tmp_path / name / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in runs[name].values())
+        r = runs[name]
+        assert r["counts"].tolist() == [d["counts"]["flagged"], d["counts"]["block_errors"], 3 * B]
+        assert r["sample_index"].tolist() == list(range(3 * B, 4 * B)) and r["flags"].shape == (B,)  # a small batch is written whole
+        assert r["x_hat"].shape == r["noise_x"].shape == (B, 882 if cfg == "c3" else 1270)
+    assert runs["a"].keys() == runs["b"].keys() and all(np.array_equal(runs["a"][k], runs["b"][k]) for k in runs["a"])
+    assert "llr" not in runs["a"] and runs["c"]["llr"].shape == (512, 3, 1270) and np.isfinite(runs["c"]["llr"]).all()
+
+
+def test_bench_builds_in_a_checkout_it_cannot_write(tmp_path, monkeypatch):
+    """The benchmark may run as a user who can read the checkout but not write to it (the libraries were built by another account):
+    the build lock then goes to the temporary directory instead of failing before the build is even asked for."""
+    import tempfile
+    import __graft_entry__
+    import bench
+    calls = []
+    monkeypatch.setattr(__graft_entry__, "build", lambda: calls.append("build"))
+    monkeypatch.setattr(bench, "ROOT", str(tmp_path / "not_writable"))  # opening the lock there fails like a read-only tree
+    monkeypatch.setattr(tempfile, "tempdir", str(tmp_path / "tmp"))
+    os.makedirs(tmp_path / "tmp")
+    bench.build_once(False)
+    assert calls == ["build"]
+    locks = os.listdir(tmp_path / "tmp")
+    assert len(locks) == 1 and locks[0].startswith(f"fgnn_bench_build_{os.getuid()}_") and locks[0].endswith(".lock")
