@@ -612,13 +612,7 @@ extern "C" int fgnn_bp4_backward(const fgnn_graph* g, int num_iter, float normal
     const size_t floats = (size_t)2 * d.E + a.nu_sz + (size_t)6 * d.n + d.rows[0] + d.rows[1];
     const size_t lds_bytes = floats * sizeof(float);
     if (lds_bytes > FGNN_LDS_BUDGET) return fgnn_fail(FGNN_ERR_ARG, "code too large for the LDS-resident backward kernel");
-    auto kern = bp4_backward_kernel;
-    if (lds_bytes > 48 * 1024)
-        FGNN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)lds_bytes));
-    hipLaunchKernelGGL(kern, dim3(B), dim3(256), lds_bytes, static_cast<hipStream_t>(stream), d, a);
-    FGNN_HIP_CHECK(hipGetLastError());
-    return FGNN_OK;
+    return fgnn_launch(bp4_backward_kernel, dim3(B), dim3(256), lds_bytes, static_cast<hipStream_t>(stream), d, a);
 }
 
 extern "C" int fgnn_feedback_gnn_backward(const fgnn_graph* g, const fgnn_weights* w, const float* llr,
@@ -661,13 +655,7 @@ extern "C" int fgnn_feedback_gnn_backward(const fgnn_graph* g, const fgnn_weight
     }
     const size_t lds_bytes = (size_t)g->d.m * sizeof(float);
     if (lds_bytes > FGNN_LDS_BUDGET) return fgnn_fail(FGNN_ERR_ARG, "too many checks for the LDS-resident kernel");
-    auto kern = gnn_backward_kernel;
-    if (lds_bytes > 48 * 1024)
-        FGNN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)lds_bytes));
-    hipLaunchKernelGGL(kern, dim3(B), dim3(256), lds_bytes, static_cast<hipStream_t>(stream), g->d, w->d, a);
-    FGNN_HIP_CHECK(hipGetLastError());
-    return FGNN_OK;
+    return fgnn_launch(gnn_backward_kernel, dim3(B), dim3(256), lds_bytes, static_cast<hipStream_t>(stream), g->d, w->d, a);
 }
 
 extern "C" int fgnn_feedback_gnn_backward_general(const fgnn_graph* g, const fgnn_weights* w, const float* llr, const float* logit_hx,
@@ -700,11 +688,5 @@ extern "C" int fgnn_feedback_gnn_backward_general(const fgnn_graph* g, const fgn
     }
     const size_t lds_bytes = (size_t)g->d.m * sizeof(float);
     if (lds_bytes > FGNN_LDS_BUDGET) return fgnn_fail(FGNN_ERR_ARG, "too many checks for the LDS-resident kernel");
-    auto kern = gnn_general_backward_kernel;
-    if (lds_bytes > 48 * 1024)
-        FGNN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)lds_bytes));
-    hipLaunchKernelGGL(kern, dim3(B), dim3(256), lds_bytes, static_cast<hipStream_t>(stream), g->d, w->gen, a);
-    FGNN_HIP_CHECK(hipGetLastError());
-    return FGNN_OK;
+    return fgnn_launch(gnn_general_backward_kernel, dim3(B), dim3(256), lds_bytes, static_cast<hipStream_t>(stream), g->d, w->gen, a);
 }

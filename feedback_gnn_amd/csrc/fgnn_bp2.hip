@@ -339,13 +339,7 @@ __global__ void __launch_bounds__(256) bsc_kernel(uint64_t seed, float p, uint64
 template <int CN_TYPE, int DV = 0, int DC = 0>
 int launch(const fgnn_graph* g, const Bp2Args& a, const LaunchGeom& L, size_t lds_bytes, hipStream_t st)
 {
-    auto kern = bp2_kernel<CN_TYPE, DV, DC>;
-    if (lds_bytes > 48 * 1024)
-        FGNN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)lds_bytes));
-    hipLaunchKernelGGL(kern, dim3(L.blocks), dim3(L.threads), lds_bytes, st, g->d, a);
-    FGNN_HIP_CHECK(hipGetLastError());
-    return FGNN_OK;
+    return fgnn_launch(bp2_kernel<CN_TYPE, DV, DC>, dim3(L.blocks), dim3(L.threads), lds_bytes, st, g->d, a);
 }
 
 }  // namespace
@@ -404,8 +398,6 @@ extern "C" int fgnn_bsc_noise(uint64_t seed, float p, uint64_t first_sample, int
     if (!noise) return fgnn_fail(FGNN_ERR_ARG, "bad noise arguments");
     const int nblk = (n + 3) / 4;
     const long long total = (long long)B * nblk;
-    hipLaunchKernelGGL(bsc_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), seed, p,
+    return fgnn_launch(bsc_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), seed, p,
                        first_sample, B, n, nblk, noise);
-    FGNN_HIP_CHECK(hipGetLastError());
-    return FGNN_OK;
 }

@@ -18,7 +18,6 @@
 //
 // Summation order is the canonical one of the oracle (ascending neighbour index) and every
 // float op is the one the oracle executes, so results are bit-identical to oracle/fgnn_oracle.c.
-#include <cstdlib>
 
 #include "fgnn_internal.h"
 #include "fgnn_math.h"
@@ -925,49 +924,107 @@ bp4_kernel(GraphDev g, BpArgs a)
     }
 }
 
+using Bp4Kernel = void (*)(GraphDev, BpArgs);
+
+// The benchmark codes' kernels carry the form of the qubit update as a compile-time argument (LSE = 0 literal / 1 shared):
+// the (3,3,6) phi kernels indexed by [lreg 0 / 4 / 5][shortcut][LSE].
+template <int NQ, bool OPT, int LSE>
+constexpr Bp4Kernel bp4_lse_kernel = bp4_kernel<FGNN_CN_BOXPLUS_PHI, 3, 3, 6, OPT, false, NQ, false, false, LSE>;
+constexpr Bp4Kernel bp4_lse_kernels[3][2][2] = {
+    {{bp4_lse_kernel<0, false, 0>, bp4_lse_kernel<0, false, 1>}, {bp4_lse_kernel<0, true, 0>, bp4_lse_kernel<0, true, 1>}},
+    {{bp4_lse_kernel<4, false, 0>, bp4_lse_kernel<4, false, 1>}, {bp4_lse_kernel<4, true, 0>, bp4_lse_kernel<4, true, 1>}},
+    {{bp4_lse_kernel<5, false, 0>, bp4_lse_kernel<5, false, 1>}, {bp4_lse_kernel<5, true, 0>, bp4_lse_kernel<5, true, 1>}}};
+
 template <int CN_TYPE, int DVX, int DVZ, int DC>
 int launch_bp4_k(const fgnn_graph* g, const BpArgs& a, const LaunchGeom& L, size_t lds_bytes, hipStream_t st)
 {
-    auto kern = a.shortcut ? bp4_kernel<CN_TYPE, DVX, DVZ, DC, true> : bp4_kernel<CN_TYPE, DVX, DVZ, DC, false>;
+    Bp4Kernel kern = a.shortcut ? bp4_kernel<CN_TYPE, DVX, DVZ, DC, true> : bp4_kernel<CN_TYPE, DVX, DVZ, DC, false>;
     if constexpr ((DVX == 3 && DVZ == 3 && DC == 6) || DVX == 0) {
         if (a.trace_x) kern = bp4_kernel<CN_TYPE, DVX, DVZ, DC, false, false, 0, true>;  // fixed dataflow, channel LLRs in LDS
     }
     if constexpr (CN_TYPE == FGNN_CN_BOXPLUS_PHI) {
         if (a.hwt) kern = bp4_kernel<CN_TYPE, DVX, DVZ, DC, false, true>;  // opt-in, fixed dataflow (fgnn_graph_set_option 3)
         if constexpr (DVX == 3 && DVZ == 3 && DC == 6) {
-            // the benchmark codes' kernels carry the form of the qubit update as a compile-time argument (LSE = 0 literal / 1 shared)
-            if (!a.trace_x && !a.hwt) {
-                const int v = (a.shortcut ? 1 : 0) | (a.shared_lse ? 2 : 0);
-                if (a.lreg == 4) {
-                    kern = v == 0 ? bp4_kernel<CN_TYPE, 3, 3, 6, false, false, 4, false, false, 0> : v == 1 ? bp4_kernel<CN_TYPE, 3, 3, 6, true, false, 4, false, false, 0>
-                         : v == 2 ? bp4_kernel<CN_TYPE, 3, 3, 6, false, false, 4, false, false, 1> : bp4_kernel<CN_TYPE, 3, 3, 6, true, false, 4, false, false, 1>;
-                } else if (a.lreg == 5) {
-                    kern = v == 0 ? bp4_kernel<CN_TYPE, 3, 3, 6, false, false, 5, false, false, 0> : v == 1 ? bp4_kernel<CN_TYPE, 3, 3, 6, true, false, 5, false, false, 0>
-                         : v == 2 ? bp4_kernel<CN_TYPE, 3, 3, 6, false, false, 5, false, false, 1> : bp4_kernel<CN_TYPE, 3, 3, 6, true, false, 5, false, false, 1>;
-                } else {
-                    kern = v == 0 ? bp4_kernel<CN_TYPE, 3, 3, 6, false, false, 0, false, false, 0> : v == 1 ? bp4_kernel<CN_TYPE, 3, 3, 6, true, false, 0, false, false, 0>
-                         : v == 2 ? bp4_kernel<CN_TYPE, 3, 3, 6, false, false, 0, false, false, 1> : bp4_kernel<CN_TYPE, 3, 3, 6, true, false, 0, false, false, 1>;
-                }
-            }
+            if (!a.trace_x && !a.hwt) kern = bp4_lse_kernels[a.lreg ? a.lreg - 3 : 0][a.shortcut][a.shared_lse];
         }
     }
-    if (lds_bytes > 48 * 1024)
-        FGNN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)lds_bytes));
-    hipLaunchKernelGGL(kern, dim3(L.blocks), dim3(L.threads), lds_bytes, st, g->d, a);
-    FGNN_HIP_CHECK(hipGetLastError());
-    return FGNN_OK;
+    return fgnn_launch(kern, dim3(L.blocks), dim3(L.threads), lds_bytes, st, g->d, a);
 }
 
+// Layout of one codeword's BP4 state and the kernel variant that runs on it.
+struct Bp4Plan {
+    size_t lds_bytes;  // dynamic LDS of the launch (0 for the global-memory variant)
+    bool gmem;         // the codeword's state lives in a global-memory workspace row (bp4_kernel<..., GMEM>)
+    size_t ws_bytes;   // that workspace: one row of lds_per_cw floats per codeword
+};
+
 template <int CN_TYPE>
-int launch_bp4(const fgnn_graph* g, const BpArgs& a, const LaunchGeom& L, size_t lds_bytes, hipStream_t st)
+int launch_bp4(const fgnn_graph* g, const BpArgs& a, const LaunchGeom& L, const Bp4Plan& p, hipStream_t st)
 {
+    if (p.gmem)
+        return fgnn_launch(bp4_kernel<CN_TYPE, 0, 0, 0, false, false, 0, false, true>, dim3(L.blocks), dim3(L.threads), 0, st, g->d, a);
     const GraphDev& d = g->d;
     if (d.cslot16 && !g->force_generic) {
-        if (d.dvx == 3 && d.dvz == 3 && d.dc == 6) return launch_bp4_k<CN_TYPE, 3, 3, 6>(g, a, L, lds_bytes, st);
-        if (d.dvx == 4 && d.dvz == 4 && d.dc == 8 && !a.trace_x) return launch_bp4_k<CN_TYPE, 4, 4, 8>(g, a, L, lds_bytes, st);
+        if (d.dvx == 3 && d.dvz == 3 && d.dc == 6) return launch_bp4_k<CN_TYPE, 3, 3, 6>(g, a, L, p.lds_bytes, st);
+        if (d.dvx == 4 && d.dvz == 4 && d.dc == 8 && !a.trace_x) return launch_bp4_k<CN_TYPE, 4, 4, 8>(g, a, L, p.lds_bytes, st);
     }
-    return launch_bp4_k<CN_TYPE, 0, 0, 0>(g, a, L, lds_bytes, st);
+    return launch_bp4_k<CN_TYPE, 0, 0, 0>(g, a, L, p.lds_bytes, st);
+}
+
+// Fills the layout and variant fields of `a` (lch_off, lreg, trace_off, sig_off, early_exit, flag_off, lds_per_cw, shortcut, hwt,
+// shared_lse) from the graph, its options and the optional buffers set in `a`.  A codeword whose state does not fit a CU's LDS is
+// planned again with gmem = true: no LDS budget, one global-memory workspace row per codeword.
+Bp4Plan plan_bp4(const fgnn_graph* g, int cn_type, const LaunchGeom& L, BpArgs& a, bool gmem = false)
+{
+    const GraphDev& d = g->d;
+    const int n = d.n;
+    const bool trace = a.trace_x != nullptr, phi = cn_type == FGNN_CN_BOXPLUS_PHI;
+    auto round4 = [](int floats) { return (floats + 3) & ~3; };
+    a.shared_lse = g->bp4_shared_lse ? 1 : 0;
+    // the trace and global-memory variants are the fixed dataflow on the shared float32 routines, channel LLRs in LDS / the workspace
+    a.hwt = (g->hw_transcendentals && phi && !trace && !gmem) ? 1 : 0;
+    a.shortcut = (g->shortcut && !a.hwt && !trace && !gmem) ? 1 : 0;
+    // floats per codeword: messages (>= 2n so the epilogue's binary LLRs fit) + channel LLRs (unless they fit the registers of
+    // the NQ variant: regular (3,3,6) graph, phi rule, exact math, one codeword per workgroup, 4 or 5 qubits per thread)
+    a.lch_off = d.E > 2 * n ? d.E : 2 * n;
+    const int per_thread = (n + L.tpc - 1) / L.tpc;
+    const bool r336 = d.cslot16 && !g->force_generic && d.dvx == 3 && d.dvz == 3 && d.dc == 6;
+    a.lreg = (a.llr_ch && !trace && !a.hwt && !gmem && phi && L.cpb == 1 && r336 && per_thread <= 5) ? (per_thread <= 4 ? 4 : 5) : 0;
+    int per = a.lch_off + ((a.llr_ch && !a.lreg) ? 3 * n : 0);
+    a.trace_off = 0;
+    if (trace) {  // 2n binary LLRs of the per-iteration soft syndromes, behind the messages and the channel LLRs
+        a.trace_off = per;
+        per += 2 * n;
+    }
+    // LDS: the workgroup's codeword rows are 4-float aligned and the detector words and the decision bytes follow them (one codeword
+    // per workgroup); GMEM: the workspace row holds all of it and is aligned as a whole
+    if (!gmem) per = round4(per);
+    a.sig_off = per;
+    int tail = 0;  // floats behind the codeword rows
+    a.early_exit = (a.shortcut && g->early_exit && d.max_vdeg <= 32 && phi && L.cpb == 1 && a.num_iter > 2) ? 1 : 0;
+    if (a.early_exit) {  // the fixed-point detector's n sign words + 4 flags, if they fit
+        if (((size_t)per * L.cpb + n + 4) * sizeof(float) <= FGNN_LDS_BUDGET) tail += n + 4;
+        else a.early_exit = 0;
+    }
+    a.flag_off = 0;
+    if (a.flagged) {  // n decision bytes + one word: inside the message area (behind the 2n floats the soft-syndrome epilogue
+                      // reuses) when it is large enough, else behind everything else
+        const int need = round4(n) / 4 + 1;
+        if (a.lch_off >= 2 * n + need) {
+            a.flag_off = 2 * n;
+        } else {
+            a.flag_off = per + tail;
+            tail += need;
+        }
+    }
+    if (gmem) {
+        a.lds_per_cw = round4(per + tail);
+        return {0, true, (size_t)L.blocks * (size_t)a.lds_per_cw * sizeof(float)};
+    }
+    a.lds_per_cw = per;
+    const size_t lds_bytes = ((size_t)per * L.cpb + tail) * sizeof(float);
+    if (lds_bytes > FGNN_LDS_BUDGET) return plan_bp4(g, cn_type, L, a, true);
+    return {lds_bytes, false, 0};
 }
 
 }  // namespace
@@ -978,7 +1035,6 @@ static int bp4_decode_core(const fgnn_graph* g, int cn_type, int num_iter, float
                            float* z_logit, float* msg_out_x, float* msg_out_z, const int* index, uint8_t* flagged,
                            float* trace_x, float* trace_z, float* tape_x, float* tape_z, void* stream)
 {
-    const bool trace = trace_x != nullptr;
     if (!g) return fgnn_fail(FGNN_ERR_ARG, "graph is NULL");
     if (B < 0 || num_iter < 0) return fgnn_fail(FGNN_ERR_ARG, "B and num_iter must be >= 0");
     if (cn_type < 0 || cn_type > 2) return fgnn_fail(FGNN_ERR_ARG, "Unknown node type.");  // decoding_q.py:107
@@ -987,7 +1043,8 @@ static int bp4_decode_core(const fgnn_graph* g, int cn_type, int num_iter, float
     if (B == 0) return FGNN_OK;  // an empty batch needs no buffers (an empty torch tensor's data pointer is NULL)
     if (!synd_x || !synd_z || !llr_out || !x_hat || !z_hat) return fgnn_fail(FGNN_ERR_ARG, "required buffer is NULL");
     FGNN_DEVICE_GUARD(g->device);
-    LaunchGeom L = fgnn_geom(g, B);
+    const LaunchGeom L = fgnn_geom(g, B);
+    if (flagged && L.cpb != 1) return fgnn_fail(FGNN_ERR_STATE, "the fused flag test needs one codeword per workgroup");
     BpArgs a;
     a.B = B;
     a.num_iter = num_iter;
@@ -1008,123 +1065,44 @@ static int bp4_decode_core(const fgnn_graph* g, int cn_type, int num_iter, float
     a.msg_out_x = msg_out_x;
     a.msg_out_z = msg_out_z;
     a.index = index;
+    a.flagged = flagged;
+    a.gmem = nullptr;
     a.trace_x = trace_x;
     a.trace_z = trace_z;
-    a.trace_off = 0;
     a.tape_x = tape_x;
     a.tape_z = tape_z;
-    a.gmem = nullptr;
-    a.shared_lse = g->bp4_shared_lse ? 1 : 0;
-    // the trace variant is the fixed dataflow on the shared float32 routines, channel LLRs in LDS
-    a.hwt = (g->hw_transcendentals && cn_type == FGNN_CN_BOXPLUS_PHI && !trace) ? 1 : 0;
-    a.shortcut = (g->shortcut && !a.hwt && !trace) ? 1 : 0;
-    // floats per codeword: messages (>= 2n so the epilogue's binary LLRs fit) + channel LLRs (unless they fit the registers of
-    // the NQ variant: regular (3,3,6) graph, phi rule, exact math, one codeword per workgroup, 4 or 5 qubits per thread)
-    a.lch_off = g->d.E > 2 * g->d.n ? g->d.E : 2 * g->d.n;
-    a.lreg = 0;
-    {
-        static const bool no_lreg = getenv("FGNN_BP4_NO_LREG") != nullptr;  // A/B knob (tools/ab_bp4_lch.py)
-        const int per_thread = (g->d.n + L.tpc - 1) / L.tpc;
-        if (llr_ch && !no_lreg && !trace && !a.hwt && cn_type == FGNN_CN_BOXPLUS_PHI && L.cpb == 1 && g->d.cslot16 && !g->force_generic &&
-            g->d.dvx == 3 && g->d.dvz == 3 && g->d.dc == 6 && per_thread <= 5)
-            a.lreg = per_thread <= 4 ? 4 : 5;
-    }
-    int per_cw = a.lch_off + ((llr_ch && !a.lreg) ? 3 * g->d.n : 0);
-    if (trace) {  // 2n binary LLRs of the per-iteration soft syndromes, behind the messages and the channel LLRs
-        a.trace_off = per_cw;
-        per_cw += 2 * g->d.n;
-    }
-    per_cw = (per_cw + 3) & ~3;
-    a.lds_per_cw = per_cw;
-    size_t lds_bytes = (size_t)per_cw * sizeof(float) * (size_t)L.cpb;
-    const bool regular = g->d.cslot16 && !g->force_generic &&
-                         ((g->d.dvx == 3 && g->d.dvz == 3 && g->d.dc == 6) || (g->d.dvx == 4 && g->d.dvz == 4 && g->d.dc == 8));
-    (void)regular;
-    a.early_exit = (a.shortcut && g->early_exit && g->d.max_vdeg <= 32 && cn_type == FGNN_CN_BOXPLUS_PHI && L.cpb == 1 &&
-                    num_iter > 2) ? 1 : 0;
-    a.sig_off = per_cw;
-    if (a.early_exit) {
-        const size_t with_det = lds_bytes + ((size_t)g->d.n + 4) * sizeof(float);
-        if (with_det <= FGNN_LDS_BUDGET) lds_bytes = with_det;
-        else a.early_exit = 0;
-    }
-    a.flagged = flagged;
-    a.flag_off = 0;
-    if (flagged) {  // n decision bytes + one word per codeword: inside the message area (behind the 2n floats the soft-syndrome
-                    // epilogue reuses) when it is large enough, else behind everything else
-        if (L.cpb != 1) return fgnn_fail(FGNN_ERR_STATE, "the fused flag test needs one codeword per workgroup");
-        const size_t need = (size_t)((g->d.n + 3) & ~3) + sizeof(unsigned);
-        if ((size_t)a.lch_off * sizeof(float) >= (size_t)2 * g->d.n * sizeof(float) + need) {
-            a.flag_off = 2 * g->d.n;
-        } else {
-            a.flag_off = (int)(lds_bytes / sizeof(float));
-            lds_bytes += need;
-        }
-    }
-    {  // experiment knob (tools/ab_bp4_lch.py): pad the dynamic LDS to lower the number of resident workgroups
-        static const long pad = getenv("FGNN_BP4_LDS_PAD") ? atol(getenv("FGNN_BP4_LDS_PAD")) : 0;
-        if (pad > 0 && lds_bytes + (size_t)pad <= FGNN_LDS_BUDGET) lds_bytes += (size_t)pad;
-    }
+    const Bp4Plan p = plan_bp4(g, cn_type, L, a);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (lds_bytes > FGNN_LDS_BUDGET) {
+    if (p.gmem) {
         // The codeword's state does not fit a CU's LDS (about E + 3n > 40 000 floats): run the same runtime-degree kernel with that
         // state in a global-memory workspace row per workgroup slot (bp4_kernel<..., GMEM>).  Fixed dataflow, float32 routines of
         // fgnn_math.h, no trace: the reference's tensors are in device memory too, so this is its dataflow with the iterations fused
         // into one launch.  The workspace is stream-ordered (allocated and freed on the caller's stream, no synchronisation).
-        if (trace) return fgnn_fail(FGNN_ERR_ARG, "code too large for the LDS-resident trace kernel");
+        if (trace_x) return fgnn_fail(FGNN_ERR_ARG, "code too large for the LDS-resident trace kernel");
         if (L.cpb != 1) return fgnn_fail(FGNN_ERR_STATE, "the global-memory BP4 variant needs one codeword per workgroup");
-        a.shortcut = a.early_exit = a.hwt = a.lreg = 0;
-        int per = a.lch_off + (llr_ch ? 3 * g->d.n : 0);
-        a.sig_off = per;
-        if (flagged) {  // n decision bytes + one word, behind the 2n floats the soft-syndrome epilogue reuses when they fit, else behind everything
-            const size_t need = (size_t)((g->d.n + 3) & ~3) + sizeof(unsigned);
-            if ((size_t)a.lch_off * sizeof(float) >= (size_t)2 * g->d.n * sizeof(float) + need) a.flag_off = 2 * g->d.n;
-            else {
-                a.flag_off = per;
-                per += (int)((need + sizeof(float) - 1) / sizeof(float));
-            }
-        }
-        per = (per + 3) & ~3;
-        a.lds_per_cw = per;
-        const size_t ws_bytes = (size_t)L.blocks * (size_t)per * sizeof(float);
+        const size_t row_bytes = (size_t)a.lds_per_cw * sizeof(float);
         {   // one workspace row per codeword of the launch (254 KB for a [[6480,1296]] code): say so before an allocation of that size
             // fails as a bare HIP error — the caller decodes in smaller batches
             size_t free_b = 0, total_b = 0;
-            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && ws_bytes > free_b)
+            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && p.ws_bytes > free_b)
                 return fgnn_fail(FGNN_ERR_ARG, "code too large for the LDS-resident kernel: the global-memory variant needs " +
-                                                   std::to_string(ws_bytes >> 20) + " MiB of workspace for " + std::to_string(B) +
-                                                   " codewords (" + std::to_string((size_t)per * sizeof(float) >> 10) + " KiB each) and " +
+                                                   std::to_string(p.ws_bytes >> 20) + " MiB of workspace for " + std::to_string(B) +
+                                                   " codewords (" + std::to_string(row_bytes >> 10) + " KiB each) and " +
                                                    std::to_string(free_b >> 20) + " MiB are free: decode in batches of at most " +
-                                                   std::to_string(free_b / ((size_t)per * sizeof(float) * 2)) + " codewords");
+                                                   std::to_string(free_b / (row_bytes * 2)) + " codewords");
         }
         void* ws = nullptr;
-        FGNN_HIP_CHECK(hipMallocAsync(&ws, ws_bytes, st));
+        FGNN_HIP_CHECK(hipMallocAsync(&ws, p.ws_bytes, st));
         a.gmem = static_cast<float*>(ws);
-        fgnn_prof_scope prof(g, st);
-        switch (cn_type) {
-        case FGNN_CN_BOXPLUS_PHI:
-            hipLaunchKernelGGL((bp4_kernel<FGNN_CN_BOXPLUS_PHI, 0, 0, 0, false, false, 0, false, true>), dim3(L.blocks), dim3(L.threads), 0, st, g->d, a);
-            break;
-        case FGNN_CN_MINSUM:
-            hipLaunchKernelGGL((bp4_kernel<FGNN_CN_MINSUM, 0, 0, 0, false, false, 0, false, true>), dim3(L.blocks), dim3(L.threads), 0, st, g->d, a);
-            break;
-        default:
-            hipLaunchKernelGGL((bp4_kernel<FGNN_CN_BOXPLUS, 0, 0, 0, false, false, 0, false, true>), dim3(L.blocks), dim3(L.threads), 0, st, g->d, a);
-            break;
-        }
-        const hipError_t launched = hipGetLastError();
-        (void)hipFreeAsync(ws, st);
-        FGNN_HIP_CHECK(launched);
-        prof.done(num_iter, B);
-        return FGNN_OK;
     }
     fgnn_prof_scope prof(g, st);
     int rc;
     switch (cn_type) {
-    case FGNN_CN_BOXPLUS_PHI: rc = launch_bp4<FGNN_CN_BOXPLUS_PHI>(g, a, L, lds_bytes, st); break;
-    case FGNN_CN_MINSUM: rc = launch_bp4<FGNN_CN_MINSUM>(g, a, L, lds_bytes, st); break;
-    default: rc = launch_bp4<FGNN_CN_BOXPLUS>(g, a, L, lds_bytes, st); break;
+    case FGNN_CN_BOXPLUS_PHI: rc = launch_bp4<FGNN_CN_BOXPLUS_PHI>(g, a, L, p, st); break;
+    case FGNN_CN_MINSUM: rc = launch_bp4<FGNN_CN_MINSUM>(g, a, L, p, st); break;
+    default: rc = launch_bp4<FGNN_CN_BOXPLUS>(g, a, L, p, st); break;
     }
+    if (a.gmem) (void)hipFreeAsync(a.gmem, st);
     if (rc == FGNN_OK) prof.done(num_iter, B);
     return rc;
 }

@@ -317,10 +317,8 @@ extern "C" int fgnn_pack_decisions(const uint8_t* x_hat, const uint8_t* z_hat, i
     if (!x_hat || !z_hat || !packed) return fgnn_fail(FGNN_ERR_ARG, "bad pack arguments");
     const int nb = (2 * n + 7) / 8;
     const long long total = (long long)B * nb;
-    hipLaunchKernelGGL(pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), x_hat,
+    return fgnn_launch(pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), x_hat,
                        z_hat, total, n, nb, packed);
-    FGNN_HIP_CHECK(hipGetLastError());
-    return FGNN_OK;
 }
 
 extern "C" int fgnn_unpack_decisions(const uint8_t* packed, int B, int n, uint8_t* x_hat, uint8_t* z_hat, void* stream)
@@ -330,10 +328,8 @@ extern "C" int fgnn_unpack_decisions(const uint8_t* packed, int B, int n, uint8_
     if (!x_hat || !z_hat || !packed) return fgnn_fail(FGNN_ERR_ARG, "bad unpack arguments");
     const int nb = (2 * n + 7) / 8;
     const long long total = (long long)B * 2 * n;
-    hipLaunchKernelGGL(unpack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), packed,
+    return fgnn_launch(unpack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), packed,
                        total, n, nb, x_hat, z_hat);
-    FGNN_HIP_CHECK(hipGetLastError());
-    return FGNN_OK;
 }
 
 extern "C" int fgnn_pauli_noise(uint64_t seed, float p, uint64_t first_sample, int B, int n, uint8_t* noise_x,
@@ -344,11 +340,9 @@ extern "C" int fgnn_pauli_noise(uint64_t seed, float p, uint64_t first_sample, i
     if (!noise_x || !noise_z) return fgnn_fail(FGNN_ERR_ARG, "bad noise arguments");
     const int nblk = (n + 3) / 4;
     const long long total = (long long)B * nblk;
-    hipLaunchKernelGGL(pauli_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), seed,
+    return fgnn_launch(pauli_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), seed,
                        p, fg_pauli_thr{0.0f, 0.0f, 0.0f}, first_sample, static_cast<const unsigned long long*>(nullptr), B, n, nblk,
                        noise_x, noise_z);
-    FGNN_HIP_CHECK(hipGetLastError());
-    return FGNN_OK;
 }
 
 extern "C" int fgnn_pauli_noise_xyz(uint64_t seed, float px, float py, float pz, uint64_t first_sample, int B, int n,
@@ -361,11 +355,9 @@ extern "C" int fgnn_pauli_noise_xyz(uint64_t seed, float px, float py, float pz,
     if (!noise_x || !noise_z) return fgnn_fail(FGNN_ERR_ARG, "bad noise arguments");
     const int nblk = (n + 3) / 4;
     const long long total = (long long)B * nblk;
-    hipLaunchKernelGGL(pauli_kernel<true>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), seed,
+    return fgnn_launch(pauli_kernel<true>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), seed,
                        0.0f, fg_pauli_thresholds_xyz(px, py, pz), first_sample, static_cast<const unsigned long long*>(nullptr), B, n,
                        nblk, noise_x, noise_z);
-    FGNN_HIP_CHECK(hipGetLastError());
-    return FGNN_OK;
 }
 
 extern "C" int fgnn_pauli_noise_dev(uint64_t seed, float p, const uint64_t* first_sample_dev, uint64_t offset, int B, int n,
@@ -376,11 +368,9 @@ extern "C" int fgnn_pauli_noise_dev(uint64_t seed, float p, const uint64_t* firs
     if (!noise_x || !noise_z || !first_sample_dev) return fgnn_fail(FGNN_ERR_ARG, "bad noise arguments");
     const int nblk = (n + 3) / 4;
     const long long total = (long long)B * nblk;
-    hipLaunchKernelGGL(pauli_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), seed,
+    return fgnn_launch(pauli_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), seed,
                        p, fg_pauli_thr{0.0f, 0.0f, 0.0f}, offset, reinterpret_cast<const unsigned long long*>(first_sample_dev), B, n,
                        nblk, noise_x, noise_z);
-    FGNN_HIP_CHECK(hipGetLastError());
-    return FGNN_OK;
 }
 
 extern "C" int fgnn_pauli_noise_wt(uint64_t seed, int wt, uint64_t first_sample, int B, int n, uint8_t* noise_x, uint8_t* noise_z,
@@ -389,10 +379,8 @@ extern "C" int fgnn_pauli_noise_wt(uint64_t seed, int wt, uint64_t first_sample,
     if (B < 0 || n <= 0 || n > 65535 || wt < 0 || wt > n) return fgnn_fail(FGNN_ERR_ARG, "bad fixed-weight noise arguments");
     if (B == 0) return FGNN_OK;
     if (!noise_x || !noise_z) return fgnn_fail(FGNN_ERR_ARG, "bad fixed-weight noise arguments");
-    hipLaunchKernelGGL(pauli_wt_kernel, dim3((B + 3) / 4), dim3(256), (size_t)4 * n * sizeof(unsigned short),
+    return fgnn_launch(pauli_wt_kernel, dim3((B + 3) / 4), dim3(256), (size_t)4 * n * sizeof(unsigned short),
                        static_cast<hipStream_t>(stream), seed, wt, first_sample, B, n, noise_x, noise_z);
-    FGNN_HIP_CHECK(hipGetLastError());
-    return FGNN_OK;
 }
 
 extern "C" int fgnn_syndrome(const fgnn_graph* g, const uint8_t* noise_x, const uint8_t* noise_z, int B, uint8_t* synd_x,
@@ -404,10 +392,8 @@ extern "C" int fgnn_syndrome(const fgnn_graph* g, const uint8_t* noise_x, const 
     FGNN_DEVICE_GUARD(g->device);
     LaunchGeom L = fgnn_geom(g, B);
     size_t lds = (size_t)L.cpb * 2 * g->d.n;
-    hipLaunchKernelGGL(syndrome_kernel, dim3(L.blocks), dim3(L.threads), lds, static_cast<hipStream_t>(stream), g->d, B, L.tpc,
+    return fgnn_launch(syndrome_kernel, dim3(L.blocks), dim3(L.threads), lds, static_cast<hipStream_t>(stream), g->d, B, L.tpc,
                        L.cpb, noise_x, noise_z, synd_x, synd_z);
-    FGNN_HIP_CHECK(hipGetLastError());
-    return FGNN_OK;
 }
 
 int fgnn_flag_update_impl(const fgnn_graph* g, const uint8_t* x_hat, const uint8_t* z_hat, const uint8_t* synd_x,
@@ -419,10 +405,8 @@ int fgnn_flag_update_impl(const fgnn_graph* g, const uint8_t* x_hat, const uint8
     FGNN_DEVICE_GUARD(g->device);
     LaunchGeom L = fgnn_geom(g, B);
     size_t lds = ((L.cpb * sizeof(unsigned) + 15) & ~size_t(15)) + (size_t)L.cpb * 2 * g->d.n;
-    hipLaunchKernelGGL(flag_kernel, dim3(L.blocks), dim3(L.threads), lds, static_cast<hipStream_t>(stream), g->d, B, L.tpc, L.cpb,
+    return fgnn_launch(flag_kernel, dim3(L.blocks), dim3(L.threads), lds, static_cast<hipStream_t>(stream), g->d, B, L.tpc, L.cpb,
                        x_hat, z_hat, synd_x, synd_z, errors, index);
-    FGNN_HIP_CHECK(hipGetLastError());
-    return FGNN_OK;
 }
 
 extern "C" int fgnn_flag_update(const fgnn_graph* g, const uint8_t* x_hat, const uint8_t* z_hat, const uint8_t* synd_x,
@@ -438,10 +422,8 @@ int fgnn_merge_impl(const uint8_t* errors, const uint8_t* x_upd, const uint8_t* 
     if (B == 0) return FGNN_OK;
     if (!errors || !x_upd || !z_upd || !x_hat || !z_hat) return fgnn_fail(FGNN_ERR_ARG, "bad merge arguments");
     const long long total = (long long)B * n;
-    hipLaunchKernelGGL(merge_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), errors,
+    return fgnn_launch(merge_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), errors,
                        x_upd, z_upd, total, n, x_hat, z_hat, index);
-    FGNN_HIP_CHECK(hipGetLastError());
-    return FGNN_OK;
 }
 
 extern "C" int fgnn_merge(const uint8_t* errors, const uint8_t* x_upd, const uint8_t* z_upd, int B, int n, uint8_t* x_hat,
@@ -462,10 +444,8 @@ extern "C" int fgnn_residual_rows(const fgnn_graph* g, int rows_x, int rows_z, c
     FGNN_DEVICE_GUARD(g->device);
     LaunchGeom L = fgnn_geom(g, B);
     size_t lds = ((L.cpb * sizeof(unsigned) + 15) & ~size_t(15)) + (size_t)L.cpb * 2 * g->d.n;
-    hipLaunchKernelGGL(residual_kernel, dim3(L.blocks), dim3(L.threads), lds, static_cast<hipStream_t>(stream), g->d, rows_x, rows_z, B,
+    return fgnn_launch(residual_kernel, dim3(L.blocks), dim3(L.threads), lds, static_cast<hipStream_t>(stream), g->d, rows_x, rows_z, B,
                        L.tpc, L.cpb, noise_x, noise_z, x_hat, z_hat, s_hat, ls_hat, flags);
-    FGNN_HIP_CHECK(hipGetLastError());
-    return FGNN_OK;
 }
 
 extern "C" int fgnn_residual(const fgnn_graph* g, const uint8_t* noise_x, const uint8_t* noise_z, const uint8_t* x_hat,
@@ -480,12 +460,10 @@ extern "C" int fgnn_count_flags_batches(const uint8_t* flags, int num_batches, i
     if (!flags || !counts || !ring || !scratch || num_batches < 0 || batch <= 0) return fgnn_fail(FGNN_ERR_ARG, "bad count arguments");
     if (num_batches == 0) return FGNN_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(count_batches_kernel, dim3(num_batches), dim3(256), 0, st, flags, batch, scratch);
-    FGNN_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(count_scan_kernel, dim3(1), dim3(64), 0, st, scratch, num_batches, batch,
+    const int rc = fgnn_launch(count_batches_kernel, dim3(num_batches), dim3(256), 0, st, flags, batch, scratch);
+    if (rc) return rc;
+    return fgnn_launch(count_scan_kernel, dim3(1), dim3(64), 0, st, scratch, num_batches, batch,
                        reinterpret_cast<unsigned long long*>(counts), reinterpret_cast<unsigned long long*>(ring));
-    FGNN_HIP_CHECK(hipGetLastError());
-    return FGNN_OK;
 }
 
 extern "C" int fgnn_count_flags(const uint8_t* flags, int B, uint64_t* counts, void* stream)
@@ -495,8 +473,6 @@ extern "C" int fgnn_count_flags(const uint8_t* flags, int B, uint64_t* counts, v
     if (!flags) return fgnn_fail(FGNN_ERR_ARG, "bad count arguments");
     int blocks = (B + 255) / 256;
     if (blocks > 1024) blocks = 1024;
-    hipLaunchKernelGGL(count_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), flags, B,
+    return fgnn_launch(count_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), flags, B,
                        reinterpret_cast<unsigned long long*>(counts));
-    FGNN_HIP_CHECK(hipGetLastError());
-    return FGNN_OK;
 }

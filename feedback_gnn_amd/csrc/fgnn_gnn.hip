@@ -956,11 +956,10 @@ int fgnn_feedback_gnn_impl(const fgnn_graph* g, const fgnn_weights* w, const flo
     fgnn_prof_scope prof(g, static_cast<hipStream_t>(stream));
     if (w->general) {
         size_t lds_gen = (size_t)a.lds_per_cw * sizeof(float) * (size_t)L.cpb;
-        hipLaunchKernelGGL(gnn_general_kernel, dim3(L.blocks), dim3(L.threads), lds_gen, static_cast<hipStream_t>(stream), g->d,
-                           w->gen, a);
-        FGNN_HIP_CHECK(hipGetLastError());
-        prof.done(FGNN_PROF_TAG_GNN, B);
-        return FGNN_OK;
+        const int rc = fgnn_launch(gnn_general_kernel, dim3(L.blocks), dim3(L.threads), lds_gen, static_cast<hipStream_t>(stream), g->d,
+                                   w->gen, a);
+        if (rc == FGNN_OK) prof.done(FGNN_PROF_TAG_GNN, B);
+        return rc;
     }
     // Below ~4 000 codewords the launch is latency-bound, and there the MFMA-tile kernel, which deals one codeword's tiles to many waves,
     // is up to 3x quicker (18 vs 52 us for <= 64 codewords of [[882,24]]; equal from 256 to 2 048; the streaming kernel wins from 4 096 on:
@@ -990,10 +989,9 @@ int fgnn_feedback_gnn_impl(const fgnn_graph* g, const fgnn_weights* w, const flo
         constexpr bool PF = FGNN_GNNS_EMBPK_FACT != 0, PL = FGNN_GNNS_EMBPK_LIT != 0;
         auto skern = g->gnn_factored ? (g->d.dvx == 3 ? gnn_stream_kernel<3, false, PF> : g->d.dvx == 4 ? gnn_stream_kernel<4, false, PF> : gnn_stream_kernel<5, false, PF>)
                                      : (g->d.dvx == 3 ? gnn_stream_kernel<3, true, PL> : g->d.dvx == 4 ? gnn_stream_kernel<4, true, PL> : gnn_stream_kernel<5, true, PL>);
-        hipLaunchKernelGGL(skern, dim3((unsigned)B), dim3(best_tpc), lds_s, static_cast<hipStream_t>(stream), g->d, w->d, a);
-        FGNN_HIP_CHECK(hipGetLastError());
-        prof.done(FGNN_PROF_TAG_GNN, B);
-        return FGNN_OK;
+        const int rc = fgnn_launch(skern, dim3((unsigned)B), dim3(best_tpc), lds_s, static_cast<hipStream_t>(stream), g->d, w->d, a);
+        if (rc == FGNN_OK) prof.done(FGNN_PROF_TAG_GNN, B);
+        return rc;
     }
     if (g->d.dvx == 3 && g->d.dvz == 3 && !g->force_generic) {
         // degree-regular graph: MFMA kernel, four waves per codeword, GNN_CPB codewords per workgroup
@@ -1005,21 +1003,16 @@ int fgnn_feedback_gnn_impl(const fgnn_graph* g, const fgnn_weights* w, const flo
         while (a.nsplit < 16 && (long long)B * a.nsplit * 2 <= 2048 && a.nsplit * 4 < ntiles) a.nsplit *= 2;
         const size_t lds_mfma = (size_t)(T_COUNT * 64 + GNN_CPB * a.lds_per_cw) * sizeof(float);
         auto kern = g->gnn_factored ? gnn_mfma_kernel<3, GNN_CPB, true> : gnn_mfma_kernel<3, GNN_CPB, false>;
-        if (lds_mfma > 48 * 1024)
-            FGNN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)lds_mfma));
-        hipLaunchKernelGGL(kern, dim3((unsigned)(((long long)B * a.nsplit + GNN_CPB - 1) / GNN_CPB)), dim3(256 * GNN_CPB), lds_mfma,
-                           static_cast<hipStream_t>(stream), g->d, w->d, a);
-        FGNN_HIP_CHECK(hipGetLastError());
-        prof.done(FGNN_PROF_TAG_GNN, B);
-        return FGNN_OK;
+        const int rc = fgnn_launch(kern, dim3((unsigned)(((long long)B * a.nsplit + GNN_CPB - 1) / GNN_CPB)), dim3(256 * GNN_CPB),
+                                   lds_mfma, static_cast<hipStream_t>(stream), g->d, w->d, a);
+        if (rc == FGNN_OK) prof.done(FGNN_PROF_TAG_GNN, B);
+        return rc;
     }
     size_t lds_bytes = (size_t)a.lds_per_cw * sizeof(float) * (size_t)L.cpb;
-    hipLaunchKernelGGL(g->gnn_factored ? gnn_kernel<true> : gnn_kernel<false>, dim3(L.blocks), dim3(L.threads), lds_bytes,
-                       static_cast<hipStream_t>(stream), g->d, w->d, a);
-    FGNN_HIP_CHECK(hipGetLastError());
-    prof.done(FGNN_PROF_TAG_GNN, B);
-    return FGNN_OK;
+    const int rc = fgnn_launch(g->gnn_factored ? gnn_kernel<true> : gnn_kernel<false>, dim3(L.blocks), dim3(L.threads), lds_bytes,
+                               static_cast<hipStream_t>(stream), g->d, w->d, a);
+    if (rc == FGNN_OK) prof.done(FGNN_PROF_TAG_GNN, B);
+    return rc;
 }
 
 extern "C" int fgnn_feedback_gnn(const fgnn_graph* g, const fgnn_weights* w, const float* llr, const float* logit_hx,

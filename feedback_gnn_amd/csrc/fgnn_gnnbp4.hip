@@ -1347,20 +1347,6 @@ extern "C" size_t fgnn_gnnbp4_workspace_bytes(const fgnn_graph* g, int B)
     return (size_t)B * (size_t)(g->d.n + g->d.m) * D * sizeof(float);
 }
 
-// FGNN_OPT_GNN_STREAM for GNN_BP4 on a (3,3,6)-regular graph: only the explicit value 2 ("always") runs the streaming packed-FMA kernel.
-// Measured in round 4 (profiles/r4_gnnbp4_stream_ab.txt, r4_gnnbp4_stream_pmc_summary.txt): bit-equal to the MFMA-tile kernel in both
-// associations, and slower — 180 ms against 134 ms per 16 384 x 10 in the factored order, 212 against 193 in the literal one.  The
-// packed fma holds a SIMD for ~4.4 cycles per two multiply-adds, so the uniform-weight multiply-adds run at the f32 MFMA's rate minus
-// nothing: what the streaming form saves on the tiles' padded rows (24 % of the MFMA cycles) it pays back in the packed instruction's
-// 10 % issue overhead, a 70 KB weight stream through a 16 KB scalar cache (12 % misses; the MFMA kernel keeps its operands in LDS) and
-// three waves per SIMD of 168 VGPRs.  Both forms price at ~107-110 ms if issued perfectly; the MFMA kernel is at 83 % of that, the
-// streaming kernel at 60 %.  It stays in the library as the tested second implementation of the same float operations.
-static bool gnnbp4_takes_stream(const fgnn_graph* g, int B)
-{
-    (void)B;
-    return g->gnn_stream == 2;
-}
-
 extern "C" int fgnn_gnnbp4_decode(const fgnn_graph* g, const fgnn_gnnbp4_weights* w, int num_iter, const uint8_t* synd_x,
                                   const uint8_t* synd_z, int B, uint8_t* x_hat, uint8_t* z_hat, float* llr_out,
                                   float* x_logit_all, float* z_logit_all, void* workspace, size_t ws_bytes, void* stream)
@@ -1387,12 +1373,19 @@ extern "C" int fgnn_gnnbp4_decode(const fgnn_graph* g, const fgnn_gnnbp4_weights
     const size_t lds_bytes = (size_t)(2 * g->d.n + g->d.m) * sizeof(float);
     fgnn_prof_scope prof(g, static_cast<hipStream_t>(stream));
     if (w->general) {
-        hipLaunchKernelGGL(gnn_bp4_general_kernel, dim3(B), dim3(256), lds_bytes, static_cast<hipStream_t>(stream), g->d, w->gen, a);
-        FGNN_HIP_CHECK(hipGetLastError());
-        prof.done(FGNN_PROF_TAG_GNNBP4, B);
-        return FGNN_OK;
+        const int rc = fgnn_launch(gnn_bp4_general_kernel, dim3(B), dim3(256), lds_bytes, static_cast<hipStream_t>(stream), g->d, w->gen, a);
+        if (rc == FGNN_OK) prof.done(FGNN_PROF_TAG_GNNBP4, B);
+        return rc;
     }
-    if (g->d.dvx == 3 && g->d.dvz == 3 && g->d.dc == 6 && !g->force_generic && gnnbp4_takes_stream(g, B)) {
+    // FGNN_OPT_GNN_STREAM for GNN_BP4 on a (3,3,6)-regular graph: only the explicit value 2 ("always") runs the streaming packed-FMA kernel.
+    // Measured in round 4 (profiles/r4_gnnbp4_stream_ab.txt, r4_gnnbp4_stream_pmc_summary.txt): bit-equal to the MFMA-tile kernel in both
+    // associations, and slower — 180 ms against 134 ms per 16 384 x 10 in the factored order, 212 against 193 in the literal one.  The
+    // packed fma holds a SIMD for ~4.4 cycles per two multiply-adds, so the uniform-weight multiply-adds run at the f32 MFMA's rate minus
+    // nothing: what the streaming form saves on the tiles' padded rows (24 % of the MFMA cycles) it pays back in the packed instruction's
+    // 10 % issue overhead, a 70 KB weight stream through a 16 KB scalar cache (12 % misses; the MFMA kernel keeps its operands in LDS) and
+    // three waves per SIMD of 168 VGPRs.  Both forms price at ~107-110 ms if issued perfectly; the MFMA kernel is at 83 % of that, the
+    // streaming kernel at 60 %.  It stays in the library as the tested second implementation of the same float operations.
+    if (g->d.dvx == 3 && g->d.dvz == 3 && g->d.dc == 6 && !g->force_generic && g->gnn_stream == 2) {
         const size_t lds_s = (size_t)(2 * g->d.n + 2 * g->d.m) * sizeof(float);
         if (lds_s > FGNN_LDS_BUDGET) return fgnn_fail(FGNN_ERR_ARG, "code too large for the GNN_BP4 streaming kernel");
         auto kern = g->gnn_factored ? gnn_bp4_stream_kernel<3, 6, true> : gnn_bp4_stream_kernel<3, 6, false>;
@@ -1403,12 +1396,9 @@ extern "C" int fgnn_gnnbp4_decode(const fgnn_graph* g, const fgnn_gnnbp4_weights
             for (MlpDev* q : {&wd.cn_msg[0], &wd.cn_msg[1], &wd.cn_embed[0], &wd.cn_embed[1], &wd.vn_msg[1], &wd.vn_embed}) *q = wd.vn_msg[0];
         }
 #endif
-        if (lds_s > 48 * 1024)
-            FGNN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s));
-        hipLaunchKernelGGL(kern, dim3(B), dim3(256), lds_s, static_cast<hipStream_t>(stream), g->d, wd, a);
-        FGNN_HIP_CHECK(hipGetLastError());
-        prof.done(FGNN_PROF_TAG_GNNBP4, B);
-        return FGNN_OK;
+        const int rc = fgnn_launch(kern, dim3(B), dim3(256), lds_s, static_cast<hipStream_t>(stream), g->d, wd, a);
+        if (rc == FGNN_OK) prof.done(FGNN_PROF_TAG_GNNBP4, B);
+        return rc;
     }
     if (g->d.dvx == 3 && g->d.dvz == 3 && g->d.dc == 6 && !g->force_generic) {
         const int cn_entries = w->d.tab_vn_msg[0] - w->d.tab_cn_msg[0], vn_entries = w->d.tab_inv + 8 - w->d.tab_vn_msg[0];
@@ -1418,15 +1408,12 @@ extern "C" int fgnn_gnnbp4_decode(const fgnn_graph* g, const fgnn_gnnbp4_weights
         const size_t lds2 = fixed + (size_t)tab_floats * sizeof(float);
         auto kern = g->gnn_factored ? gnn_bp4_mfma_kernel<3, 6, true> : gnn_bp4_mfma_kernel<3, 6, false>;
         if (lds2 > FGNN_LDS_BUDGET) return fgnn_fail(FGNN_ERR_ARG, "code too large for the GNN_BP4 MFMA kernel");
-        FGNN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
-        hipLaunchKernelGGL(kern, dim3(B), dim3(FGNN_GNNBP4_THREADS), lds2, static_cast<hipStream_t>(stream), g->d, w->d, a, tab_floats, resident);
-        FGNN_HIP_CHECK(hipGetLastError());
-        prof.done(FGNN_PROF_TAG_GNNBP4, B);
-        return FGNN_OK;
+        const int rc = fgnn_launch(kern, dim3(B), dim3(FGNN_GNNBP4_THREADS), lds2, static_cast<hipStream_t>(stream), g->d, w->d, a, tab_floats, resident);
+        if (rc == FGNN_OK) prof.done(FGNN_PROF_TAG_GNNBP4, B);
+        return rc;
     }
-    hipLaunchKernelGGL(g->gnn_factored ? gnn_bp4_kernel<true> : gnn_bp4_kernel<false>, dim3(B), dim3(256), lds_bytes,
-                       static_cast<hipStream_t>(stream), g->d, w->d, a);
-    FGNN_HIP_CHECK(hipGetLastError());
-    prof.done(FGNN_PROF_TAG_GNNBP4, B);
-    return FGNN_OK;
+    const int rc = fgnn_launch(g->gnn_factored ? gnn_bp4_kernel<true> : gnn_bp4_kernel<false>, dim3(B), dim3(256), lds_bytes,
+                               static_cast<hipStream_t>(stream), g->d, w->d, a);
+    if (rc == FGNN_OK) prof.done(FGNN_PROF_TAG_GNNBP4, B);
+    return rc;
 }

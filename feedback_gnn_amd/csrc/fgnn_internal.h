@@ -159,6 +159,17 @@ struct fgnn_prof_scope {
 // dynamic LDS a kernel may ask for: the CU's 160 KB minus the 256-byte log table of fgnn_math.h (static LDS)
 constexpr size_t FGNN_LDS_BUDGET = 160 * 1024 - 256;
 
+// One kernel launch: the dynamic-LDS attribute when the launch asks for more than 48 KiB, the launch, its error as FGNN_ERR_HIP.
+template <typename... Params, typename... Args>
+int fgnn_launch(void (*kern)(Params...), dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args)
+{
+    if (lds > 48 * 1024)
+        FGNN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, grid, block, lds, st, args...);
+    FGNN_HIP_CHECK(hipGetLastError());
+    return FGNN_OK;
+}
+
 // launch geometry shared by the per-codeword kernels
 struct LaunchGeom {
     int tpc, cpb, threads, blocks;

@@ -195,11 +195,7 @@ extern "C" int fgnn_osd0(const fgnn_graph* g, int side, const float* marg, const
     const size_t lds = sizeof(unsigned long long) * (size_t)a.NP + sizeof(unsigned) * (size_t)a.rank * a.WS +
                        sizeof(int) * (size_t)(2 * g->d.n + a.rank);
     if (lds > FGNN_LDS_BUDGET) return fgnn_fail(FGNN_ERR_ARG, "code too large for the LDS-resident OSD kernel");
-    if (lds > 48 * 1024)
-        FGNN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(osd0_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(osd0_kernel, dim3(count), dim3(256), lds, static_cast<hipStream_t>(stream), g->d, a);
-    FGNN_HIP_CHECK(hipGetLastError());
-    return FGNN_OK;
+    return fgnn_launch(osd0_kernel, dim3(count), dim3(256), lds, static_cast<hipStream_t>(stream), g->d, a);
 }
 
 // index[0..count) = ids of the samples with (mask[b] & bit) != 0; *count must be zeroed by the caller (device int).
@@ -208,8 +204,6 @@ extern "C" int fgnn_compact(const uint8_t* mask, int bit, int B, int32_t* index,
     if (!count || B < 0 || bit <= 0 || bit > 255) return fgnn_fail(FGNN_ERR_ARG, "bad compact arguments");
     if (B == 0) return FGNN_OK;
     if (!mask || !index) return fgnn_fail(FGNN_ERR_ARG, "bad compact arguments");
-    hipLaunchKernelGGL(compact_u8_kernel, dim3((B + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), mask, (uint8_t)bit, B,
+    return fgnn_launch(compact_u8_kernel, dim3((B + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), mask, (uint8_t)bit, B,
                        index, count);
-    FGNN_HIP_CHECK(hipGetLastError());
-    return FGNN_OK;
 }

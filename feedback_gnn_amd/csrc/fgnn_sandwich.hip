@@ -126,7 +126,8 @@ extern "C" int fgnn_sandwich_decode(const fgnn_graph* g, int num_layers, const i
                               nullptr, (fuse && !only) ? ws.errors : nullptr, stream);
     if (rc) return rc;
     const int blk = (B + 255) / 256;
-    if (num_layers > 1 && !fuse) hipLaunchKernelGGL(fill_u8, dim3(blk), dim3(256), 0, st, ws.errors, (uint8_t)1, B);  // (:322)
+    if (num_layers > 1 && !fuse) rc = fgnn_launch(fill_u8, dim3(blk), dim3(256), 0, st, ws.errors, (uint8_t)1, B);  // (:322)
+    if (rc) return rc;
     if (rounds) FGNN_HIP_CHECK(hipMemsetAsync(rounds, 0, (size_t)B, st));
     int listed = 0;  // compact mode: samples in ws.index from the previous round (the only ones whose estimate changed)
     for (int i = 1; i < num_layers; ++i) {
@@ -136,12 +137,14 @@ extern "C" int fgnn_sandwich_decode(const fgnn_graph* g, int num_layers, const i
             else rc = fgnn_flag_update(g, x_hat, z_hat, synd_x, synd_z, B, ws.errors, stream);
             if (rc) return rc;
         }
-        if (rounds) hipLaunchKernelGGL(rounds_add, dim3(blk), dim3(256), 0, st, ws.errors, rounds, B);
+        if (rounds) rc = fgnn_launch(rounds_add, dim3(blk), dim3(256), 0, st, ws.errors, rounds, B);
+        if (rc) return rc;
         int nact = B;
         const int* index = nullptr;
         if (compact) {
             FGNN_HIP_CHECK(hipMemsetAsync(ws.count, 0, sizeof(int), st));
-            hipLaunchKernelGGL(compact_kernel, dim3(blk), dim3(256), 0, st, ws.errors, B, ws.index, ws.count);
+            rc = fgnn_launch(compact_kernel, dim3(blk), dim3(256), 0, st, ws.errors, B, ws.index, ws.count);
+            if (rc) return rc;
             FGNN_HIP_CHECK(hipMemcpyAsync(&nact, ws.count, sizeof(int), hipMemcpyDeviceToHost, st));
             FGNN_HIP_CHECK(hipStreamSynchronize(st));
             index = ws.index;
@@ -164,7 +167,8 @@ extern "C" int fgnn_sandwich_decode(const fgnn_graph* g, int num_layers, const i
         if (rc) return rc;
         // next round's flag test: the merged estimate of a sample still in `errors` IS this round's x_upd/z_upd, whose syndrome test
         // the decoder just wrote; samples outside `errors` stay outside (their fnext entry is stale or unset, and 0 & x = 0)
-        if (fuse && !last) hipLaunchKernelGGL(and_u8, dim3(blk), dim3(256), 0, st, ws.errors, ws.fnext, B);
+        if (fuse && !last) rc = fgnn_launch(and_u8, dim3(blk), dim3(256), 0, st, ws.errors, ws.fnext, B);
+        if (rc) return rc;
         if (compact) {  // keep this round's list for the next flag update (the compaction below overwrites ws.index)
             FGNN_HIP_CHECK(hipMemcpyAsync(ws.index2, ws.index, sizeof(int) * (size_t)nact, hipMemcpyDeviceToDevice, st));
             listed = nact;
@@ -172,6 +176,5 @@ extern "C" int fgnn_sandwich_decode(const fgnn_graph* g, int num_layers, const i
     }
     if (llr_final)
         FGNN_HIP_CHECK(hipMemcpyAsync(llr_final, ws.llr_a, sizeof(float) * 3 * (size_t)n * B, hipMemcpyDeviceToDevice, st));
-    FGNN_HIP_CHECK(hipGetLastError());
     return FGNN_OK;
 }
