@@ -28,13 +28,13 @@ def __getattr__(name):
     if name in ("LDPCBPDecoder", "BP_BSC_Model"):
         from . import decoding as _d
         return getattr(_d, name)
-    if name in ("OSD0_Decoder", "BP4_OSD_Model", "BP2_OSD_Model"):
+    if name in ("OSD0_Decoder", "OSD_Decoder", "BP4_OSD_Model", "BP2_OSD_Model"):
         from . import bp_osd as _o
         return getattr(_o, name)
     if name in ("GNN_BP4", "MLP"):
         from . import gnn as _gn
         return getattr(_gn, name)
-    if name in ("TannerGraph", "GnnWeights"):
+    if name in ("TannerGraph", "GnnWeights", "OSD_METHODS"):
         from . import graph as _g
         return getattr(_g, name)
     raise AttributeError(name)

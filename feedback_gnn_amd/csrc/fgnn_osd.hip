@@ -23,20 +23,48 @@ struct OsdArgs {
     const uint8_t* synd;                 // [B,m_side]
     const int* index;                    // [nact] or null
     uint8_t* e_hat;                      // [B,n]
+    int32_t* chosen;                     // [B] or null: winning candidate index (osd_search_kernel only)
+    int method, order;                   // FGNN_OSD_* and the requested order (osd_search_kernel only)
 };
 
-__global__ void __launch_bounds__(256) osd0_kernel(GraphDev g, OsdArgs a)
+// bytes of the OsdLds buffers (the search kernel's scratch follows, 8-aligned)
+__host__ __device__ inline size_t osd_lds_bytes(int n, int rank, int WS, int NP)
 {
-    FG_LOG_TAB_SETUP();
-    extern __shared__ unsigned char smem[];
+    return sizeof(unsigned long long) * (size_t)NP + sizeof(unsigned) * (size_t)rank * WS + sizeof(int) * (size_t)(2 * n + rank);
+}
+constexpr size_t OSD_SEARCH_SCRATCH = 4 * sizeof(unsigned long long) + 8;  // per-wave best keys, |T|
+
+// LDS of one OSD workgroup, carved from the dynamic allocation (osd_lds_bytes on the host counts the same buffers)
+struct OsdLds {
+    unsigned long long* keys;  // [NP]
+    unsigned* mat;             // [rank][WS]
+    int* order;                // [n]
+    int* inv;                  // [n]
+    int* piv;                  // [rank]
+};
+
+__device__ inline OsdLds osd_lds(unsigned char* smem, const GraphDev& g, const OsdArgs& a)
+{
+    OsdLds L;
+    L.keys = reinterpret_cast<unsigned long long*>(smem);
+    L.mat = reinterpret_cast<unsigned*>(L.keys + a.NP);
+    L.order = reinterpret_cast<int*>(L.mat + (size_t)a.rank * a.WS);
+    L.inv = L.order + g.n;
+    L.piv = L.inv + g.n;
+    return L;
+}
+
+// Steps 1-4 of OSD for sample b: sorted reliabilities (keys), order/inv permutation, e_hat[b] zeroed, and the reduced augmented
+// matrix with pivot column piv[row] of every row.  Shared by osd0_kernel and osd_search_kernel.
+__device__ __forceinline__ void osd_eliminate(const GraphDev& g, const OsdArgs& a, int b, const OsdLds& L)
+{
     const int tid = threadIdx.x, T = 256;
     const int n = g.n, rank = a.rank, W = a.W, WS = a.WS;
-    const int b = a.index ? a.index[blockIdx.x] : (int)blockIdx.x;
-    unsigned long long* keys = reinterpret_cast<unsigned long long*>(smem);     // [NP]
-    unsigned* mat = reinterpret_cast<unsigned*>(keys + a.NP);                   // [rank][WS]
-    int* order = reinterpret_cast<int*>(mat + (size_t)rank * WS);               // [n]
-    int* inv = order + n;                                                       // [n]
-    int* piv = inv + n;                                                         // [rank]
+    unsigned long long* keys = L.keys;
+    unsigned* mat = L.mat;
+    int* order = L.order;
+    int* inv = L.inv;
+    int* piv = L.piv;
 
     // 1. reliabilities -> sortable 64-bit keys (value, qubit): ascending, ties by qubit index (stable)
     for (int v = tid; v < a.NP; v += T) {
@@ -120,11 +148,192 @@ __global__ void __launch_bounds__(256) osd0_kernel(GraphDev g, OsdArgs a)
             }
         __syncthreads();
     }
+}
+
+__global__ void __launch_bounds__(256) osd0_kernel(GraphDev g, OsdArgs a)
+{
+    FG_LOG_TAB_SETUP();
+    extern __shared__ unsigned char smem[];
+    const int tid = threadIdx.x, T = 256;
+    const int n = g.n, rank = a.rank, WS = a.WS;
+    const int b = a.index ? a.index[blockIdx.x] : (int)blockIdx.x;
+    const OsdLds L = osd_lds(smem, g, a);
+    osd_eliminate(g, a, b, L);
+    const unsigned* mat = L.mat;
+    const int* order = L.order;
+    const int* piv = L.piv;
+    uint8_t* eo = a.e_hat + (size_t)b * n;
     // 5. e_hat[order[pivot_r]] = transformed syndrome bit of row r (bp_osd.py:44-45, :68-69)
     for (int r = tid; r < rank; r += T) {
         const int p = piv[r];
         if (p < n) eo[order[p]] = (uint8_t)((mat[(size_t)r * WS + (n >> 5)] >> (n & 31)) & 1u);
     }
+}
+
+// float -> uint32 whose unsigned order is the float order (the sort key of step 1), and back
+__device__ __forceinline__ unsigned osd_sortable(float f)
+{
+    const unsigned u = fg_f2u(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float osd_unsortable(unsigned s) { return fg_u2f((s & 0x80000000u) ? (s & 0x7fffffffu) : ~s); }
+
+// Candidate c of the list (fgnn.h, fgnn_osd) as a mask over the search columns T[0..lam) plus at most one further column T[xc]
+// (xc = -1: none).  osd_e: bit i of c sets T[i].  osd_cs: 0, then T[0..k) one at a time, then the pairs {T[i], T[j]}, i < j < lam.
+__device__ __forceinline__ void osd_candidate(int method, int c, int k, int lam, unsigned long long& cbits, int& xc)
+{
+    cbits = 0ull;
+    xc = -1;
+    if (method == FGNN_OSD_E) {
+        cbits = (unsigned long long)c;
+    } else if (c >= 1 && c <= k) {
+        if (c - 1 < lam) cbits = 1ull << (c - 1);
+        else xc = c - 1;
+    } else if (c > k) {
+        int q = c - k - 1, i = 0;
+        while (q >= lam - 1 - i) {
+            q -= lam - 1 - i;
+            ++i;
+        }
+        cbits = (1ull << i) | (1ull << (i + 1 + q));
+    }
+}
+
+// OSD-E / OSD-CS: the elimination of osd_eliminate, then every candidate of the list scored by its soft weight (the fixed-order tree
+// sum of fgnn.h), the cheapest (lowest index on ties) written to e_hat[b].  NPL = max(NP, 64) / 64 sorted positions per lane: lane l
+// of every wave holds positions l + 64 m (m < NPL) in registers — reliability, pivot row / non-pivot index, the bit of candidate 0
+// and the row's bits on the search columns — so a candidate costs one masked parity per position, NPL - 1 lane-local adds per
+// tree level h >= 64 and six cross-lane adds.  The four waves take candidates round-robin.
+template <int NPL>
+__global__ void __launch_bounds__(256) osd_search_kernel(GraphDev g, OsdArgs a)
+{
+    FG_LOG_TAB_SETUP();
+    extern __shared__ unsigned char smem[];
+    const int tid = threadIdx.x, T = 256, lane = tid & 63, wave = tid >> 6;
+    const int n = g.n, rank = a.rank, WS = a.WS;
+    const int b = a.index ? a.index[blockIdx.x] : (int)blockIdx.x;
+    const OsdLds L = osd_lds(smem, g, a);
+    unsigned long long* wave_best = reinterpret_cast<unsigned long long*>(smem + ((osd_lds_bytes(n, rank, WS, a.NP) + 7) & ~(size_t)7));  // [4]
+    int* tcount = reinterpret_cast<int*>(wave_best + 4);                                                               // [1]
+    osd_eliminate(g, a, b, L);
+    const unsigned* mat = L.mat;
+    const int* piv = L.piv;
+    // after the sort, keys[p] = (sortable(r_sorted[p]) << 32) | order[p]; the low words are free and take the list T
+    unsigned* kw = reinterpret_cast<unsigned*>(L.keys);  // kw[2p] = T[p] (p < k), kw[2p + 1] = sortable(r_sorted[p])
+    int* pos = L.inv;                                    // pos[p] = pivot row of sorted position p, or -(j + 1) for p = T[j]
+    // 5. pivot positions S: a row is a pivot row iff its pivot bit is set (a zero row of a rank-deficient basis is not)
+    for (int p = tid; p < n; p += T) pos[p] = -1;
+    __syncthreads();
+    for (int r = tid; r < rank; r += T) {
+        const int p = piv[r];
+        if (p < n && ((mat[(size_t)r * WS + (p >> 5)] >> (p & 31)) & 1u)) pos[p] = r;
+    }
+    __syncthreads();
+    // 6. T = the non-pivot positions in ascending order (one wave, ballot compaction)
+    if (wave == 0) {
+        int cnt = 0;
+        for (int base = 0; base < n; base += 64) {
+            const int p = base + lane;
+            const bool isT = p < n && pos[p] < 0;
+            const unsigned long long ball = __ballot(isT);
+            if (isT) {
+                const int j = cnt + __popcll(ball & ((1ull << lane) - 1ull));
+                kw[2 * j] = (unsigned)p;
+                pos[p] = -(j + 1);
+            }
+            cnt += __popcll(ball);
+        }
+        if (lane == 0) *tcount = cnt;
+    }
+    __syncthreads();
+    const int k = *tcount;
+    const int lam = a.order < k ? a.order : k;
+    const int ncand = a.order == 0 ? 1 : a.method == FGNN_OSD_E ? (1 << lam) : 1 + k + lam * (lam - 1) / 2;
+    // 7. per-lane registers for positions p = lane + 64 m
+    float rv[NPL];
+    int info[NPL];
+    unsigned long long msk[NPL];
+    unsigned e0 = 0u;
+#pragma unroll
+    for (int m = 0; m < NPL; ++m) {
+        const int p = lane + 64 * m;
+        rv[m] = 0.0f;
+        info[m] = -(n + 1);  // padding: matches no column
+        msk[m] = 0ull;
+        if (p < n) {
+            rv[m] = osd_unsortable(kw[2 * p + 1]);
+            const int ip = pos[p];
+            info[m] = ip;
+            if (ip >= 0) {
+                const unsigned* row = mat + (size_t)ip * WS;
+                e0 |= ((row[n >> 5] >> (n & 31)) & 1u) << m;
+                unsigned long long mm = 0ull;
+                for (int j = 0; j < lam; ++j) {
+                    const int t = (int)kw[2 * j];
+                    mm |= (unsigned long long)((row[t >> 5] >> (t & 31)) & 1u) << j;
+                }
+                msk[m] = mm;
+            } else if (-ip - 1 < lam) {
+                msk[m] = 1ull << (-ip - 1);
+            }
+        }
+    }
+    // 8. the search: lane 0 of each wave keeps the wave's least (sortable(cost) << 32 | c)
+    unsigned long long best = ~0ull;
+    for (int c = wave; c < ncand; c += 4) {
+        unsigned long long cbits;
+        int xc;
+        osd_candidate(a.method, c, k, lam, cbits, xc);
+        const int xt = xc >= 0 ? (int)kw[2 * xc] : 0;
+        float x[NPL];
+#pragma unroll
+        for (int m = 0; m < NPL; ++m) {
+            unsigned bit = ((e0 >> m) & 1u) ^ ((unsigned)__popcll(msk[m] & cbits) & 1u);
+            if (xc >= 0) {
+                if (info[m] >= 0) bit ^= (mat[(size_t)info[m] * WS + (xt >> 5)] >> (xt & 31)) & 1u;
+                else bit ^= info[m] == -(xc + 1) ? 1u : 0u;
+            }
+            x[m] = bit ? rv[m] : 0.0f;
+        }
+#pragma unroll
+        for (int h = NPL / 2; h >= 1; h >>= 1)
+#pragma unroll
+            for (int m = 0; m < h; ++m) x[m] = x[m] + x[m + h];
+        float s = x[0];
+#pragma unroll
+        for (int h = 32; h >= 1; h >>= 1) s = s + __shfl_xor(s, h);
+        const unsigned long long key = ((unsigned long long)osd_sortable(s) << 32) | (unsigned)c;
+        best = key < best ? key : best;
+    }
+    if (lane == 0) wave_best[wave] = best;
+    __syncthreads();
+    unsigned long long w = wave_best[0];
+    for (int i = 1; i < 4; ++i) w = wave_best[i] < w ? wave_best[i] : w;
+    const int cw = (int)(unsigned)w;
+    // 9. e_hat[b][order[p]] = bit p of the winner's solution
+    unsigned long long cbits;
+    int xc;
+    osd_candidate(a.method, cw, k, lam, cbits, xc);
+    const int xt = xc >= 0 ? (int)kw[2 * xc] : 0;
+    uint8_t* eo = a.e_hat + (size_t)b * n;
+    for (int p = tid; p < n; p += T) {
+        const int ip = pos[p];
+        unsigned bit;
+        if (ip >= 0) {
+            const unsigned* row = mat + (size_t)ip * WS;
+            bit = (row[n >> 5] >> (n & 31)) & 1u;
+            for (unsigned long long cb = cbits; cb; cb &= cb - 1ull) {
+                const int t = (int)kw[2 * (__ffsll((long long)cb) - 1)];
+                bit ^= (row[t >> 5] >> (t & 31)) & 1u;
+            }
+            if (xc >= 0) bit ^= (row[xt >> 5] >> (xt & 31)) & 1u;
+        } else {
+            const int j = -ip - 1;
+            bit = (j < 64 && ((cbits >> j) & 1ull)) || j == xc ? 1u : 0u;
+        }
+        eo[L.order[p]] = (uint8_t)bit;
+    }
+    if (tid == 0 && a.chosen) a.chosen[b] = cw;
 }
 
 __global__ void __launch_bounds__(256) compact_u8_kernel(const uint8_t* __restrict__ mask, uint8_t bit, int B, int* __restrict__ index,
@@ -167,16 +376,18 @@ extern "C" int fgnn_graph_set_basis(fgnn_graph* g, int side, int rank, const int
     return FGNN_OK;
 }
 
-extern "C" int fgnn_osd0(const fgnn_graph* g, int side, const float* marg, const float* llr_bin, const uint8_t* synd, int B,
-                         const int32_t* index, int nact, uint8_t* e_hat, void* stream)
+// The argument checks and launch parameters shared by fgnn_osd0 and fgnn_osd.  count = samples to process (0: nothing to launch);
+// lds = the OSD-0 layout, plus `scratch` bytes after it rounded up to 8 when scratch > 0.
+static int osd_prepare(const fgnn_graph* g, int side, const float* marg, const float* llr_bin, const uint8_t* synd, int B,
+                       const int32_t* index, int nact, uint8_t* e_hat, size_t scratch, OsdArgs& a, size_t& lds, int& count)
 {
+    count = 0;
     if (!g || side < 0 || side > 1) return fgnn_fail(FGNN_ERR_ARG, "bad OSD arguments");
     if (!g->basis_dev[side]) return fgnn_fail(FGNN_ERR_STATE, "row basis not installed (fgnn_graph_set_basis)");
     if ((!marg && !llr_bin) || !synd || !e_hat || B < 0) return fgnn_fail(FGNN_ERR_ARG, "required buffer is NULL");
-    const int count = index ? nact : B;
-    if (count <= 0) return FGNN_OK;
-    FGNN_DEVICE_GUARD(g->device);
-    OsdArgs a;
+    const int cnt = index ? nact : B;
+    if (cnt <= 0) return FGNN_OK;
+    a = OsdArgs{};
     a.side = side;
     a.rank = g->basis_rank[side];
     a.B = B;
@@ -192,10 +403,50 @@ extern "C" int fgnn_osd0(const fgnn_graph* g, int side, const float* marg, const
     a.synd = synd;
     a.index = index;
     a.e_hat = e_hat;
-    const size_t lds = sizeof(unsigned long long) * (size_t)a.NP + sizeof(unsigned) * (size_t)a.rank * a.WS +
-                       sizeof(int) * (size_t)(2 * g->d.n + a.rank);
+    lds = osd_lds_bytes(g->d.n, a.rank, a.WS, a.NP);
+    if (scratch) lds = ((lds + 7) & ~(size_t)7) + scratch;
     if (lds > FGNN_LDS_BUDGET) return fgnn_fail(FGNN_ERR_ARG, "code too large for the LDS-resident OSD kernel");
+    count = cnt;
+    return FGNN_OK;
+}
+
+extern "C" int fgnn_osd0(const fgnn_graph* g, int side, const float* marg, const float* llr_bin, const uint8_t* synd, int B,
+                         const int32_t* index, int nact, uint8_t* e_hat, void* stream)
+{
+    OsdArgs a;
+    size_t lds;
+    int count;
+    const int rc = osd_prepare(g, side, marg, llr_bin, synd, B, index, nact, e_hat, 0, a, lds, count);
+    if (rc != FGNN_OK || count == 0) return rc;
+    FGNN_DEVICE_GUARD(g->device);
     return fgnn_launch(osd0_kernel, dim3(count), dim3(256), lds, static_cast<hipStream_t>(stream), g->d, a);
+}
+
+extern "C" int fgnn_osd(const fgnn_graph* g, int side, int method, int order, const float* marg, const float* llr_bin, const uint8_t* synd,
+                        int B, const int32_t* index, int nact, uint8_t* e_hat, int32_t* chosen, void* stream)
+{
+    if (method != FGNN_OSD_0 && method != FGNN_OSD_E && method != FGNN_OSD_CS) return fgnn_fail(FGNN_ERR_ARG, "unknown OSD method");
+    if (order < 0) return fgnn_fail(FGNN_ERR_ARG, "OSD order must be >= 0");
+    if (method == FGNN_OSD_E && order > 16) return fgnn_fail(FGNN_ERR_ARG, "osd_e supports order <= 16");
+    if (method == FGNN_OSD_CS && order > 64) return fgnn_fail(FGNN_ERR_ARG, "osd_cs supports order <= 64");
+    OsdArgs a;
+    size_t lds;
+    int count;
+    const int rc = osd_prepare(g, side, marg, llr_bin, synd, B, index, nact, e_hat, OSD_SEARCH_SCRATCH, a, lds, count);
+    if (rc != FGNN_OK || count == 0) return rc;
+    a.chosen = chosen;
+    a.method = method;
+    a.order = method == FGNN_OSD_0 ? 0 : order;
+    FGNN_DEVICE_GUARD(g->device);
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    switch ((a.NP > 64 ? a.NP : 64) / 64) {
+    case 1: return fgnn_launch(osd_search_kernel<1>, dim3(count), dim3(256), lds, st, g->d, a);
+    case 2: return fgnn_launch(osd_search_kernel<2>, dim3(count), dim3(256), lds, st, g->d, a);
+    case 4: return fgnn_launch(osd_search_kernel<4>, dim3(count), dim3(256), lds, st, g->d, a);
+    case 8: return fgnn_launch(osd_search_kernel<8>, dim3(count), dim3(256), lds, st, g->d, a);
+    case 16: return fgnn_launch(osd_search_kernel<16>, dim3(count), dim3(256), lds, st, g->d, a);
+    default: return fgnn_launch(osd_search_kernel<32>, dim3(count), dim3(256), lds, st, g->d, a);
+    }
 }
 
 // index[0..count) = ids of the samples with (mask[b] & bit) != 0; *count must be zeroed by the caller (device int).

@@ -31,6 +31,19 @@ def _stream(device):
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
+# osd_method names of ldpc.bposd_decoder (examples/OSD.ipynb cell 5) -> FGNN_OSD_0 / FGNN_OSD_E / FGNN_OSD_CS of include/fgnn.h
+OSD_METHODS = {"osd0": 0, "osd_0": 0, "osd_e": 1, "osde": 1, "exhaustive": 1, "osd_cs": 2, "osdcs": 2, "combination_sweep": 2}
+
+
+def osd_method_id(method):
+    if isinstance(method, str):
+        key = method.lower()
+        if key not in OSD_METHODS:
+            raise ValueError(f"unknown OSD method {method!r} (one of {sorted(OSD_METHODS)})")
+        return OSD_METHODS[key]
+    return int(method)
+
+
 def _resolve_device(device):
     """torch.device with an explicit index: None and a bare "cuda" mean torch's CURRENT device (not device 0)."""
     device = torch.device("cuda" if device is None else device)
@@ -638,6 +651,26 @@ class TannerGraph:
             index = self._chk(index, tuple(index.shape), torch.int32, "index")
         check(_lib.lib().fgnn_osd0(self.handle, int(side), _ptr(marg), _ptr(llr_bin), _ptr(synd), B, _ptr(index), int(nact),
                                    _ptr(e_hat), _stream(self.device)))
+        return e_hat
+
+    def osd(self, side, synd, e_hat, method, order, marg=None, llr_bin=None, index=None, nact=0, chosen=None):
+        """Overwrite e_hat[b] for the listed samples with the OSD-E / OSD-CS solution of side 0 (hx) / 1 (hz) (`fgnn_osd`): `method` a
+        name of `OSD_METHODS` or its FGNN_OSD_* id, `order` the search depth.  `chosen` (int32 [B], optional) receives the winning
+        candidate index of every processed sample (0 = the OSD-0 solution)."""
+        method = osd_method_id(method)
+        B = int(synd.shape[0])
+        synd = self._chk(synd, (B, self.m_x if side == 0 else self.m_z), torch.uint8, "synd")
+        e_hat = self._chk_out(e_hat, (B, self.n), torch.uint8, "e_hat")
+        if marg is not None:
+            marg = self._chk(marg, tuple(marg.shape), torch.float32, "marg")
+        if llr_bin is not None:
+            llr_bin = self._chk(llr_bin, tuple(llr_bin.shape), torch.float32, "llr_bin")
+        if index is not None:
+            index = self._chk(index, tuple(index.shape), torch.int32, "index")
+        if chosen is not None:
+            chosen = self._chk_out(chosen, (B,), torch.int32, "chosen")
+        check(_lib.lib().fgnn_osd(self.handle, int(side), method, int(order), _ptr(marg), _ptr(llr_bin), _ptr(synd), B, _ptr(index),
+                                  int(nact), _ptr(e_hat), _ptr(chosen), _stream(self.device)))
         return e_hat
 
     def residual_rows(self, rows_x, rows_z, ex, ez, x_hat, z_hat):

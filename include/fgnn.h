@@ -279,6 +279,26 @@ int fgnn_bsc_noise(uint64_t seed, float p, uint64_t first_sample, int B, int n, 
 int fgnn_graph_set_basis(fgnn_graph* g, int side, int rank, const int32_t* pivot_rows);
 int fgnn_osd0(const fgnn_graph* g, int side, const float* marg, const float* llr_bin, const uint8_t* synd, int B,
               const int32_t* index, int nact, uint8_t* e_hat, void* stream);
+/* Higher-order OSD (OSD-E, OSD-CS), the osd_method / osd_order choices of ldpc.bposd_decoder (examples/OSD.ipynb cell 5), on the same
+ * row basis and inputs as fgnn_osd0.  The reliabilities r, the -0 -> +0 step, the stable ascending sort into positions 0..n-1 and the
+ * Gauss-Jordan elimination (pivot of a row = its first set column) are those of fgnn_osd0.  S = the pivot positions, T = the other
+ * positions in ascending order (T[0] = the least reliable non-pivot column), k = |T| = n - rank, lambda = min(order, k).
+ * A candidate t is a bit vector over T; its solution e(t) equals t on T and, on the pivot of reduced row i, s'[i] XOR the parity of
+ * row i over the set bits of t (s' = the transformed syndrome).  Candidate 0 (t = 0) is the OSD-0 solution.  Candidates, by index c:
+ *   FGNN_OSD_0   c = 0 only (order is ignored);
+ *   FGNN_OSD_E   c = 0 .. 2^lambda - 1, bit i of c sets T[i] (order <= 16);
+ *   FGNN_OSD_CS  c = 0, then c = 1..k the weight-1 vectors T[c-1], then the pairs {T[i], T[j]}, 0 <= i < j < lambda, in
+ *                lexicographic (i, j) order: 1 + k + lambda(lambda-1)/2 candidates (order <= 64);
+ *   order 0 = OSD-0 for every method.
+ * Cost = soft weight, bit-reproducibly: x[p] = r_sorted[p] where e(t) has bit p, +0.0f elsewhere, zero-padded to NP (the power of
+ * two >= n); for h = NP/2, NP/4, ..., 1: x[i] = x[i] + x[i+h] for i < h (float32, round to nearest, no fma); cost = x[0].  The
+ * winner minimises (sortable(cost) << 32) | c, with the order-preserving float -> uint32 map of the sort key: ties go to the lowest
+ * index and the answer never costs more than OSD-0.  Inputs must be finite.  e_hat[b,:] = e(winner) mapped back to qubit order;
+ * chosen (device int32[B]) may be NULL, else chosen[b] = the winner's index for every processed b (other entries untouched).
+ * Same n <= 2047 limit and LDS check as fgnn_osd0 (the search adds 40 bytes).  The basis must be full rank. */
+enum { FGNN_OSD_0 = 0, FGNN_OSD_E = 1, FGNN_OSD_CS = 2 };
+int fgnn_osd(const fgnn_graph* g, int side, int method, int order, const float* marg, const float* llr_bin, const uint8_t* synd, int B,
+             const int32_t* index, int nact, uint8_t* e_hat, int32_t* chosen, void* stream);
 /* index[0..*count) = ids b with (mask[b] & bit) != 0 (tf.where(err), bp_osd.py:166-171); *count (device int32) must be
  * zero on entry; ids of one 256-sample block are ascending, blocks arrive in any order. */
 int fgnn_compact(const uint8_t* mask, int bit, int B, int32_t* index, int32_t* count, void* stream);
