@@ -75,9 +75,11 @@ class _StandaloneOSD:
 
     def __call__(self, llr, pcm, s, bs=None):
         """The reference's standalone call (bp_osd.py:47-77): ``llr [bs, n]`` binary reliabilities (sorted ascending: the least
-        reliable "no error" positions become the pivots), ``pcm [bs, rank, n]`` the FULL-RANK row basis tiled over the batch (the
+        reliable "no error" positions become the pivots), ``pcm [bs, rank, n]`` the row basis tiled over the batch (the
         reference's models tile one matrix, :147-150; this implementation requires that — or takes a plain ``[rank, n]`` matrix),
         ``s [rank, bs]`` the syndrome of those rows → ``e_hat [bs, n]`` bool with ``pcm e_hat = s`` on the most reliable basis.
+        The rows may be dependent (a full ``hx`` is fine): rows that reduce to zero are ignored, and ``pcm e_hat = s`` holds
+        whenever ``s`` lies in the row space of ``pcm`` (for any ``s`` that comes from an error).
         Ties in the sort keep qubit order (tf.argsort leaves them unspecified).
 
         Host-side cost: the first call with a given ``pcm`` tensor checks that it is one matrix tiled over the batch (skipped for an

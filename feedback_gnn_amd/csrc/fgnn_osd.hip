@@ -163,10 +163,14 @@ __global__ void __launch_bounds__(256) osd0_kernel(GraphDev g, OsdArgs a)
     const int* order = L.order;
     const int* piv = L.piv;
     uint8_t* eo = a.e_hat + (size_t)b * n;
-    // 5. e_hat[order[pivot_r]] = transformed syndrome bit of row r (bp_osd.py:44-45, :68-69)
+    // 5. e_hat[order[pivot_r]] = transformed syndrome bit of row r (bp_osd.py:44-45, :68-69), for the rows whose pivot bit is set: a
+    //    zero row of a rank-deficient basis (pivot 0) writes nothing, as in og_osd0 and osd_search_kernel step 5
     for (int r = tid; r < rank; r += T) {
         const int p = piv[r];
-        if (p < n) eo[order[p]] = (uint8_t)((mat[(size_t)r * WS + (n >> 5)] >> (n & 31)) & 1u);
+        if (p < n) {
+            const unsigned* row = mat + (size_t)r * WS;
+            if ((row[p >> 5] >> (p & 31)) & 1u) eo[order[p]] = (uint8_t)((row[n >> 5] >> (n & 31)) & 1u);
+        }
     }
 }
 

@@ -275,7 +275,10 @@ int fgnn_bsc_noise(uint64_t seed, float p, uint64_t first_sample, int B, int n, 
  * side 0 -> z_hat from hx and osd_llrz, side 1 -> x_hat from hz and osd_llrx (:125-131), computed from the BP4 marginals
  * marg [B,3,n], or from llr_bin [B,n] if given (BP2_OSD_Model).  synd [B,m_side] is the FULL syndrome (reduced
  * internally, :144-145).  index (device int32[nact]) selects the samples to process, NULL = all B.
- * Ties in the reliability sort keep qubit order (tf.argsort leaves them unspecified). */
+ * Ties in the reliability sort keep qubit order (tf.argsort leaves them unspecified).
+ * The basis may be rank-deficient (find_mrb runs on any matrix): a row whose pivot bit is not set after the elimination (an all-zero
+ * row, or one that is zero on H with syndrome bit 1 — an inconsistent syndrome) writes nothing.  H_basis e = syndrome holds whenever
+ * the syndrome lies in the row space of H_basis. */
 int fgnn_graph_set_basis(fgnn_graph* g, int side, int rank, const int32_t* pivot_rows);
 int fgnn_osd0(const fgnn_graph* g, int side, const float* marg, const float* llr_bin, const uint8_t* synd, int B,
               const int32_t* index, int nact, uint8_t* e_hat, void* stream);
@@ -295,7 +298,9 @@ int fgnn_osd0(const fgnn_graph* g, int side, const float* marg, const float* llr
  * winner minimises (sortable(cost) << 32) | c, with the order-preserving float -> uint32 map of the sort key: ties go to the lowest
  * index and the answer never costs more than OSD-0.  Inputs must be finite.  e_hat[b,:] = e(winner) mapped back to qubit order;
  * chosen (device int32[B]) may be NULL, else chosen[b] = the winner's index for every processed b (other entries untouched).
- * Same n <= 2047 limit and LDS check as fgnn_osd0 (the search adds 40 bytes).  The basis must be full rank. */
+ * Same n <= 2047 limit and LDS check as fgnn_osd0 (the search adds 40 bytes).  The basis may be rank-deficient: S holds only the pivots
+ * of the rows whose pivot bit is set (zero rows are ignored, as in fgnn_osd0), so k = n - rank(H_basis), and every candidate solves
+ * H_basis e = syndrome whenever the syndrome lies in the row space. */
 enum { FGNN_OSD_0 = 0, FGNN_OSD_E = 1, FGNN_OSD_CS = 2 };
 int fgnn_osd(const fgnn_graph* g, int side, int method, int order, const float* marg, const float* llr_bin, const uint8_t* synd, int B,
              const int32_t* index, int nact, uint8_t* e_hat, int32_t* chosen, void* stream);

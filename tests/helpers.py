@@ -122,3 +122,26 @@ def unpack(g, key, attr):
 def to_gpu(a):
     import torch
     return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def random_sparse_basis(n, m, seed, col_weight=3):
+    """A seeded random sparse binary matrix [m, n] (uint8) in which every row and every column holds at least one 1 (fgnn_graph_create
+    takes no duplicate edges, and an edge-free row or column is no code), with its GF(2) rank: (basis, rank)."""
+    from feedback_gnn_amd.gf2 import rank
+    rng = np.random.RandomState(seed)
+    h = np.zeros((m, n), np.uint8)
+    for v in range(n):
+        h[rng.choice(m, size=min(col_weight, m), replace=False), v] = 1
+    for c in np.nonzero(h.sum(1) == 0)[0]:
+        h[c, rng.randint(n)] = 1
+    return h, rank(h)
+
+
+def binary_oracle(basis):
+    """The CPU oracle's graph of one binary parity-check matrix on both sides (what decoding._binary_graph builds on the GPU)."""
+    import types
+    from oracle.oracle import OracleGraph
+    pcm = np.asarray(basis).astype(np.int64)
+    zero = np.zeros((1, pcm.shape[1]), np.int64)
+    c = types.SimpleNamespace(hx=pcm, hz=pcm, hx_perp=zero, hz_perp=zero, lx=zero, lz=zero)
+    return OracleGraph(c, stage_one=True, forms="library-default")

@@ -1,5 +1,7 @@
 """OSD-E / OSD-CS on the GPU (fgnn_osd, Graph.osd, OSD_Decoder): bit-exact against the NumPy restatement of
-tests/test_osd_search_cpu.py on the llr_bin path, order 0 = fgnn_osd0 byte for byte on the marginal path, and the model level."""
+tests/test_osd_search_cpu.py on the llr_bin path, order 0 = fgnn_osd0 byte for byte on the marginal path, and the model level.
+Shape coverage (every osd_search_kernel instantiation, n up to 2047, the LDS limit, rank-deficient bases, m_x != m_z, order extremes,
+edge-value reliabilities) is in tests/test_gpu_osd_shapes.py."""
 import numpy as np
 import pytest
 import torch

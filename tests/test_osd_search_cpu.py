@@ -17,7 +17,10 @@ def sortable(x):
 
 
 def eliminate(r, basis, synd):
-    """Steps 1-4 of fgnn_osd0 for one sample: (order, r_sorted, reduced augmented matrix [rank, n+1], pivot of every row)."""
+    """Steps 1-4 of fgnn_osd0 for one sample: (order, r_sorted, reduced augmented matrix [rank, n+1], pivot of every row, and which
+    rows are real pivot rows).  The pivot of a row is its first set column of the augmented row, syndrome column n included, or 0 for
+    an all-zero row (tf.argmax).  A row of a rank-deficient basis that reduces to zero on H is not a real pivot row: its pivot bit is
+    clear (all-zero row, pivot 0) or its pivot is column n (zero on H, syndrome bit 1: an inconsistent syndrome)."""
     r = np.asarray(r, dtype=np.float32) + np.float32(0.0)  # -0 -> +0
     order = np.argsort(sortable(r), kind="stable")
     m, n = basis.shape
@@ -27,10 +30,10 @@ def eliminate(r, basis, synd):
         nz = np.nonzero(a[i])[0]
         p = int(nz[0]) if len(nz) else 0
         piv[i] = p
-        assert p < n and a[i, p], "basis must be full rank"
         rows = np.nonzero(a[:, p])[0]
         a[rows[rows != i]] ^= a[i]
-    return order, r[order], a, piv
+    real = np.array([piv[i] < n and a[i, piv[i]] == 1 for i in range(m)], dtype=bool)
+    return order, r[order], a, piv, real
 
 
 def candidates(method, order, k):
@@ -66,21 +69,24 @@ def tree_cost(e_sorted, r_sorted):
     x = np.zeros((ncand, NP), np.float32)
     x[:, :n] = np.where(e_sorted != 0, r_sorted[None, :], np.float32(0.0))
     h = NP // 2
-    while h >= 1:
-        x[:, :h] = x[:, :h] + x[:, h:2 * h]
-        h //= 2
+    with np.errstate(over="ignore"):  # a sum may round to +-inf (FLT_MAX inputs), as on the device
+        while h >= 1:
+            x[:, :h] = x[:, :h] + x[:, h:2 * h]
+            h //= 2
     return x[:, 0]
 
 
-def osd_search(r, basis, synd, method, order, return_all=False):
-    """One sample of fgnn_osd: (e_hat in qubit order, winning candidate index)."""
+def osd_search(r, basis, synd, method, order, return_all=False, elim=None):
+    """One sample of fgnn_osd: (e_hat in qubit order, winning candidate index).  `elim` = eliminate(r, basis, synd) if already known."""
     n = basis.shape[1]
-    order_, rs, a, piv = eliminate(r, basis, synd)
+    order_, rs, a, piv, real = eliminate(r, basis, synd) if elim is None else elim
+    a, piv = a[real], piv[real]  # S and T from the real pivot rows only (osd_search_kernel step 5)
     T = np.setdiff1d(np.arange(n), piv)
     C = candidates(method, order, len(T))
     es = np.zeros((len(C), n), np.uint8)
     es[:, T] = C
-    es[:, piv] = (a[:, n][None, :] ^ ((C.astype(np.int64) @ a[:, T].T.astype(np.int64)) & 1)).astype(np.uint8)
+    par = (C.astype(np.float64) @ a[:, T].T.astype(np.float64)).astype(np.int64) & 1  # exact: counts <= n
+    es[:, piv] = (a[:, n][None, :] ^ par).astype(np.uint8)
     cost = tree_cost(es, rs)
     key = (sortable(cost).astype(np.uint64) << np.uint64(32)) | np.arange(len(C), dtype=np.uint64)
     w = int(np.argmin(key))
@@ -91,11 +97,17 @@ def osd_search(r, basis, synd, method, order, return_all=False):
     return e, w
 
 
-def osd_search_batch(r, basis, synd, method, order, index):
+def osd_search_batch(r, basis, synd, method, order, index, elims=None):
+    """fgnn_osd over the samples `index`; `elims` (optional dict b -> eliminate(...)) caches the elimination across calls."""
     e = np.zeros((r.shape[0], basis.shape[1]), np.uint8)
     chosen = np.zeros(r.shape[0], np.int32)
     for b in index:
-        e[b], chosen[b] = osd_search(r[b], basis, synd[b], method, order)
+        el = None
+        if elims is not None:
+            el = elims.get(int(b))
+            if el is None:
+                el = elims[int(b)] = eliminate(r[b], basis, synd[b])
+        e[b], chosen[b] = osd_search(r[b], basis, synd[b], method, order, elim=el)
     return e, chosen
 
 
@@ -106,8 +118,26 @@ def _random_full_rank(rng, m, n):
             return h
 
 
+def _deficient(rng, h):
+    """h with dependent rows added and the rows shuffled: a duplicate row, a sum of two rows, an all-zero row.  Same row space."""
+    extra = np.stack([h[-1], h[0] ^ h[1], np.zeros_like(h[0])])
+    hb = np.concatenate([h, extra]).astype(np.uint8)
+    return hb[rng.permutation(len(hb))]
+
+
 @pytest.mark.parametrize("seed", [0, 1, 2, 3])
 def test_osd_e_at_full_order_is_the_minimum_soft_weight_of_the_coset(seed):
+    _check_coset_minimum(seed, deficient=False)
+
+
+@pytest.mark.parametrize("seed", [0, 1, 2, 3])
+def test_osd_e_at_full_order_is_the_minimum_soft_weight_of_the_coset_rank_deficient(seed):
+    """The same row space with dependent rows added (a duplicate, a sum, an all-zero row): the zero rows are ignored, so still
+    k = n - rank and 2^k candidates, exactly the coset."""
+    _check_coset_minimum(seed, deficient=True)
+
+
+def _check_coset_minimum(seed, deficient):
     rng = np.random.RandomState(seed)
     m, n = 12, 26
     h = _random_full_rank(rng, m, n)
@@ -118,10 +148,11 @@ def test_osd_e_at_full_order_is_the_minimum_soft_weight_of_the_coset(seed):
         r = np.abs(r)
         r[:6] = np.float32(0.0)  # zero-weight columns: many solutions share the least cost, the tie rule decides
     err = (rng.uniform(size=n) < 0.2).astype(np.uint8)
-    s = (h.astype(np.int64) @ err % 2).astype(np.uint8)
-    e, w, es, cost, order_ = osd_search(r, h, s, OSD_E, k, return_all=True)
+    hb = _deficient(rng, h) if deficient else h
+    s = (hb.astype(np.int64) @ err % 2).astype(np.uint8)
+    e, w, es, cost, order_ = osd_search(r, hb, s, OSD_E, k, return_all=True)
     assert len(es) == 1 << k
-    assert np.array_equal(h.astype(np.int64) @ e % 2, s)
+    assert np.array_equal(hb.astype(np.int64) @ e % 2, s)
     # brute force over the coset: e + span(kernel(H)), 2^k solutions, all different
     K = np.asarray(kernel(h)[0], dtype=np.int64) % 2
     assert K.shape == (k, n)
@@ -200,3 +231,64 @@ def test_osd_decoder_method_names_and_limits():
     for method, order in (("osd_e", 17), ("osd_cs", 65), ("osd_cs", -1), ("osd_x", 1)):
         with pytest.raises(ValueError):
             F.OSD_Decoder(882, method, order)
+
+
+def _osd0_cases():
+    """(name, basis) pairs: full-rank and rank-deficient random bases (dependent duplicate rows, row sums, an all-zero row)."""
+    from helpers import random_sparse_basis
+    rng = np.random.RandomState(21)
+    out = []
+    for n, m in ((7, 3), (33, 16), (65, 40), (96, 48)):
+        h, _ = random_sparse_basis(n, m, seed=n)
+        out.append((f"random{n}", h))
+        out.append((f"deficient{n}", _deficient(rng, h)))
+    h = _random_full_rank(rng, 12, 26)
+    out.append(("duplicates", np.concatenate([h, h[:4], h[:2] ^ h[2:4]]).astype(np.uint8)))
+    out.append(("rank1", np.tile(h[:1], (5, 1))))
+    return out
+
+
+@pytest.mark.parametrize("name,basis", _osd0_cases(), ids=lambda x: x if isinstance(x, str) else "")
+def test_restatement_order0_equals_oracle_osd0_on_any_basis(name, basis):
+    """The restatement at order 0 (real pivot rows only) is og_osd0 bit for bit on the llr_bin path, on full-rank and rank-deficient
+    bases, for syndromes of errors (H e = s then holds) and for random — possibly inconsistent — syndromes."""
+    from helpers import binary_oracle
+    m, n = basis.shape
+    og = binary_oracle(basis)
+    rng = np.random.RandomState(m * 1000 + n)
+    B = 48
+    llr = rng.normal(1.0, 2.0, size=(B, n)).astype(np.float32)
+    llr[::3, ::4] = np.float32(0.5)  # ties
+    llr[1::3] = np.abs(llr[1::3]) * np.where(rng.uniform(size=(1, n)) < 0.5, np.float32(-0.0), np.float32(0.0))  # +-0
+    err = (rng.uniform(size=(B, n)) < 0.15).astype(np.uint8)
+    synd = (err.astype(np.int64) @ basis.T.astype(np.int64) % 2).astype(np.uint8)
+    synd[B // 2:] = (rng.uniform(size=(B - B // 2, m)) < 0.5).astype(np.uint8)  # random syndromes: inconsistent if rank < m
+    piv = np.arange(m, dtype=np.int32)
+    ref = og.osd0(0, piv, synd, llr_bin=llr)
+    for method in (OSD_0, OSD_E, OSD_CS):
+        e, w = osd_search_batch(llr, basis, synd, method, 0, np.arange(B))
+        assert np.array_equal(e, ref), f"{name} method {method}: samples {np.nonzero((e != ref).any(1))[0][:6]} differ from og_osd0"
+        assert not w.any()
+    ok = (ref[:B // 2].astype(np.int64) @ basis.T % 2 == synd[:B // 2]).all(1)
+    assert ok.all(), f"{name}: H e != s for an error syndrome"
+    if rank(basis) < m:
+        # an inconsistent syndrome: the zero rows with syndrome bit 1 write nothing, H e = s cannot hold there
+        bad = ~(ref[B // 2:].astype(np.int64) @ basis.T % 2 == synd[B // 2:]).all(1)
+        assert bad.any() or name == "rank1"
+
+
+def test_restatement_pivot_rows_on_a_rank_deficient_basis():
+    """The zero rows are exactly the dependent ones: real pivot rows = rank, pivots distinct, and the first set bit of every real row."""
+    rng = np.random.RandomState(3)
+    h = _random_full_rank(rng, 10, 24)
+    hb = _deficient(rng, h)
+    r = rng.normal(size=24).astype(np.float32)
+    s = (rng.uniform(size=len(hb)) < 0.5).astype(np.uint8)
+    order_, rs, a, piv, real = eliminate(r, hb, s)
+    assert real.sum() == 10 and len(set(piv[real].tolist())) == 10
+    for i in np.nonzero(~real)[0]:
+        assert not a[i, :24].any()
+        assert piv[i] == (24 if a[i, 24] else 0)
+    for i in np.nonzero(real)[0]:
+        assert int(np.nonzero(a[i])[0][0]) == piv[i]
+        assert a[:, piv[i]].sum() == 1
