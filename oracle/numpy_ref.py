@@ -1,4 +1,4 @@
-"""Independent NumPy restatement of the reference's BP4 + feedback-GNN arithmetic.
+"""Independent NumPy restatement of the reference's BP4 + feedback-GNN arithmetic, and of binary syndrome BP in float64.
 
 TEST INFRASTRUCTURE ONLY.  Purpose: a second, independently written statement of
 /root/reference sionna/fec/ldpc/decoding_q.py and feedback_gnn.py that uses NumPy's OWN float32
@@ -339,3 +339,95 @@ def gnn_bp4_general_shapes(code, cfg):
         shapes += [(hx.shape[0], An), (hz.shape[0], An), (int(hx.sum()), Am), (int(hz.sum()), Am), (hx.shape[1], An),
                    (int(hx.sum()), Am), (int(hz.sum()), Am)]
     return shapes
+
+
+# ---- binary syndrome BP: LDPCBPDecoder.call with is_syndrome=True (sionna/fec/ldpc/decoding.py:874-1048), float64 ----
+# The reference holds these constants in float32 tensors; the restatement uses the float32 values in float64 arithmetic.
+_D = np.float64
+_LLR_MAX = _D(F(20.0))                 # self._llr_max (:320)
+_ATANH_CLIP = _D(F(1 - 1e-7))          # self._atanh_clip_value (:318), 0.99999988 as a float32
+_PHI_LO, _PHI_HI = _D(F(8.5e-8)), _D(F(16.635532))  # _phi's clip (:632)
+_TANH_ZERO, _TANH_SMALL = _D(F(1e-12)), _D(F(1e-7))  # _where_ragged / _where_ragged_inv (:563, :568)
+_LARGE = _D(10000.0)                   # LARGE_VAL (:756)
+
+
+def _bp2_phi(x):
+    """_phi (:625-633): log(exp(x)+1) - log(exp(x)-1) after the clip."""
+    x = np.clip(x, _PHI_LO, _PHI_HI)
+    return np.log(np.exp(x) + 1.0) - np.log(np.exp(x) - 1.0)
+
+
+def _bp2_sign(x):
+    """tf.sign with 0 replaced by 1 (:697-703): -0 counts as +1 too."""
+    s = np.sign(x)
+    return np.where(s == 0, 1.0, s)
+
+
+def _bp2_cn(rule, msg, seg, starts, syndrome):
+    """One check-node update on check-major messages [E,B]; seg [E] = the check of each edge (0.. over non-empty checks), starts its
+    first edges, syndrome [checks,B] = (-1)^s."""
+    def reduce(ufunc, v):
+        return ufunc.reduceat(v, starts, axis=0)
+
+    if rule == "boxplus-phi":  # _cn_update_phi (:637-693)
+        sign_val = _bp2_sign(msg)
+        sign_node = reduce(np.multiply, sign_val) * syndrome
+        sign_val = sign_val * sign_node[seg]
+        a = _bp2_phi(np.abs(msg))
+        msg_sum = reduce(np.add, a)
+        return sign_val * _bp2_phi(-1.0 * a + msg_sum[seg])
+    if rule == "minsum":  # _cn_update_minsum (:744-850)
+        msg = np.clip(msg, -_LLR_MAX, _LLR_MAX)
+        sign_val = _bp2_sign(msg)
+        sign_node = reduce(np.multiply, sign_val) * syndrome
+        sign_val = sign_val * sign_node[seg]
+        msg = np.abs(msg)
+        min_val = reduce(np.minimum, msg)
+        msg = msg - min_val[seg]
+        msg = np.where(msg == 0, _LARGE, msg)
+        min_val2 = reduce(np.minimum, msg) + min_val
+        node_sum = reduce(np.add, msg) - (2 * _LARGE - 1.0)
+        double_min = 0.5 * (1 - np.sign(node_sum))
+        min_val_e = (1 - double_min) * min_val + double_min * min_val2
+        return sign_val * np.where(msg == _LARGE, min_val_e[seg], min_val[seg])
+    # _cn_update_tanh (:575-623)
+    t = np.tanh(msg / 2)
+    t = np.where(t == 0, _TANH_ZERO, t)
+    prod = reduce(np.multiply, t) * syndrome
+    q = t ** -1 * prod[seg]
+    q = np.where(np.abs(q) < _TANH_SMALL, 0.0, q)
+    q = np.clip(q, -_ATANH_CLIP, _ATANH_CLIP)
+    return 2 * np.arctanh(q)
+
+
+def bp2_decode(hx, synd, num_iter, cn_type, factor, llr_ch=None, llr_const=None):
+    """LDPCBPDecoder.call with is_syndrome=True (decoding.py:874-1048) on the parity-check matrix hx [m,n], in float64 with the reference's
+    batch-minor edge tensors.  synd [B,m]; llr_ch [B,n] logits (log p(1)/p(0)) or llr_const for every bit.  Returns (soft [B,n], hard [B,n]):
+    the output logits -(-clip(llr) + sum of incoming messages) (:1025-1031) and their hard decisions 0 < logit (:1033-1034)."""
+    hx = np.asarray(hx)
+    synd = np.asarray(synd)
+    B, (m, n) = synd.shape[0], hx.shape
+    chk, var = np.nonzero(hx)  # check-major edges, ascending bits inside a check
+    E = chk.size
+    first = np.r_[True, chk[1:] != chk[:-1]] if E else np.zeros(0, bool)
+    starts = np.flatnonzero(first)
+    seg = np.cumsum(first) - 1
+    syndrome = ((-1.0) ** synd.T.astype(_D))[chk[starts]]  # (:904-908), for the non-empty checks
+    if llr_ch is None:
+        llr = np.full((n, B), _D(F(llr_const)))
+    else:
+        llr = np.asarray(llr_ch, F).T.astype(_D)
+    llr = -1.0 * np.clip(llr, -_LLR_MAX, _LLR_MAX)  # (:918-920, :940)
+    fac = _D(F(factor))
+
+    def vn_sum(msg):  # reduce_sum over each bit's edges (a bit without edges sums to 0)
+        idx = (var[:, None] * B + np.arange(B)[None, :]).ravel()
+        return np.bincount(idx, weights=msg.ravel(), minlength=n * B).reshape(n, B)
+
+    msg = np.zeros((E, B))  # check-to-bit messages
+    for _ in range(num_iter):
+        x = vn_sum(msg) + llr  # _vn_update (:511-537)
+        msg_vn = -1.0 * msg + x[var]
+        msg = _bp2_cn(cn_type, msg_vn, seg, starts, syndrome) * fac  # (:988-991)
+    x_hat = -1.0 * (llr + vn_sum(msg))
+    return np.ascontiguousarray(x_hat.T), np.ascontiguousarray((0.0 < x_hat).T.astype(np.uint8))
