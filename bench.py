@@ -1,8 +1,14 @@
 #!/usr/bin/env python3
 """bench.py — decoded codewords/s of the BP4 + feedback-GNN sandwich (and of GNN_BP4) on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config c3|c4|c5]   (N > 1: starts N ranks itself, one per GPU, before touching a GPU)
+    python bench.py --gpus N --steps K --warmup W [--config c3|c4|c5] [--full]   (N > 1: starts N ranks itself, one per GPU, before touching a GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run does only what its headline figure needs: it builds (or finds up to date) the libraries, sets up, runs the settle phase
+and the W warm-up steps, times the K steps, writes --dump-outputs if asked, and prints the line (`roofline`, `counts`, `dist` come
+from the timed region itself).  `--full` adds everything that takes runs of its own: the CPU baselines and the GPU == oracle check on
+their sample, the same step under the other forms with their `forms_agreement`, `extras`, and the other stream count of the published
+workloads.  Without `--full` the line carries `"full": false`, `reassociated_forms: null`, and none of the keys those legs write.
 
 `--config` picks the BASELINE.json configuration (per-GPU shard of it; default c3):
   c3  configs[2]  [[882,24]]  sandwich BP4-64 + feedback GNN + BP4-16, 65 536 codewords per GPU and step (n882.py:45-66) — the headline
@@ -16,7 +22,7 @@
   n1270_5r / n1270_coarse   n1270.ipynb cells 4 and 9 (five rounds at p = 0.08; the coarse GNN at p = 0.02)
   n882_3r / n882_5r / n1270_3r   the workloads of the reference's only published timings (one RTX 4090, TF-XLA):
                   (64, G, 16) x 3 or 5 feedback rounds, batch_size 5 000, p = 0.05 / 0.07 (n882.py:13,39,56-66, n1270.py:57-70); timed on one
-                  stream (`value`) and with consecutive batches alternating between two HIP streams (`two_streams`) in the same run.
+                  stream (`value`) and, with --full, with consecutive batches alternating between two HIP streams (`two_streams`) in the same run.
 `--cn-type` / `--factor` set the check-node rule and normalization factor of every decoder (default: the configuration's).
 `--dump-outputs DIR` writes what the last timed step of rank 0 computed to DIR/<name>.npy (float32 / float64, at most 64 MB): `flags`
 (per sample: bit 0 flagged, bit 1 block error), `counts` (the timed region's counters), and `noise_x`, `noise_z`, `x_hat`, `z_hat`
@@ -27,7 +33,7 @@ One "step" = one Monte-Carlo batch through the whole hot path, everything on dev
 (c3 / c4: BP4 -> flag update -> feedback GNN (trained weights) -> BP4 -> masked merge; c5: GNN_BP4) -> residual check -> counters, at
 p = 0.01, p0 = 0.05.  Every sample goes through every stage and every iteration with NO data-dependent shortcut (no compaction, no
 early exit, the exact saturation shortcut of the product default switched OFF): the operation count per codeword is a constant, like
-the reference's fixed dataflow; the shortcut / compaction variants (bit-identical outputs) are reported under `extras`.  Batches are
+the reference's fixed dataflow; the shortcut / compaction variants (bit-identical outputs) are reported under `extras` (--full).  Batches are
 sharded over ranks by global sample index with no data-path collective; the three counters are all-reduced once at the end ("weak"
 scaling: per-GPU batch fixed).
 
@@ -36,7 +42,7 @@ formulas term by term: one reduce_logsumexp per edge in the qubit update (decodi
 feedback GNN (feedback_gnn.py:175-184 / gnn.py:573-610) — `config` names them (`gnn_association: literal`, `bp4_qubit_update_lse: per edge
 (literal)`), and `literal_forms` repeats the figure under the key earlier rounds used.  The two OPT-IN re-associations (include/fgnn.h
 options 4 and 5: the log-sum-exp term shared per qubit side, the GNNs' Dense layers factored; the same real-number functions, statistically
-the same decoder, NOT the reference's operation sequence) are timed in the same run on single-GPU runs and reported under
+the same decoder, NOT the reference's operation sequence) are timed in the same run on single-GPU --full runs and reported under
 `extras.reassociated_forms` {value, ms_per_step, forms_agreement} next to the opt-in hardware-transcendental variant; `forms_agreement`
 decodes the first timed batch under both and reports, per sample, how many final decisions differ and how far the marginals are apart
 (north-star bar: decisions identical, LLRs within 1e-4 — which the re-associated forms do NOT meet on every sample: DESIGN.md §3).
@@ -63,7 +69,7 @@ launch time / 8 TB/s.  `roofline.gnn` prices the feedback-GNN launch the same wa
 `dist` is the multi-GPU pre-flight: world size and backend as torch.distributed reports them and one row per rank (LOCAL_RANK -> device
 index, name, uuid, pid) gathered by all-gather; a rank that is not on cuda:LOCAL_RANK under RCCL exits 6, ranks sharing a device exit 7.
 
-`cpu_baseline` times the oracle (a C port of the reference arithmetic, OpenMP over codewords) on the host cores on a bounded sample of
+`cpu_baseline` (--full) times the oracle (a C port of the reference arithmetic, OpenMP over codewords) on the host cores on a bounded sample of
 the same workload; `cpu_baseline_tf_like` times an op-for-op restatement of how the reference executes on a host (batch-minor [E,B]
 tensors, one framework op at a time: oracle/torch_cpu_baseline.py; c5: the batched-matmul NumPy restatement oracle/numpy_ref.py) —
 TensorFlow itself can run on neither box.  Both CPU legs run BEFORE the GPU is touched, in a child interpreter whose thread pools end with
@@ -278,16 +284,19 @@ def parse_args(argv=None):
     ap.add_argument("--streams", type=int, default=1,
                     help="HIP streams consecutive batches alternate between (Sandwich_BP_GNN_Evaluation_Model(streams=)); the published-workload "
                          "configurations time 1 and 2 in the same run")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baselines and the GPU == oracle check on their sample, "
+                         "the other forms with forms_agreement and extras (single-GPU runs), the published workloads' other stream count")
     ap.add_argument("--cpu-sample", type=int, default=-1,
-                    help="codewords for the CPU baseline (0 = skip, -1 = sized from a probe to ~12 s of CPU work)")
+                    help="--full: codewords for the CPU baseline (0 = skip, -1 = sized from a probe to ~12 s of CPU work)")
     ap.add_argument("--cpu-baseline", default="both", choices=["both", "port", "torch", "none"],
-                    help="which CPU legs to time: the C port of the reference arithmetic, the TF-CPU-shaped restatement, or both")
-    ap.add_argument("--no-extras", action="store_true")
+                    help="--full: which CPU legs to time: the C port of the reference arithmetic, the TF-CPU-shaped restatement, or both")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip extras")
     ap.add_argument("--no-build", action="store_true",
                     help="do not run make: only check that the libraries exist (profiled runs, child ranks)")
     ap.add_argument("--no-literal", "--no-other-forms", dest="no_literal", action="store_true",
-                    help="skip the timing of the other forms (the opt-in re-associations on a default run) and the forms_agreement decode "
-                         "(profiled runs: only the launches of the warm-up and of the timed region reach the trace)")
+                    help="--full: skip the timing of the other forms (the opt-in re-associations on a default run) and the forms_agreement "
+                         "decode (profiled runs: only the launches of the warm-up and of the timed region reach the trace)")
     ap.add_argument("--settle-ms", type=float, default=250.0,
                     help="untimed GPU work (an elementwise torch loop, none of this library's kernels) before the warm-up steps, in ms of wall time")
     ap.add_argument("--cpu-legs-to", default=None, help=argparse.SUPPRESS)  # internal: run the CPU legs only and pickle them to this path
@@ -863,7 +872,7 @@ def main():
         with open(args.cpu_legs_to, "wb") as f:
             pickle.dump(res, f)
         return
-    if rank == 0 and world == 1 and args.cpu_sample != 0 and args.cpu_baseline != "none":
+    if args.full and rank == 0 and world == 1 and args.cpu_sample != 0 and args.cpu_baseline != "none":
         import pickle
         import subprocess
         import tempfile
@@ -1005,7 +1014,7 @@ def main():
 
         launches_per_step = 2 * len(iters) - 1  # BP4 launches + feedback-GNN launches
     # Headline = the reference's fixed dataflow: every exp/log of every iteration is evaluated.  The product
-    # default (exact wave-uniform shortcut for saturated nodes, same bits) is timed separately under `extras`.
+    # default (exact wave-uniform shortcut for saturated nodes, same bits) is timed separately under `extras` (--full).
     g.set_saturation_shortcut(False)
     if kept is not None:
         # every step ends in one residual check of the noise against the decisions (Sandwich_BP_GNN_Evaluation_Model.mc_step / step
@@ -1084,7 +1093,7 @@ def main():
         # default, the literal forms when an A/B run made the re-associated ones the headline; same bracket, same sample stream ----
         other_forms = None
         headline_is_literal = not factored and (is_c5 or not shared_lse)
-        if world == 1 and not args.no_literal and (headline_is_literal or factored or shared_lse):
+        if args.full and world == 1 and not args.no_literal and (headline_is_literal or factored or shared_lse):
             to_reassociated = headline_is_literal
             g.set_gnn_factored(to_reassociated)
             if not is_c5:
@@ -1109,7 +1118,7 @@ def main():
         # ---- the reference's published workloads run 5 000-codeword batches (n882.py:39): one such batch fills a fraction of the chip,
         # so the same step is also timed with consecutive batches alternating between two HIP streams (same samples, same counters)
         other_streams = None
-        if args.config in PUBLISHED_CONFIGS and not is_c5:
+        if args.full and args.config in PUBLISHED_CONFIGS and not is_c5:
             ns = 1 if args.streams > 1 else 2
             model_o = make_model(ns)
 
@@ -1138,7 +1147,7 @@ def main():
         info = g.info()
         common = {"value": value, "unit": "codewords/s", "n_gpus": world, "steps": K, "warmup": W,
                   "ms_per_step": elapsed / K * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-                  "dtype": "f32", "data": "synthetic"}
+                  "dtype": "f32", "data": "synthetic", "full": args.full}
         counts_obj = {"flagged": int(cnt[0]), "block_errors": int(cnt[1]), "samples": int(cnt[2])}
         if is_c5:
             out = dict({"metric": "decoded codewords/sec, [[1270,28]] GNN_BP4 full-GNN decoder, 10 iterations"}, **common, **{
@@ -1209,10 +1218,10 @@ def main():
         if other_streams is not None:
             out["two_streams" if other_streams["streams"] == 2 else "one_stream"] = other_streams
         out["value_is"] = ("the reference's formulas term by term (literal forms), the library's default operation sequence: one log-sum-exp per edge "
-                           "(decoding_q.py:254-273), one Dense per edge (feedback_gnn.py:175-184 / gnn.py:573-610); extras.reassociated_forms is the "
-                           "same step under the two opt-in re-associations" if headline_is_literal else
+                           "(decoding_q.py:254-273), one Dense per edge (feedback_gnn.py:175-184 / gnn.py:573-610); extras.reassociated_forms (--full) is "
+                           "the same step under the two opt-in re-associations" if headline_is_literal else
                            "AN A/B RUN, not the library default: the opt-in re-associated forms named in `config` (FGNN_BENCH_BP4_LSE / "
-                           "FGNN_BENCH_GNN_ORDER); literal_forms.value is the same step with the reference's formulas term by term")
+                           "FGNN_BENCH_GNN_ORDER); literal_forms.value (--full) is the same step with the reference's formulas term by term")
         # ---- multi-GPU proof of the sharding (no 8-GPU node needed to test it: gloo world 2-3 in tests/test_bench_contract.py): every rank's
         # timed sample range and own counters; the per-step ranges of all ranks must tile [W*world*B, (W+K)*world*B) without overlap, and the
         # ranks' own counters must add up to the all-reduced ones
@@ -1223,7 +1232,7 @@ def main():
         out["dist"]["sharding"], sharding_ok = sharding_report(step_ranges, rank_rows, W, K, world, B, cnt)
 
     fa = None
-    if rank == 0 and world == 1 and not args.no_literal:
+    if args.full and rank == 0 and world == 1 and not args.no_literal:
         # ---- per-sample agreement of the opt-in re-associated forms with the literal ones on the first batch of the timed region ----
         first_timed = W * world * B  # rank 0's first timed batch starts at global sample W * world * B
         ex, ez = g.pauli_noise(SEED, args.p, first_timed, B)
@@ -1264,9 +1273,9 @@ def main():
             out["speedup_vs_cpu"] = value / out["cpu_baseline"]["value"]
         if "cpu_baseline_tf_like" in out:
             out["speedup_vs_cpu_tf_like"] = value / out["cpu_baseline_tf_like"]["value"]
-        if not args.no_extras and not is_c5:
+        if args.full and not args.no_extras and not is_c5:
             out["extras"] = sandwich_extras(g, model, code, decs, G, iters, B, args.p, SEED, args.cn_type, args.factor, args.p0)
-        elif not args.no_extras:
+        elif args.full and not args.no_extras:
             out["extras"] = {}
         if "extras" in out:
             # the opt-in re-associated forms (NOT the reference's operation sequence) next to the other opt-in variants, with their agreement
@@ -1276,8 +1285,8 @@ def main():
                 out["extras"]["forms_agreement (this A/B run's re-associated headline vs the literal forms)"] = fa
         elif other_forms is not None and headline_is_literal:  # --no-extras: keep the figure, under its own key
             out["reassociated_forms"] = dict(other_forms, forms_agreement=fa)
-        elif args.no_literal:
-            out["reassociated_forms"] = None  # --no-literal / --no-other-forms: not timed, and the line says so
+        elif args.no_literal or not args.full:
+            out["reassociated_forms"] = None  # a plain run or --no-literal / --no-other-forms: not timed, and the line says so
     if rank == 0:
         print(json.dumps(out))
         sys.stdout.flush()

@@ -24,10 +24,10 @@ def test_algorithmic_bytes_are_the_survey_figures():
 
 @pytest.mark.gpu
 def test_bench_prints_one_contract_line():
-    """A small run of the real bench (same code path as the driver's, batch 2 048): one JSON line with every contract field,
-    the roofline and cpu_baseline objects, and a GPU result that equals the CPU oracle's on the sampled codewords."""
+    """A small --full run of the real bench (batch 2 048): one JSON line with every contract field, the roofline and cpu_baseline
+    objects, and a GPU result that equals the CPU oracle's on the sampled codewords."""
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "2048",
-                          "--cpu-sample", "256", "--no-extras"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
+                          "--cpu-sample", "256", "--no-extras", "--full"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
                          timeout=600, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [l for l in res.stdout.splitlines() if l.strip()]
@@ -95,6 +95,32 @@ def test_bench_prints_one_contract_line():
     assert abs(r["frac_of_hw_transcendental_rate"] - hw) < 1e-9 and r["hw_transcendental_peak_per_s"] == 1024 * 64 * 2.4e9 / 8
 
 
+def test_full_is_off_by_default():
+    import bench
+    assert bench.parse_args([]).full is False and bench.parse_args(["--full"]).full is True
+
+
+@pytest.mark.gpu
+def test_a_plain_bench_run_times_the_headline_only():
+    """`bench.py --steps K --warmup W` without --full: the contract line and what the timed region itself yields (roofline, counts,
+    dist), and none of the legs that take runs of their own — no CPU baselines, no other forms, no extras."""
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "2048"],
+                         stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600, cwd=ROOT)
+    assert res.returncode == 0, res.stderr[-2000:]
+    lines = [l for l in res.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, res.stdout
+    d = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                "vs_baseline", "dtype", "data", "config", "roofline", "counts", "dist", "literal_forms"):
+        assert key in d, key
+    assert d["full"] is False and d["steps"] == 2 and d["warmup"] == 1 and d["counts"]["samples"] == 2 * 2048
+    assert abs(d["value"] - 2 * 2048 / (d["ms_per_step"] * 2e-3)) < 1e-6 * d["value"] and d["literal_forms"]["value"] == d["value"]
+    assert d["roofline"]["launches_timed"] == 2 and d["dist"]["sharding"]["ranges_tile_the_region_without_overlap"] is True
+    assert d["reassociated_forms"] is None
+    for key in ("cpu_baseline", "cpu_baseline_tf_like", "speedup_vs_cpu", "extras", "two_streams", "one_stream"):
+        assert key not in d, key
+
+
 def test_config_shapes_and_the_algorithmic_counts_of_the_other_two_configs():
     """--config c3 | c4 | c5 = BASELINE.json configs[2] / [3] / [4] at their per-GPU shard; the per-codeword figures the rooflines are
     priced with: exp / log evaluations of a fixed-dataflow BP4 decode (decoding_q.py:254-273, 365-431, 455-471) and the GNN_BP4 FLOPs of
@@ -156,7 +182,7 @@ def test_bench_lines_of_the_other_two_configs(config, batch):
     (c5: against the f32 MFMA peak in the reference's FLOPs) and cpu_baseline, GPU == oracle on the sampled codewords; at a batch
     that has no PMC entry `--require-roofline` turns the null fraction into exit code 5 AFTER the line has been printed."""
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", config, "--steps", "2", "--warmup", "1", "--batch", str(batch),
-                          "--cpu-sample", "32", "--no-extras", "--require-roofline"], stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                          "--cpu-sample", "32", "--no-extras", "--require-roofline", "--full"], stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                          text=True, timeout=900, cwd=ROOT)
     assert res.returncode == 5 and "--require-roofline" in res.stderr, res.stderr[-2000:]
     lines = [l for l in res.stdout.splitlines() if l.strip()]
@@ -196,7 +222,7 @@ def test_bench_lines_of_the_bp4_only_configs():
         # configs[0] as the reference constructs it (cn_type='boxplus', normalization_factor=0.625: decoding_q.py:18-22), then the
         # QLDPC.ipynb cell 11 helper's 'boxplus-phi' variant of the same case
         res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c1", "--steps", "4", "--warmup", "1", "--cpu-sample", "32",
-                              "--no-extras", "--require-roofline"] + extra, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900, cwd=ROOT)
+                              "--no-extras", "--require-roofline", "--full"] + extra, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900, cwd=ROOT)
         d = json.loads([l for l in res.stdout.splitlines() if l.strip()][0])
         r = d["roofline"]
         ent, _ = bench.pmc_entry("bp4", key)
@@ -214,7 +240,7 @@ def test_bench_lines_of_the_bp4_only_configs():
         assert d["counts"]["samples"] == 4 * 256 and d["literal_forms"]["value"] > 0
         assert d["dist"]["world_size"] == 1 and d["dist"]["ranks"][0]["device_index"] == 0 and "value_is" in d
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c2", "--steps", "2", "--warmup", "1", "--batch", "2048",
-                          "--cpu-sample", "32", "--no-extras", "--no-build"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
+                          "--cpu-sample", "32", "--no-extras", "--no-build", "--full"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
                          timeout=900, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-2000:]
     d = json.loads([l for l in res.stdout.splitlines() if l.strip()][0])
@@ -229,7 +255,7 @@ def test_bench_line_of_a_published_workload():
     16), batch_size 5 000, p = 0.05, n882.py:39,56-66) — one stream and two streams timed in the same run, literal forms and the
     per-sample agreement at p = 0.05, GPU == oracle on the sampled codewords."""
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "n882_3r", "--steps", "3", "--warmup", "1", "--cpu-sample", "32",
-                          "--no-extras"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900, cwd=ROOT)
+                          "--no-extras", "--full"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-2000:]
     d = json.loads([l for l in res.stdout.splitlines() if l.strip()][0])
     assert d["config"]["bp_iters"] == [64, 16, 16, 16] and d["config"]["batch_per_gpu"] == 5000 and d["config"]["p"] == 0.05

@@ -24,22 +24,22 @@ cp $O/traffic.json profiles/traffic.json
 cp profiles/traffic.json $O/traffic_after_counts.json
 fi
 if has lines; then
-python bench.py --no-build --steps 20 --warmup 5 --require-roofline > $O/bench_c3.json 2> $O/bench.err   # the driver's own command line
-python bench.py --no-build --config c4 --require-roofline > $O/bench_c4.json 2>> $O/bench.err
-python bench.py --no-build --config c5 --require-roofline > $O/bench_c5.json 2>> $O/bench.err
+python bench.py --no-build --full --steps 20 --warmup 5 --require-roofline > $O/bench_c3.json 2> $O/bench.err   # the driver's command line, with --full
+python bench.py --no-build --full --config c4 --require-roofline > $O/bench_c4.json 2>> $O/bench.err
+python bench.py --no-build --full --config c5 --require-roofline > $O/bench_c5.json 2>> $O/bench.err
 # configs[0] as the reference constructs it (cn_type='boxplus', normalization_factor=0.625) and the QLDPC.ipynb cell 11 variant ('boxplus-phi')
-python bench.py --no-build --config c1 --steps 50 --warmup 5 --require-roofline > $O/bench_c1_boxplus.json 2>> $O/bench.err
-python bench.py --no-build --config c1 --cn-type boxplus-phi --steps 50 --warmup 5 --require-roofline > $O/bench_c1_boxplus_phi.json 2>> $O/bench.err
-python bench.py --no-build --config c2 --require-roofline > $O/bench_c2.json 2>> $O/bench.err
+python bench.py --no-build --full --config c1 --steps 50 --warmup 5 --require-roofline > $O/bench_c1_boxplus.json 2>> $O/bench.err
+python bench.py --no-build --full --config c1 --cn-type boxplus-phi --steps 50 --warmup 5 --require-roofline > $O/bench_c1_boxplus_phi.json 2>> $O/bench.err
+python bench.py --no-build --full --config c2 --require-roofline > $O/bench_c2.json 2>> $O/bench.err
 # the workloads of the reference's published timings: batch_size 5 000, one and two streams in the same run
-python bench.py --no-build --config n882_3r --steps 100 --warmup 5 --require-roofline > $O/bench_n882_3r.json 2>> $O/bench.err
-python bench.py --no-build --config n882_5r --steps 100 --warmup 5 --require-roofline > $O/bench_n882_5r.json 2>> $O/bench.err
-python bench.py --no-build --config n1270_3r --steps 100 --warmup 5 --require-roofline > $O/bench_n1270_3r.json 2>> $O/bench.err
-python bench.py --no-build --config n1270_5r --steps 100 --warmup 5 --require-roofline > $O/bench_n1270_5r.json 2>> $O/bench.err
-python bench.py --no-build --config n1270_coarse --steps 100 --warmup 5 --require-roofline > $O/bench_n1270_coarse.json 2>> $O/bench.err
-python bench.py --no-build --config osd_bp4_minsum --steps 20 --warmup 3 --require-roofline > $O/bench_osd_bp4_minsum.json 2>> $O/bench.err
-python bench.py --no-build --config qldpc_882 --steps 100 --warmup 5 --require-roofline > $O/bench_qldpc_882.json 2>> $O/bench.err
-python bench.py --no-build --config qldpc_1270 --steps 100 --warmup 5 --require-roofline > $O/bench_qldpc_1270.json 2>> $O/bench.err
+python bench.py --no-build --full --config n882_3r --steps 100 --warmup 5 --require-roofline > $O/bench_n882_3r.json 2>> $O/bench.err
+python bench.py --no-build --full --config n882_5r --steps 100 --warmup 5 --require-roofline > $O/bench_n882_5r.json 2>> $O/bench.err
+python bench.py --no-build --full --config n1270_3r --steps 100 --warmup 5 --require-roofline > $O/bench_n1270_3r.json 2>> $O/bench.err
+python bench.py --no-build --full --config n1270_5r --steps 100 --warmup 5 --require-roofline > $O/bench_n1270_5r.json 2>> $O/bench.err
+python bench.py --no-build --full --config n1270_coarse --steps 100 --warmup 5 --require-roofline > $O/bench_n1270_coarse.json 2>> $O/bench.err
+python bench.py --no-build --full --config osd_bp4_minsum --steps 20 --warmup 3 --require-roofline > $O/bench_osd_bp4_minsum.json 2>> $O/bench.err
+python bench.py --no-build --full --config qldpc_882 --steps 100 --warmup 5 --require-roofline > $O/bench_qldpc_882.json 2>> $O/bench.err
+python bench.py --no-build --full --config qldpc_1270 --steps 100 --warmup 5 --require-roofline > $O/bench_qldpc_1270.json 2>> $O/bench.err
 cat $O/bench_c3.json
 echo "bench stderr:"; cat $O/bench.err || true
 fi
