@@ -20,6 +20,7 @@
 
 #include "fgnn_internal.h"
 #include "fgnn_math.h"
+#include "fgnn_mlp.h"
 
 namespace {
 
@@ -394,15 +395,6 @@ struct GnnGenBwArgs {
     float* deltas[FGNN_GEN_MAX_LAYERS];     // layer li: [rows_li, J_li]
 };
 
-__device__ __forceinline__ float gen_act_bw(float a, int act)
-{
-    switch (act) {
-    case FGNN_ACT_TANH: return fg_tanh(a);
-    case FGNN_ACT_RELU: return FG_MAX(a, 0.0f);
-    case FGNN_ACT_SIGMOID: return fg_sigmoid(a);
-    default: return a;
-    }
-}
 __device__ __forceinline__ float gen_act_deriv(float h, int act)
 {
     switch (act) {
@@ -410,18 +402,6 @@ __device__ __forceinline__ float gen_act_deriv(float h, int act)
     case FGNN_ACT_RELU: return h > 0.0f ? 1.0f : 0.0f;
     case FGNN_ACT_SIGMOID: return h * (1.0f - h);
     default: return 1.0f;
-    }
-}
-__device__ __forceinline__ void gen_dense_bw(const GnnGeneralDev& w, int li, const float* in, float* out)
-{
-    const int K = w.K[li], J = w.J[li], act = w.act_l[li];
-    const float* W = w.W[li];
-    const float* b = w.b[li];
-    for (int j = 0; j < J; ++j) {
-        float a = 0.0f;
-        for (int k = 0; k < K; ++k) a = FG_FMA(in[k], W[k * J + j], a);
-        if (b) a = a + b[j];
-        out[j] = gen_act_bw(a, act);
     }
 }
 // d in[k] = sum_j W[k][j] delta[j]
@@ -470,7 +450,7 @@ __global__ void __launch_bounds__(256) gnn_general_backward_kernel(GraphDev g, G
                 ha[0][1] = X;
                 ha[0][2] = Y;
                 ha[0][3] = Z;
-                for (int l = 0; l < L; ++l) gen_dense_bw(w, s * L + l, ha[l], ha[l + 1]);
+                for (int l = 0; l < L; ++l) gen_dense(w, s * L + l, ha[l], ha[l + 1]);
                 for (int i = 0; i < D; ++i) {
                     const float m = ha[L][i];
                     float r;
@@ -492,7 +472,7 @@ __global__ void __launch_bounds__(256) gnn_general_backward_kernel(GraphDev g, G
                     ha[0][1] = X;
                     ha[0][2] = Y;
                     ha[0][3] = Z;
-                    for (int l = 0; l < L; ++l) gen_dense_bw(w, s * L + l, ha[l], ha[l + 1]);
+                    for (int l = 0; l < L; ++l) gen_dense(w, s * L + l, ha[l], ha[l + 1]);
                     for (int i = 0; i < D; ++i) cnt[s][i] += (ha[L][i] == acc[i]) ? 1.0f : 0.0f;
                 }
             }
@@ -503,7 +483,7 @@ __global__ void __launch_bounds__(256) gnn_general_backward_kernel(GraphDev g, G
         // ---- embed MLP + _llr_inv_embed: forward with every activation kept, then backward ----
         const size_t nrow = (size_t)b * n + v;
         for (int k = 0; k < 2 * D + 3; ++k) ha[0][k] = z[k];
-        for (int l = 0; l < L - 1; ++l) gen_dense_bw(w, 2 * L + l, ha[l], ha[l + 1]);
+        for (int l = 0; l < L - 1; ++l) gen_dense(w, 2 * L + l, ha[l], ha[l + 1]);
         for (int l = 0; l < L; ++l) {  // inputs of the L - 1 embed layers and of _llr_inv_embed (layer 3L - 1, input ha[L - 1])
             const int li = l < L - 1 ? 2 * L + l : 3 * L - 1, K = w.K[li];
             float* o = a.acts[li] + nrow * K;
@@ -544,7 +524,7 @@ __global__ void __launch_bounds__(256) gnn_general_backward_kernel(GraphDev g, G
                 ha[0][1] = X;
                 ha[0][2] = Y;
                 ha[0][3] = Z;
-                for (int l = 0; l < L; ++l) gen_dense_bw(w, s * L + l, ha[l], ha[l + 1]);
+                for (int l = 0; l < L; ++l) gen_dense(w, s * L + l, ha[l], ha[l + 1]);
                 for (int l = 0; l < L; ++l) {
                     const int li = s * L + l, K = w.K[li];
                     float* o = a.acts[li] + row * K;

@@ -13,6 +13,7 @@
 
 #include "fgnn_internal.h"
 #include "fgnn_math.h"
+#include "fgnn_cn.h"
 #include "fgnn_rng.h"
 
 #ifndef FGNN_BP2_WAVES
@@ -32,81 +33,6 @@ struct Bp2Args {
     float* soft_out;       // [B,n] or null
     uint8_t* hard_out;     // [B,n] or null
 };
-
-__device__ __forceinline__ unsigned sign_bit(float x) { return fg_f2u(x) >> 31; }
-__device__ __forceinline__ float with_sign(float mag, unsigned neg) { return fg_u2f(fg_f2u(mag) ^ (neg << 31)); }
-
-template <int CN_TYPE>
-__device__ __forceinline__ void cn_update2(float* msg, const int* __restrict__ slot, int deg, unsigned synd, float factor)
-{
-    if constexpr (CN_TYPE == FGNN_CN_BOXPLUS_PHI) {  // _cn_update_phi (decoding.py:637-693)
-        unsigned neg = synd;
-        float T = 0.0f;
-        for (int j = 0; j < deg; ++j) {
-            const int s = slot[j];
-            const float v = msg[s];
-            const unsigned ng = v < 0.0f;
-            neg ^= ng;
-            const float a = fg_phi_gnn(FG_ABS(v));
-            T = T + a;
-            msg[s] = with_sign(a, ng);
-        }
-        for (int j = 0; j < deg; ++j) {
-            const int s = slot[j];
-            const float w = msg[s];
-            msg[s] = with_sign(fg_phi_gnn(T - FG_ABS(w)), neg ^ sign_bit(w)) * factor;
-        }
-    } else if constexpr (CN_TYPE == FGNN_CN_MINSUM) {  // _cn_update_minsum (decoding.py:744-850)
-        const float LARGE = 10000.0f;
-        unsigned neg = synd;
-        float minv = 0.0f;
-        for (int j = 0; j < deg; ++j) {
-            const int s = slot[j];
-            const float v = FG_MIN(FG_MAX(msg[s], -20.0f), 20.0f);
-            const unsigned ng = v < 0.0f;
-            neg ^= ng;
-            const float a = FG_ABS(v);
-            minv = (j == 0) ? a : FG_MIN(minv, a);
-            msg[s] = with_sign(a, ng);
-        }
-        float min2 = 0.0f, nsum = 0.0f;
-        for (int j = 0; j < deg; ++j) {
-            float d = FG_ABS(msg[slot[j]]) - minv;
-            d = (d == 0.0f) ? LARGE : d;
-            min2 = (j == 0) ? d : FG_MIN(min2, d);
-            nsum = nsum + d;
-        }
-        min2 = min2 + minv;
-        nsum = nsum - (2.0f * LARGE - 1.0f);
-        const float sg = (nsum > 0.0f) ? 1.0f : ((nsum < 0.0f) ? -1.0f : 0.0f);
-        const float dm = 0.5f * (1.0f - sg);
-        const float min_e = (1.0f - dm) * minv + dm * min2;
-        for (int j = 0; j < deg; ++j) {
-            const int s = slot[j];
-            const float w = msg[s];
-            const float d = FG_ABS(w) - minv;
-            msg[s] = with_sign((d == 0.0f) ? min_e : minv, neg ^ sign_bit(w)) * factor;
-        }
-    } else {  // _cn_update_tanh (decoding.py:575-623)
-        float P = 1.0f;
-        for (int j = 0; j < deg; ++j) {
-            const int s = slot[j];
-            float t = fg_tanh(msg[s] / 2.0f);
-            t = (t == 0.0f) ? 1e-12f : t;
-            P = (j == 0) ? t : P * t;
-            msg[s] = t;
-        }
-        P = P * (synd ? -1.0f : 1.0f);
-        const float clipv = 0.99999988f;
-        for (int j = 0; j < deg; ++j) {
-            const int s = slot[j];
-            float q = fg_rcp_unit(msg[s]) * P;
-            q = (FG_ABS(q) < 1e-7f) ? 0.0f : q;
-            q = FG_MIN(FG_MAX(q, -clipv), clipv);
-            msg[s] = (2.0f * fg_atanh(q)) * factor;
-        }
-    }
-}
 
 // N evaluations of fg_phi_gnn with the table reads of all 2N logarithms in flight together: the float operations of
 // fg_phi_gnn (fg_exp, then fg_log(y + 1) - fg_log(y - 1)) in the same order, only the instruction schedule differs.
@@ -149,8 +75,8 @@ __device__ __forceinline__ void phi_gnn_n(const float (&x)[N], float (&out)[N])
 }
 
 // _cn_update_phi (decoding.py:637-693) for a check of compile-time degree DC: its DC messages are read once, live in registers
-// between the two phi passes (cn_update2 parks phi(|v|) in LDS and reads it back) and are written once; signs travel as bit 31
-// of integer words.  Same float operations in the same order as cn_update2<FGNN_CN_BOXPLUS_PHI>.
+// between the two phi passes (cn_update parks phi(|v|) in LDS and reads it back) and are written once; signs travel as bit 31
+// of integer words.  Same float operations in the same order as cn_update<FGNN_CN_BOXPLUS_PHI, PhiGnn> (fgnn_cn.h).
 template <int DC>
 __device__ __forceinline__ void cn2_phi_regular(float* msg, const unsigned (&off)[DC], unsigned synd, float factor, bool f1)
 {
@@ -158,8 +84,8 @@ __device__ __forceinline__ void cn2_phi_regular(float* msg, const unsigned (&off
     uint32_t neg = synd << 31;
 #pragma unroll
     for (int j = 0; j < DC; ++j) {
-        v[j] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(msg) + off[j]);
-        // cn_update2 tests v < 0: a message of -0 counts as positive there, and its parked copy carries no sign either
+        v[j] = slot_ref(msg, off[j]);
+        // cn_update tests v < 0: a message of -0 counts as positive there, and its parked copy carries no sign either
         neg ^= (v[j] < 0.0f) ? 0x80000000u : 0u;
     }
 #pragma unroll
@@ -182,50 +108,11 @@ __device__ __forceinline__ void cn2_phi_regular(float* msg, const unsigned (&off
         phi_gnn_n<FGNN_BP2_PHI_STAGE>(xa, oa);
 #pragma unroll
         for (int k = 0; k < FGNN_BP2_PHI_STAGE; ++k) {
-            // sign of the parked word with_sign(phi(|v|), v < 0) that cn_update2 reads back
+            // sign of the parked word with_sign(phi(|v|), v < 0) that cn_update reads back
             const uint32_t sg = neg ^ ((v[j + k] < 0.0f) ? 0x80000000u : 0u) ^ (fg_f2u(aa[j + k]) & 0x80000000u);
             const float o = fg_u2f(fg_f2u(oa[k]) ^ sg);
-            *reinterpret_cast<float*>(reinterpret_cast<char*>(msg) + off[j + k]) = f1 ? o : o * factor;
+            slot_ref(msg, off[j + k]) = f1 ? o : o * factor;
         }
-    }
-}
-
-// _cn_update_minsum (decoding.py:744-850) on a check of compile-time degree DC, registers only: same float operations in the same
-// order as cn_update2<FGNN_CN_MINSUM>.  deg < DC (runtime-degree graphs compiled for a maximum degree): edge j takes part iff j < deg;
-// the guards fold away when deg == DC.
-template <int DC>
-__device__ __forceinline__ void cn2_minsum_regular(float* msg, const unsigned (&off)[DC], int deg, unsigned synd, float factor)
-{
-    const float LARGE = 10000.0f;
-    float a[DC];
-    unsigned ng[DC];
-    unsigned neg = synd;
-    float minv = 0.0f;
-#pragma unroll
-    for (int j = 0; j < DC; ++j) {
-        const float v = (j < deg) ? FG_MIN(FG_MAX(*reinterpret_cast<const float*>(reinterpret_cast<const char*>(msg) + off[j]), -20.0f), 20.0f) : 1.0f;
-        ng[j] = v < 0.0f;
-        neg ^= ng[j];
-        a[j] = FG_ABS(v);
-        minv = (j == 0) ? a[j] : ((j < deg) ? FG_MIN(minv, a[j]) : minv);
-    }
-    float min2 = 0.0f, nsum = 0.0f;
-#pragma unroll
-    for (int j = 0; j < DC; ++j) {
-        float d = a[j] - minv;
-        d = (d == 0.0f) ? LARGE : d;
-        min2 = (j == 0) ? d : ((j < deg) ? FG_MIN(min2, d) : min2);
-        nsum = (j < deg) ? nsum + d : nsum;
-    }
-    min2 = min2 + minv;
-    nsum = nsum - (2.0f * LARGE - 1.0f);
-    const float sg = (nsum > 0.0f) ? 1.0f : ((nsum < 0.0f) ? -1.0f : 0.0f);
-    const float dm = 0.5f * (1.0f - sg);
-    const float min_e = (1.0f - dm) * minv + dm * min2;
-#pragma unroll
-    for (int j = 0; j < DC; ++j) {
-        const float out = ((a[j] - minv) == 0.0f) ? min_e : minv;
-        if (j < deg) *reinterpret_cast<float*>(reinterpret_cast<char*>(msg) + off[j]) = with_sign(out, neg ^ ng[j]) * factor;
     }
 }
 
@@ -303,7 +190,7 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_
                     unsigned off[DC];
 #pragma unroll
                     for (int j = 0; j < DC; ++j) off[j] = (w[j >> 1] >> ((j & 1) * 16)) & 0xffffu;
-                    if constexpr (CN_TYPE == FGNN_CN_MINSUM) cn2_minsum_regular<DC>(msg, off, DC, sy, a.factor);
+                    if constexpr (CN_TYPE == FGNN_CN_MINSUM) cn_minsum_regular<DC>(msg, off, DC, sy, a.factor);
                     else cn2_phi_regular<DC>(msg, off, sy, a.factor, f1);
                 } else if constexpr (DC > 0 && CN_TYPE == FGNN_CN_MINSUM) {
                     // runtime degrees up to DC: the slot list is read once (all loads in flight together), then the regular update with
@@ -312,10 +199,10 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_
                     unsigned off[DC];
 #pragma unroll
                     for (int j = 0; j < DC; ++j) off[j] = (j < deg) ? 4u * (unsigned)g.cslot[c0 + j] : 0u;
-                    cn2_minsum_regular<DC>(msg, off, deg, sy, a.factor);
+                    cn_minsum_regular<DC>(msg, off, deg, sy, a.factor);
                 } else {
                     const int c0 = g.cptr[c], deg = g.cptr[c + 1] - c0;
-                    cn_update2<CN_TYPE>(msg, g.cslot + c0, deg, sy, a.factor);
+                    cn_update<CN_TYPE, PhiGnn>(msg, g.cslot + c0, deg, sy, a.factor);
                 }
             }
         }

@@ -21,6 +21,7 @@
 
 #include "fgnn_internal.h"
 #include "fgnn_math.h"
+#include "fgnn_cn.h"
 
 #ifndef FGNN_BP4_WAVES
 #define FGNN_BP4_WAVES 7  // waves per SIMD the register allocator must leave room for (LDS admits 5-7 workgroups of 4 waves per CU)
@@ -65,9 +66,6 @@ struct BpArgs {
     float* tape_z;            //                          [num_iter+1, B, E_z] — the tape fgnn_bp4_backward reads
     int shared_lse;           // 1: the (a - b)-dependent part of the qubit update's log-sum-exp once per qubit and side (FGNN_OPT_BP4_SHARED_LSE)
 };
-
-__device__ __forceinline__ unsigned sign_bit(float x) { return fg_f2u(x) >> 31; }
-__device__ __forceinline__ float with_sign(float mag, unsigned neg) { return fg_u2f(fg_f2u(mag) ^ (neg << 31)); }
 
 // Elementary-function policy of the kernel.  Mx<false> = fgnn_math.h: the float operations the CPU oracle executes, bit for bit
 // (the default, the headline, every parity test).  Mx<true> = the same TensorFlow op structure on the hardware's own
@@ -118,100 +116,7 @@ struct Mx<true> {
     }
 };
 
-// ---------------------------------------------------------------------------------------------
-// Check-node rules on runtime-degree rows.  `msg` = this codeword's LDS message array, `slot` =
-// the check's slot list.  Pass 1 parks |.|-type intermediates in the slots themselves (sign kept in
-// the sign bit), pass 2 writes the c->v messages.  decoding_q.py line numbers as in the oracle.
-// ---------------------------------------------------------------------------------------------
-template <int CN_TYPE, bool HWT = false>
-__device__ __forceinline__ void cn_update(float* msg, const int* __restrict__ slot, int deg, unsigned synd, float factor)
-{
-    if constexpr (CN_TYPE == FGNN_CN_BOXPLUS_PHI) {  // _cn_update_phi (:376-431)
-        unsigned neg = synd;
-        float T = 0.0f;
-        for (int j = 0; j < deg; ++j) {
-            int s = slot[j];
-            float v = msg[s];
-            unsigned ng = v < 0.0f;
-            neg ^= ng;
-            float a = Mx<HWT>::phi(FG_ABS(v));
-            T = T + a;
-            msg[s] = with_sign(a, ng);
-        }
-        for (int j = 0; j < deg; ++j) {
-            int s = slot[j];
-            float w = msg[s];
-            float out = Mx<HWT>::phi(T - FG_ABS(w));
-            msg[s] = with_sign(out, neg ^ sign_bit(w)) * factor;
-        }
-    } else if constexpr (CN_TYPE == FGNN_CN_MINSUM) {  // _cn_update_minsum (:539-644)
-        const float LARGE = 10000.0f;
-        unsigned neg = synd;
-        float minv = 0.0f;
-        for (int j = 0; j < deg; ++j) {
-            int s = slot[j];
-            float v = FG_MIN(FG_MAX(msg[s], -20.0f), 20.0f);
-            unsigned ng = v < 0.0f;
-            neg ^= ng;
-            float a = FG_ABS(v);
-            minv = (j == 0) ? a : FG_MIN(minv, a);
-            msg[s] = with_sign(a, ng);
-        }
-        float min2 = 0.0f, nsum = 0.0f;
-        for (int j = 0; j < deg; ++j) {
-            float d = FG_ABS(msg[slot[j]]) - minv;
-            d = (d == 0.0f) ? LARGE : d;
-            min2 = (j == 0) ? d : FG_MIN(min2, d);
-            nsum = nsum + d;
-        }
-        min2 = min2 + minv;
-        nsum = nsum - (2.0f * LARGE - 1.0f);
-        float sg = (nsum > 0.0f) ? 1.0f : ((nsum < 0.0f) ? -1.0f : 0.0f);
-        float dm = 0.5f * (1.0f - sg);
-        float min_e = (1.0f - dm) * minv + dm * min2;
-        for (int j = 0; j < deg; ++j) {
-            int s = slot[j];
-            float w = msg[s];
-            float d = FG_ABS(w) - minv;
-            float out = (d == 0.0f) ? min_e : minv;
-            msg[s] = with_sign(out, neg ^ sign_bit(w)) * factor;
-        }
-    } else {  // _cn_update_tanh (:313-363)
-        float P = 1.0f;
-        for (int j = 0; j < deg; ++j) {
-            int s = slot[j];
-            float t = fg_tanh(msg[s] / 2.0f);
-            t = (t == 0.0f) ? 1e-12f : t;
-            P = (j == 0) ? t : P * t;
-            msg[s] = t;
-        }
-        P = P * (synd ? -1.0f : 1.0f);
-        const float clipv = 0.99999988f;
-        for (int j = 0; j < deg; ++j) {
-            int s = slot[j];
-            float q = fg_rcp_unit(msg[s]) * P;
-            q = (FG_ABS(q) < 1e-7f) ? 0.0f : q;
-            q = FG_MIN(FG_MAX(q, -clipv), clipv);
-            msg[s] = (2.0f * fg_atanh(q)) * factor;
-        }
-    }
-}
-
-// soft syndrome of one row, _cn_update_phi_loss (:433-453)
-template <bool HWT = false>
-__device__ __forceinline__ float logit_row(const float* llr, const int* __restrict__ col, int deg)
-{
-    unsigned neg = 0;
-    float T = 0.0f;
-    for (int j = 0; j < deg; ++j) {
-        float v = llr[col[j]];
-        neg ^= (v < 0.0f);
-        T = T + Mx<HWT>::phi(FG_ABS(v));
-    }
-    return with_sign(Mx<HWT>::phi(T), neg);
-}
-
-// The same with the exact saturation shortcut: a wave whose rows all see |llr| >= 16.635532 everywhere has phi(|.|) = 0 for every
+// logit_row (fgnn_cn.h) with the exact saturation shortcut: a wave whose rows all see |llr| >= 16.635532 everywhere has phi(|.|) = 0 for every
 // term, T = 0 and phi(T) = phi(clip min) = phi0 — the soft syndrome of a converged codeword.
 template <bool HWT = false>
 __device__ __forceinline__ float logit_row_opt(const float* llr, const int* __restrict__ col, int deg, float phi0, bool shortcut)
@@ -226,7 +131,7 @@ __device__ __forceinline__ float logit_row_opt(const float* llr, const int* __re
         }
         if (__all(sat)) return with_sign(phi0, neg);
     }
-    return logit_row<HWT>(llr, col, deg);
+    return logit_row<Mx<HWT>>(llr, col, deg);
 }
 
 // N evaluations of fg_phi (fgnn_math.h) with the work of the N lanes-worth of values laid out in three stages, so that the 2N table
@@ -284,10 +189,6 @@ __device__ __forceinline__ void phi_n(const float (&x)[N], float (&out)[N])
 // outgoing sign of edge j is bit 31 of neg ^ bits(v_j) — one xor per edge in, one xor + one bit-field insert per edge out.
 // `sl` = BYTE offsets of the check's slots from `msg` (the packed rows of g.cslot16 hold 4 * slot); F1 = the normalisation factor is
 // exactly 1 (feedback_gnn.py / n882.py: every paper run), so the product with it — the identity on every float — is not issued.
-__device__ __forceinline__ float& slot_ref(float* msg, int byte_off)
-{
-    return *reinterpret_cast<float*>(reinterpret_cast<char*>(msg) + byte_off);
-}
 template <int DC, bool HWT = false, bool F1 = false>
 __device__ __forceinline__ bool cn_phi_regular(float* msg, const int (&sl)[DC], unsigned synd, float factor, float phi0,
                                                bool shortcut)
@@ -341,45 +242,9 @@ __device__ __forceinline__ bool cn_phi_regular(float* msg, const int (&sl)[DC], 
     return false;
 }
 
-// The min-sum and tanh rules on a check of compile-time degree DC: the DC messages are read once, every intermediate that cn_update
-// parks in the slots (|v| with the sign bit, tanh(v/2)) stays in registers, each slot is written once.  Same float operations in the
-// same order as cn_update<FGNN_CN_MINSUM> / <FGNN_CN_BOXPLUS>.
-template <int DC>
-__device__ __forceinline__ void cn_minsum_regular(float* msg, const int (&sl)[DC], unsigned synd, float factor)
-{
-    const float LARGE = 10000.0f;
-    float a[DC];
-    unsigned ng[DC];
-    unsigned neg = synd;
-    float minv = 0.0f;
-#pragma unroll
-    for (int j = 0; j < DC; ++j) {
-        const float v = FG_MIN(FG_MAX(slot_ref(msg, sl[j]), -20.0f), 20.0f);
-        ng[j] = v < 0.0f;
-        neg ^= ng[j];
-        a[j] = FG_ABS(v);
-        minv = (j == 0) ? a[j] : FG_MIN(minv, a[j]);
-    }
-    float min2 = 0.0f, nsum = 0.0f;
-#pragma unroll
-    for (int j = 0; j < DC; ++j) {
-        float d = a[j] - minv;
-        d = (d == 0.0f) ? LARGE : d;
-        min2 = (j == 0) ? d : FG_MIN(min2, d);
-        nsum = nsum + d;
-    }
-    min2 = min2 + minv;
-    nsum = nsum - (2.0f * LARGE - 1.0f);
-    const float sg = (nsum > 0.0f) ? 1.0f : ((nsum < 0.0f) ? -1.0f : 0.0f);
-    const float dm = 0.5f * (1.0f - sg);
-    const float min_e = (1.0f - dm) * minv + dm * min2;
-#pragma unroll
-    for (int j = 0; j < DC; ++j) {
-        const float out = ((a[j] - minv) == 0.0f) ? min_e : minv;
-        slot_ref(msg, sl[j]) = with_sign(out, neg ^ ng[j]) * factor;
-    }
-}
-
+// The tanh rule on a check of compile-time degree DC (the min-sum one is cn_minsum_regular of fgnn_cn.h): the DC messages are read
+// once, the tanh(v/2) that cn_update parks in the slots stay in registers, each slot is written once.  Same float operations in the
+// same order as cn_update<FGNN_CN_BOXPLUS>.
 template <int DC>
 __device__ __forceinline__ void cn_tanh_regular(float* msg, const int (&sl)[DC], unsigned synd, float factor)
 {
@@ -424,7 +289,7 @@ __device__ __forceinline__ bool cn_phi_generic(float* msg, const int* __restrict
             return true;
         }
     }
-    cn_update<FGNN_CN_BOXPLUS_PHI, HWT>(msg, slot, deg, synd, factor);
+    cn_update<FGNN_CN_BOXPLUS_PHI, Mx<HWT>>(msg, slot, deg, synd, factor);
     return false;
 }
 
@@ -593,12 +458,12 @@ bp4_kernel(GraphDev g, BpArgs a)
             float* tx = a.trace_x + ((size_t)k * a.B + b) * g.rows[0];
             for (int r = lane; r < g.rows[0]; r += a.tpc) {
                 const int p0 = g.rptr[0][r];
-                tx[r] = logit_row<HWT>(tlx, g.rcol[0] + p0, g.rptr[0][r + 1] - p0);
+                tx[r] = logit_row<Mx<HWT>>(tlx, g.rcol[0] + p0, g.rptr[0][r + 1] - p0);
             }
             float* tz = a.trace_z + ((size_t)k * a.B + b) * g.rows[1];
             for (int r = lane; r < g.rows[1]; r += a.tpc) {
                 const int p0 = g.rptr[1][r];
-                tz[r] = logit_row<HWT>(tlz, g.rcol[1] + p0, g.rptr[1][r + 1] - p0);
+                tz[r] = logit_row<Mx<HWT>>(tlz, g.rcol[1] + p0, g.rptr[1][r + 1] - p0);
             }
         }
         // the binary LLRs are next written one iteration (two barriers) later: no barrier needed here
@@ -798,7 +663,7 @@ bp4_kernel(GraphDev g, BpArgs a)
                         else fast = cn_phi_regular<DC, HWT, false>(msg, sl, synd, a.factor, phi0, opt_shortcut);
                         cn_slow = !fast || cn_slow;
                     } else if constexpr (CN_TYPE == FGNN_CN_MINSUM) {
-                        cn_minsum_regular<DC>(msg, sl, synd, a.factor);
+                        cn_minsum_regular<DC>(msg, sl, DC, synd, a.factor);
                     } else {
                         cn_tanh_regular<DC>(msg, sl, synd, a.factor);
                     }
@@ -806,7 +671,7 @@ bp4_kernel(GraphDev g, BpArgs a)
                     const int c0 = g.cptr[c], deg = g.cptr[c + 1] - c0;
                     if constexpr (CN_TYPE == FGNN_CN_BOXPLUS_PHI)
                         cn_slow = !cn_phi_generic<HWT>(msg, g.cslot + c0, deg, synd, a.factor, phi0, opt_shortcut) || cn_slow;
-                    else cn_update<CN_TYPE, HWT>(msg, g.cslot + c0, deg, synd, a.factor);
+                    else cn_update<CN_TYPE, Mx<HWT>>(msg, g.cslot + c0, deg, synd, a.factor);
                 }
             }
         }

@@ -25,6 +25,7 @@
 
 #include "fgnn_internal.h"
 #include "fgnn_math.h"
+#include "fgnn_mlp.h"
 #include "fgnn_pk.h"
 
 namespace {
@@ -144,10 +145,6 @@ enum {
     T_W10 = 132, // + side*10 + s         W1[0, 4s+q]: the check-feature row of layer 1 as a per-lane multiplier (factored order)
     T_COUNT = 152
 };
-
-typedef float f4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ f4 mfma4(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
 // CPB codewords per workgroup, four waves each: the 34 KB of operand tables are shared, so LDS no longer caps the CU at four
 // workgroups of four waves — with CPB = 4 two 16-wave workgroups fill all 8 wave slots of every SIMD.
@@ -607,29 +604,6 @@ gnn_stream_kernel(GraphDev g, WeightsDev w, GnnArgs a)
 // then (+ bias) then activation, exactly as the oracle (og_feedback_gnn_general).  Activations of one layer ping-pong between
 // two per-thread buffers (scratch memory: this is the compatibility path, not the benchmark path).
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ float gen_act(float a, int act)
-{
-    switch (act) {
-    case FGNN_ACT_TANH: return fg_tanh(a);
-    case FGNN_ACT_RELU: return FG_MAX(a, 0.0f);
-    case FGNN_ACT_SIGMOID: return fg_sigmoid(a);
-    default: return a;
-    }
-}
-
-__device__ __forceinline__ void gen_dense(const GnnGeneralDev& w, int li, const float* in, float* out)
-{
-    const int K = w.K[li], J = w.J[li], act = w.act_l[li];
-    const float* W = w.W[li];
-    const float* b = w.b[li];
-    for (int j = 0; j < J; ++j) {
-        float a = 0.0f;
-        for (int k = 0; k < K; ++k) a = FG_FMA(in[k], W[k * J + j], a);
-        if (b) a = a + b[j];
-        out[j] = gen_act(a, act);
-    }
-}
-
 __global__ void __launch_bounds__(1024) gnn_general_kernel(GraphDev g, GnnGeneralDev w, GnnArgs a)
 {
     extern __shared__ float lds[];
@@ -788,28 +762,28 @@ extern "C" int fgnn_weights_create(const float* const host_arrays[12], int devic
         float* T = &h[off_tab];
         auto put = [&](int entry, int lane, float val) { T[(size_t)entry * 64 + lane] = val; };
         for (int lane = 0; lane < 64; ++lane) {
-            const int rho = lane & 15, kk = lane >> 4, qp = rho >> 2, rp = rho & 3, qq = lane >> 4;
+            const int rho = lane & 15, kk = lane >> 4, qq = lane >> 4;
             for (int s2 = 0; s2 < 2; ++s2) {
                 const float* W1 = host_arrays[2 + 4 * s2];
                 const float* B1 = host_arrays[3 + 4 * s2];
                 const float* W2 = host_arrays[4 + 4 * s2];
                 const float* B2 = host_arrays[5 + 4 * s2];
                 for (int t = 0; t < 3; ++t) {
-                    const int unit = 16 * t + 4 * rp + qp;
+                    const int unit = mfma_unit(lane, t);
                     put(T_W1 + s2 * 3 + t, lane, unit < HID ? W1[kk * HID + unit] : 0.0f);
                 }
                 for (int s = 0; s < 10; ++s) put(T_B1 + s2 * 10 + s, lane, B1[4 * s + qq]);
                 for (int u = 0; u < 2; ++u)
                     for (int s = 0; s < 10; ++s) {
-                        const int mu = (u == 0) ? 4 * rp + qp : (rp == 0 ? 16 + qp : -1);
+                        const int mu = mfma_w2_col(lane, u);
                         put(T_W2 + (s2 * 2 + u) * 10 + s, lane, mu >= 0 ? W2[(4 * s + kk) * MSG + mu] : 0.0f);
                     }
-                for (int i = 0; i < 5; ++i) put(T_B2 + s2 * 5 + i, lane, B2[i < 4 ? 4 * i + qq : 16 + qq]);
+                for (int i = 0; i < 5; ++i) put(T_B2 + s2 * 5 + i, lane, B2[mfma_b2_row(lane, i)]);
                 for (int s = 0; s < 10; ++s) put(T_W10 + s2 * 10 + s, lane, W1[0 * HID + 4 * s + qq]);
             }
             for (int t = 0; t < 3; ++t)
                 for (int s = 0; s < 11; ++s) {
-                    const int unit = 16 * t + 4 * rp + qp, k = 4 * s + kk;
+                    const int unit = mfma_unit(lane, t), k = 4 * s + kk;
                     put(T_WE + t * 11 + s, lane, (unit < HID && k < 43) ? host_arrays[10][k * HID + unit] : 0.0f);
                 }
             for (int s = 0; s < 10; ++s) {
@@ -822,14 +796,7 @@ extern "C" int fgnn_weights_create(const float* const host_arrays[12], int devic
 
     fgnn_weights* w = new fgnn_weights();
     w->device = device;
-    w->blob = nullptr;
-    hipError_t e = hipMalloc(&w->blob, h.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(w->blob, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        if (w->blob) (void)hipFree(w->blob);
-        delete w;
-        return fgnn_fail(FGNN_ERR_HIP, std::string("weights upload: ") + hipGetErrorString(e));
-    }
+    if (int rc = fgnn_weights_upload(w, h, "weights upload: ")) return rc;
     const float* base = static_cast<const float*>(w->blob);
     for (int s = 0; s < 2; ++s) {
         w->d.w1t[s] = base + off[4 * s + 0];
@@ -866,7 +833,6 @@ extern "C" int fgnn_weights_create_general(const fgnn_gnn_config* cfg, const flo
     FGNN_DEVICE_GUARD(device);
     fgnn_weights* w = new fgnn_weights();
     w->device = device;
-    w->blob = nullptr;
     w->general = true;
     std::memset(&w->d, 0, sizeof(w->d));
     GnnGeneralDev& G = w->gen;
@@ -905,13 +871,7 @@ extern "C" int fgnn_weights_create_general(const fgnn_gnn_config* cfg, const flo
             h.resize((h.size() + 3) & ~size_t(3), 0.0f);
         }
     }
-    hipError_t e = hipMalloc(&w->blob, h.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(w->blob, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        if (w->blob) (void)hipFree(w->blob);
-        delete w;
-        return fgnn_fail(FGNN_ERR_HIP, std::string("weights upload: ") + hipGetErrorString(e));
-    }
+    if (int rc = fgnn_weights_upload(w, h, "weights upload: ")) return rc;
     const float* base = static_cast<const float*>(w->blob);
     for (int li = 0; li < G.nl; ++li) {
         G.W[li] = base + offW[li];
@@ -923,10 +883,7 @@ extern "C" int fgnn_weights_create_general(const fgnn_gnn_config* cfg, const flo
 
 extern "C" void fgnn_weights_destroy(fgnn_weights* w)
 {
-    if (!w) return;
-    fgnn_device_guard _dg(w->device);
-    if (w->blob) (void)hipFree(w->blob);
-    delete w;
+    fgnn_weights_free(w);
 }
 
 int fgnn_feedback_gnn_impl(const fgnn_graph* g, const fgnn_weights* w, const float* llr, const float* logit_hx,

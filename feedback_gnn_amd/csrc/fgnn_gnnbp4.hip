@@ -18,6 +18,7 @@
 
 #include "fgnn_internal.h"
 #include "fgnn_math.h"
+#include "fgnn_mlp.h"
 #include "fgnn_pk.h"
 
 namespace {
@@ -101,6 +102,8 @@ __device__ __forceinline__ void msg_mean_factored(const float (&own)[D], int deg
     }
 }
 
+// logit_row<PhiGnn> of fgnn_cn.h, the same values; its sign goes on as a negation rather than a sign-bit xor, and the two forms
+// schedule differently in the kernels around them, so each kernel keeps the one it was tuned with.
 __device__ __forceinline__ float logit_row_gnn(const float* llr, const int* __restrict__ col, int deg)
 {
     unsigned neg = 0;
@@ -120,8 +123,6 @@ __device__ __forceinline__ float logit_row_gnn(const float* llr, const int* __re
 // the next layer's B operand; weight rows are permuted at upload so that k-step s finds units 4s..4s+3 on lane
 // groups 0..3.  A wave owns a tile of 16 receiving nodes.  Per MLP the table holds, in this order:
 //   W1 [3 row tiles][S1 k-steps] | B1 [10] | W2 [2 row tiles][10 k-steps] | B2 [5]
-typedef float f4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ f4 mfma4(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
 template <int S1>
 __device__ __forceinline__ void mlp_tile(const float* __restrict__ lane_tab, int first, const float (&Bin)[S1], float (&out)[5])
@@ -937,16 +938,8 @@ struct GnnBp4GenDev {
     const float* vn_msga[2];  // [E_s][Am], permuted to the VN-major slot order at upload
 };
 
-__device__ __forceinline__ float gg_act(float a, int act)
-{
-    switch (act) {
-    case FGNN_ACT_TANH: return fg_tanh(a);
-    case FGNN_ACT_RELU: return FG_MAX(a, 0.0f);
-    case FGNN_ACT_SIGMOID: return fg_sigmoid(a);
-    default: return a;
-    }
-}
-
+// the layers of MLP q in turn; each is gen_dense of fgnn_mlp.h on this kernel's weight layout, written out in place (a call to a
+// shared Dense function compiles this kernel's branches differently)
 __device__ __forceinline__ void gg_run(const GnnBp4GenDev& w, int q, const float* in, float* out, float* bufA, float* bufB)
 {
     const float* cur = in;
@@ -959,7 +952,7 @@ __device__ __forceinline__ void gg_run(const GnnBp4GenDev& w, int q, const float
             float a = 0.0f;
             for (int kk = 0; kk < K; ++kk) a = FG_FMA(cur[kk], W[kk * J + j], a);
             if (bb) a = a + bb[j];
-            nxt[j] = gg_act(a, act);
+            nxt[j] = mlp_act(a, act);
         }
         cur = nxt;
     }
@@ -1162,7 +1155,7 @@ extern "C" int fgnn_gnnbp4_weights_create(const float* const host_arrays[30], in
             for (int st = 0; st < S1; ++st) {
                 size_t e = entry();
                 for (int lane = 0; lane < 64; ++lane) {
-                    const int rho = lane & 15, kk = lane >> 4, unit = 16 * t + 4 * (rho & 3) + (rho >> 2), k = 4 * st + kk;
+                    const int unit = mfma_unit(lane, t), k = 4 * st + (lane >> 4);
                     T[e * 64 + lane] = (unit < H && k < nin[qm]) ? a[0][(size_t)k * H + unit] : 0.0f;
                 }
             }
@@ -1174,14 +1167,13 @@ extern "C" int fgnn_gnnbp4_weights_create(const float* const host_arrays[30], in
             for (int st = 0; st < 10; ++st) {
                 size_t e = entry();
                 for (int lane = 0; lane < 64; ++lane) {
-                    const int rho = lane & 15, kk = lane >> 4, rp = rho & 3, qp = rho >> 2;
-                    const int mu = (u == 0) ? 4 * rp + qp : (rp == 0 ? 16 + qp : -1);
-                    T[e * 64 + lane] = mu >= 0 ? a[2][(size_t)(4 * st + kk) * D + mu] : 0.0f;
+                    const int mu = mfma_w2_col(lane, u);
+                    T[e * 64 + lane] = mu >= 0 ? a[2][(size_t)(4 * st + (lane >> 4)) * D + mu] : 0.0f;
                 }
             }
         for (int i = 0; i < 5; ++i) {
             size_t e = entry();
-            for (int lane = 0; lane < 64; ++lane) T[e * 64 + lane] = a[3][i < 4 ? 4 * i + (lane >> 4) : 16 + (lane >> 4)];
+            for (int lane = 0; lane < 64; ++lane) T[e * 64 + lane] = a[3][mfma_b2_row(lane, i)];
         }
     }
     tab_inv = (int)(T.size() / 64);
@@ -1201,14 +1193,7 @@ extern "C" int fgnn_gnnbp4_weights_create(const float* const host_arrays[30], in
 
     fgnn_gnnbp4_weights* w = new fgnn_gnnbp4_weights();
     w->device = device;
-    w->blob = nullptr;
-    hipError_t e = hipMalloc(&w->blob, h.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(w->blob, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        if (w->blob) (void)hipFree(w->blob);
-        delete w;
-        return fgnn_fail(FGNN_ERR_HIP, std::string("GNN_BP4 weights upload: ") + hipGetErrorString(e));
-    }
+    if (int rc = fgnn_weights_upload(w, h, "GNN_BP4 weights upload: ")) return rc;
     const float* base = static_cast<const float*>(w->blob);
     MlpDev* dst[7] = {&w->d.cn_msg[0], &w->d.cn_msg[1], &w->d.cn_embed[0], &w->d.cn_embed[1], &w->d.vn_msg[0], &w->d.vn_msg[1],
                       &w->d.vn_embed};
@@ -1254,7 +1239,6 @@ extern "C" int fgnn_gnnbp4_weights_create_general(const fgnn_graph* g, const fgn
     const int nin[7] = {2 * Dg + Am, 2 * Dg + Am, 2 * Dg + An + 1, 2 * Dg + An + 1, 2 * Dg + Am, 2 * Dg + Am, 3 * Dg + An};
     fgnn_gnnbp4_weights* w = new fgnn_gnnbp4_weights();
     w->device = g->device;
-    w->blob = nullptr;
     w->general = true;
     std::memset(&w->d, 0, sizeof(w->d));
     GnnBp4GenDev& G = w->gen;
@@ -1302,13 +1286,7 @@ extern "C" int fgnn_gnnbp4_weights_create_general(const fgnn_graph* g, const fgn
         }
     }
     if (h.empty()) h.resize(4, 0.0f);
-    hipError_t e = hipMalloc(&w->blob, h.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(w->blob, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        if (w->blob) (void)hipFree(w->blob);
-        delete w;
-        return fgnn_fail(FGNN_ERR_HIP, std::string("GNN_BP4 weights upload: ") + hipGetErrorString(e));
-    }
+    if (int rc = fgnn_weights_upload(w, h, "GNN_BP4 weights upload: ")) return rc;
     const float* base = static_cast<const float*>(w->blob);
     for (int q = 0; q < 7; ++q)
         for (int k = 0; k < L; ++k) {
@@ -1335,10 +1313,7 @@ extern "C" size_t fgnn_gnnbp4_weights_workspace_bytes(const fgnn_graph* g, const
 
 extern "C" void fgnn_gnnbp4_weights_destroy(fgnn_gnnbp4_weights* w)
 {
-    if (!w) return;
-    fgnn_device_guard _dg(w->device);
-    if (w->blob) (void)hipFree(w->blob);
-    delete w;
+    fgnn_weights_free(w);
 }
 
 extern "C" size_t fgnn_gnnbp4_workspace_bytes(const fgnn_graph* g, int B)

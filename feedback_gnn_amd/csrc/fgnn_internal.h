@@ -132,6 +132,32 @@ struct fgnn_device_guard {
     if (_dev_guard.err != hipSuccess)                                                                 \
         return fgnn_fail(FGNN_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(_dev_guard.err))
 
+// Weight handles (fgnn_weights, fgnn_gnnbp4_weights) own one device blob of floats.  Upload `h` to w->blob on the current device;
+// on failure free what was allocated, delete w and report `what` followed by the HIP error.
+template <typename W>
+int fgnn_weights_upload(W* w, const std::vector<float>& h, const char* what)
+{
+    w->blob = nullptr;
+    hipError_t e = hipMalloc(&w->blob, h.size() * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy(w->blob, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        if (w->blob) (void)hipFree(w->blob);
+        delete w;
+        return fgnn_fail(FGNN_ERR_HIP, std::string(what) + hipGetErrorString(e));
+    }
+    return FGNN_OK;
+}
+
+// the body of the weight handles' destroy functions: free the blob on the handle's device, delete the handle
+template <typename W>
+void fgnn_weights_free(W* w)
+{
+    if (!w) return;
+    fgnn_device_guard _dg(w->device);
+    if (w->blob) (void)hipFree(w->blob);
+    delete w;
+}
+
 // Optional per-launch timing (fgnn_profile_*): HIP events on the launch stream around one kernel launch.  `tag` is what
 // fgnn_profile_read reports as `iters`: the BP4 iteration count, FGNN_PROF_TAG_GNN for a feedback-GNN launch, FGNN_PROF_TAG_GNNBP4
 // for a GNN_BP4 launch.
