@@ -308,7 +308,7 @@ __device__ __forceinline__ float softplus_saturated(float t)
 // NQ > 0: per-qubit channel LLRs (llr_ch != null: every decoder of a sandwich but the first) live in REGISTERS, 3 x NQ per thread
 // for the at most NQ qubits lane, lane + tpc, ... a thread owns, instead of 3n floats of LDS: the workgroup then needs the message
 // area only and 7 instead of 4 ([[882,24]]) / 5 instead of 3 ([[1270,28]]) workgroups share a CU; the register budget is that of
-// 6 waves per SIMD.  The launch picks NQ = ceil(n / tpc) when that is 4 or 5.
+// 6 waves per SIMD.  The launch picks NQ = 4 when a thread owns at most 4 qubits (ceil(n / tpc) <= 4) and NQ = 5 when it owns 5.
 // TRACE: the `trainable` / `stage_two` return mode of the reference (decoding_q.py:743-746, 779-781): the soft syndromes of the
 // marginals are recorded after EVERY iteration (and before the first) by the kernel itself, from 2n binary LLRs in their own LDS
 // area — one launch instead of num_iter + 1 chained one-iteration launches with the messages going through HBM in between.  Same

@@ -431,3 +431,109 @@ def bp2_decode(hx, synd, num_iter, cn_type, factor, llr_ch=None, llr_const=None)
         msg = _bp2_cn(cn_type, msg_vn, seg, starts, syndrome) * fac  # (:988-991)
     x_hat = -1.0 * (llr + vn_sum(msg))
     return np.ascontiguousarray(x_hat.T), np.ascontiguousarray((0.0 < x_hat).T.astype(np.uint8))
+
+
+# ---- BP4: QLDPCBPDecoder.call (sionna/fec/ldpc/decoding_q.py:661-797), float64 ----
+# Line-by-line reading of decoding.py against decoding_q.py: _cn_update_tanh (decoding.py:573-623 / decoding_q.py:313-363) and
+# _cn_update_minsum (:744-850 / :539-644) state the same operations with the same constants (_atanh_clip_value = 1 - 1e-7, _llr_max = 20,
+# LARGE_VAL = 10000, the 1e-12 / 1e-7 substitutions); they differ only in decoding.py's `syndrome=None` default, and QLDPCBPDecoder always
+# passes the syndrome.  So those two rules reuse _bp2_cn.  _phi differs: decoding_q.py:373 returns softplus(x) - log(exp(x) - 1),
+# decoding.py:633 log(exp(x) + 1) - log(exp(x) - 1) — the same real function, restated below in its own form.
+def _bp4_phi(x):
+    """_phi (decoding_q.py:365-373): softplus(x) - log(exp(x) - 1) after the clip."""
+    x = np.clip(x, _PHI_LO, _PHI_HI)
+    return np.logaddexp(0.0, x) - np.log(np.expm1(x))
+
+
+def _bp4_cn(rule, msg, seg, starts, syndrome):
+    """One check-node update of QLDPCBPDecoder on check-major messages [E,B] (the arguments of _bp2_cn)."""
+    if rule != "boxplus-phi":
+        return _bp2_cn(rule, msg, seg, starts, syndrome)
+    # _cn_update_phi (:376-431)
+    sign_val = _bp2_sign(msg)
+    sign_node = np.multiply.reduceat(sign_val, starts, axis=0) * syndrome
+    sign_val = sign_val * sign_node[seg]
+    a = _bp4_phi(np.abs(msg))
+    msg_sum = np.add.reduceat(a, starts, axis=0)
+    return sign_val * _bp4_phi(-1.0 * a + msg_sum[seg])
+
+
+def _bp4_side(pcm):
+    """Edges of one Tanner graph: VN-major (by qubit, then check: the slot order of the library and the oracle) and the check-major
+    permutation with its segments over the non-empty checks."""
+    chk, var = np.nonzero(np.asarray(pcm))
+    o = np.lexsort((chk, var))
+    chk, var = chk[o], var[o]
+    to_cn = np.lexsort((var, chk))
+    c = chk[to_cn]
+    first = np.r_[True, c[1:] != c[:-1]] if c.size else np.zeros(0, bool)
+    starts = np.flatnonzero(first)
+    return dict(var=var, to_cn=to_cn, inv=np.argsort(to_cn), starts=starts, seg=np.cumsum(first) - 1, cn_chk=c[starts])
+
+
+def _bp4_soft_syndrome(rows, llr):
+    """_cn_update_phi_loss (:433-453) over the rows of `rows` [r,n] on binary LLRs [n,B]: the sign product (0 -> +1) times
+    phi(sum of phi(|llr|)); an empty row gives phi(0)."""
+    rows = np.asarray(rows)
+    r, c = np.nonzero(rows)
+    v = llr[c]
+    neg = np.zeros((rows.shape[0], llr.shape[1]))
+    np.add.at(neg, r, (v < 0).astype(np.float64))
+    T = np.zeros_like(neg)
+    np.add.at(T, r, _bp4_phi(np.abs(v)))
+    return (1.0 - 2.0 * (neg % 2)) * _bp4_phi(T)
+
+
+def bp4_decode64(code, synd_x, synd_z, num_iter, cn_type="boxplus-phi", factor=1.0, llr_ch=None, llr_const=None, msg_init=None,
+                 stage_one=True):
+    """QLDPCBPDecoder.call (decoding_q.py:661-797) in float64 with the reference's batch-minor edge tensors.  synd_x [B,m_x] / synd_z
+    [B,m_z]; llr_ch [B,3,n] (x, y, z planes) or llr_const for every qubit and plane; msg_init = (msg_x [B,E_x], msg_z [B,E_z]): the c->v
+    messages to start from, VN-major (the reference starts from zeros, :726-727).  The soft syndromes are over hz / hx (stage_one,
+    :35-37) or hx_perp / hz_perp.  Returns dict(llr [B,3,n], x_hat, z_hat [B,n], x_logit, z_logit [B,rows], msg_x [B,E_x], msg_z
+    [B,E_z], llr_x, llr_z [B,n]: the binary LLRs the soft syndromes are formed from), the soft outputs in float64."""
+    hx, hz = np.asarray(code.hx), np.asarray(code.hz)
+    sx, sz = np.asarray(synd_x), np.asarray(synd_z)
+    B, n = sx.shape[0], hx.shape[1]
+    sides = [_bp4_side(hx), _bp4_side(hz)]
+    syndrome = [((-1.0) ** s.T.astype(_D))[d["cn_chk"]] for s, d in zip((sx, sz), sides)]  # 0 -> +1, 1 -> -1 (:720-721)
+    if llr_ch is None:
+        L = np.full((3, n, B), _D(F(llr_const)))
+    else:  # [3,n,B] (:716); the input clip of :705-708 is commented out in the reference
+        L = np.transpose(np.asarray(llr_ch, F), (1, 2, 0)).astype(_D)
+    fac = _D(F(factor))
+    if msg_init is None:
+        msg = [np.zeros((d["var"].size, B)) for d in sides]
+    else:
+        msg = [np.asarray(m, F).T.astype(_D) for m in msg_init]
+
+    def vn_sum(m, var):
+        idx = (var[:, None] * B + np.arange(B)[None, :]).ravel()
+        return np.bincount(idx, weights=m.ravel(), minlength=n * B).reshape(n, B)
+
+    def totals():  # (:244-248): X = sum of hz messages + llr_x, Z = sum of hx messages + llr_z, Y = both + llr_y
+        Sz, Sx = vn_sum(msg[1], sides[1]["var"]), vn_sum(msg[0], sides[0]["var"])
+        return Sz + L[0], (Sz + Sx) + L[1], Sx + L[2]
+
+    def softplus(t):
+        return np.logaddexp(0.0, t)
+
+    for _ in range(num_iter):
+        X, Y, Z = totals()
+        vx, vz = sides[0]["var"], sides[1]["var"]
+        # _vn_update (:250-273): an hx edge sends softplus(-X) - logsumexp(-(Z - mu), -(Y - mu)), an hz edge softplus(-Z) -
+        # logsumexp(-(X - mu), -(Y - mu)), mu = the edge's own incoming c->v message
+        nu = [softplus(-X)[vx] - np.logaddexp(-(Z[vx] - msg[0]), -(Y[vx] - msg[0])),
+              softplus(-Z)[vz] - np.logaddexp(-(X[vz] - msg[1]), -(Y[vz] - msg[1]))]
+        for s, d in enumerate(sides):  # CN-order gather, check rule, normalization, gather back (:752-767)
+            msg[s] = (_bp4_cn(cn_type, nu[s][d["to_cn"]], d["seg"], d["starts"], syndrome[s]) * fac)[d["inv"]]
+    X, Y, Z = totals()  # the sum_only pass (:777)
+    dec = np.argmin(np.stack([np.zeros_like(X), X, Z, Y], 0), axis=0)  # (:783-790), the first minimum wins
+    llr_z = softplus(-X) - np.logaddexp(-Z, -Y)  # cal_logit (:455-464)
+    llr_x = softplus(-Z) - np.logaddexp(-X, -Y)
+    xp, zp = (hz, hx) if stage_one else (code.hx_perp, code.hz_perp)
+    return dict(llr=np.ascontiguousarray(np.stack([X, Y, Z], 0).transpose(2, 0, 1)),
+                x_hat=(dec & 1).T.astype(np.uint8), z_hat=(dec >> 1).T.astype(np.uint8),
+                x_logit=np.ascontiguousarray(_bp4_soft_syndrome(xp, llr_x).T),
+                z_logit=np.ascontiguousarray(_bp4_soft_syndrome(zp, llr_z).T),
+                msg_x=np.ascontiguousarray(msg[0].T), msg_z=np.ascontiguousarray(msg[1].T),
+                llr_x=np.ascontiguousarray(llr_x.T), llr_z=np.ascontiguousarray(llr_z.T))
