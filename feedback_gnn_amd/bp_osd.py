@@ -10,6 +10,36 @@ import torch
 from ._lib import ROWS_LX, ROWS_LZ
 from .feedback_gnn import Pauli
 
+_SEARCH = "osd_cs"  # fgnn_osd_resident of a search method asks whether fgnn_osd (the kernel every osd() call runs) takes the basis
+
+
+class _OsdWorkspace:
+    """The device workspace of the OSD path beyond LDS (`fgnn_osd_ws`), taken only for a basis the LDS-resident kernels refuse: one
+    tensor per owner, grown on demand (the default slot count of the largest request so far)."""
+
+    def __init__(self):
+        self.buf = None
+
+    def get(self, g, side, method, order):
+        self.buf = g.osd_workspace(side, method, order, out=self.buf)
+        return self.buf
+
+
+def _run_osd0(g, ws, side, synd, e_hat, **kw):
+    """OSD-0 of side `side`: `fgnn_osd0` where it takes the basis, else `fgnn_osd_ws` on the owner's workspace."""
+    if g.osd_resident(side, "osd0"):
+        g.osd0(side, synd, e_hat, **kw)
+    else:
+        g.osd_ws(side, synd, e_hat, "osd0", 0, workspace=ws.get(g, side, "osd0", 0), **kw)
+
+
+def _run_osd(g, ws, side, synd, e_hat, method, order, **kw):
+    """OSD-E / OSD-CS of side `side`: `fgnn_osd` where it takes the basis, else `fgnn_osd_ws` on the owner's workspace."""
+    if g.osd_resident(side, _SEARCH):
+        g.osd(side, synd, e_hat, method, order, **kw)
+    else:
+        g.osd_ws(side, synd, e_hat, method, order, workspace=ws.get(g, side, method, order), **kw)
+
 
 class _StandaloneOSD:
     """The reference's standalone ``decoder(llr, pcm, s, bs)`` call (bp_osd.py:47-77) over one device graph per row basis; the
@@ -24,6 +54,7 @@ class _StandaloneOSD:
         self._seen = {}       # identity of a pcm tensor already resolved (storage pointer, shape, strides, version) -> its graph
         self._seen_refs = {}  # same keys -> weak reference to that tensor: a hit needs the very same live tensor (a freed one's
         #                       storage may come back from the allocator for a different matrix with an identical key)
+        self._ws = _OsdWorkspace()  # used only for a basis the LDS-resident kernels refuse
 
     def _graph_of(self, basis):
         from .decoding import _binary_graph
@@ -105,10 +136,10 @@ class _StandaloneOSD:
 class OSD0_Decoder(_StandaloneOSD):
     """Order-0 ordered-statistics decoder (bp_osd.py:8-77).  Inside `BP4_OSD_Model` / `BP2_OSD_Model` the row basis lives in the
     model's device graph (`fgnn_graph_set_basis`) and only the BP failures are re-solved; the reference's standalone
-    ``decoder(llr, pcm, s, bs)`` is served by `__call__` through the same HIP kernel (`fgnn_osd0`)."""
+    ``decoder(llr, pcm, s, bs)`` is served by `__call__` through the same HIP kernel (`fgnn_osd0`; `fgnn_osd_ws` for a basis beyond LDS)."""
 
     def _solve(self, g, synd, e_hat, llr):
-        g.osd0(0, synd, e_hat, llr_bin=llr)
+        _run_osd0(g, self._ws, 0, synd, e_hat, llr_bin=llr)
 
 
 class OSD_Decoder(_StandaloneOSD):
@@ -127,7 +158,7 @@ class OSD_Decoder(_StandaloneOSD):
             raise ValueError(f"osd_order must be in 0..{limit} for {self.osd_method}")
 
     def _solve(self, g, synd, e_hat, llr):
-        g.osd(0, synd, e_hat, self.method_id, self.osd_order, llr_bin=llr)
+        _run_osd(g, self._ws, 0, synd, e_hat, self.method_id, self.osd_order, llr_bin=llr)
 
 
 def _search_of(osd_decoder):
@@ -159,6 +190,7 @@ class BP4_OSD_Model:
         self.rank, self.world_size, self._next = int(rank), int(world_size), 0
         self.last_num_osd = 0
         self.last_osd_improved = 0  # processed samples whose OSD winner is not the OSD-0 solution (OSD_Decoder only)
+        self._ws = _OsdWorkspace()  # used only for a basis the LDS-resident kernels refuse
 
     def decode(self, batch_size, p):
         B, g, d = int(batch_size), self.graph, self.bp4_decoder
@@ -177,12 +209,12 @@ class BP4_OSD_Model:
         search = _search_of(self.osd_decoder)
         if nact and search is not None:
             cz, cx = torch.zeros((2, B), dtype=torch.int32, device=g.device)
-            g.osd(0, sx, z_hat, *search, marg=out["llr"], index=index, nact=nact, chosen=cz)
-            g.osd(1, sz, x_hat, *search, marg=out["llr"], index=index, nact=nact, chosen=cx)
+            _run_osd(g, self._ws, 0, sx, z_hat, *search, marg=out["llr"], index=index, nact=nact, chosen=cz)
+            _run_osd(g, self._ws, 1, sz, x_hat, *search, marg=out["llr"], index=index, nact=nact, chosen=cx)
             self.last_osd_improved = _improved([cz, cx])
         elif nact:
-            g.osd0(0, sx, z_hat, marg=out["llr"], index=index, nact=nact)  # z_hat_osd from hx, osd_llrz (:155)
-            g.osd0(1, sz, x_hat, marg=out["llr"], index=index, nact=nact)  # x_hat_osd from hz, osd_llrx (:156)
+            _run_osd0(g, self._ws, 0, sx, z_hat, marg=out["llr"], index=index, nact=nact)  # z_hat_osd from hx, osd_llrz (:155)
+            _run_osd0(g, self._ws, 1, sz, x_hat, marg=out["llr"], index=index, nact=nact)  # x_hat_osd from hz, osd_llrx (:156)
         return dict(noise_x=ex, noise_z=ez, x_hat=x_hat, z_hat=z_hat)
 
     def __call__(self, batch_size, ebno_db=None, **kw):
@@ -206,6 +238,7 @@ class BP2_OSD_Model:
         self.seed, self.rank, self.world_size, self._next = int(seed), int(rank), int(world_size), 0
         self.last_num_osd = 0
         self.last_osd_improved = 0  # processed samples whose OSD winner is not the OSD-0 solution (OSD_Decoder only)
+        self._ws = _OsdWorkspace()  # used only for a basis the LDS-resident kernels refuse
 
     def __call__(self, batch_size, ebno_db=None, **kw):
         p = float(kw.get("p", ebno_db))
@@ -225,10 +258,10 @@ class BP2_OSD_Model:
         search = _search_of(self.osd_decoder)
         if nact and search is not None:
             chosen = torch.zeros(B, dtype=torch.int32, device=g.device)
-            g.osd(0, synd, noise_hat, *search, llr_bin=(-soft).contiguous(), index=index, nact=nact, chosen=chosen)
+            _run_osd(g, self._ws, 0, synd, noise_hat, *search, llr_bin=(-soft).contiguous(), index=index, nact=nact, chosen=chosen)
             self.last_osd_improved = _improved([chosen])
         elif nact:
-            g.osd0(0, synd, noise_hat, llr_bin=(-soft).contiguous(), index=index, nact=nact)  # llr_hat = -decoder output (:225)
+            _run_osd0(g, self._ws, 0, synd, noise_hat, llr_bin=(-soft).contiguous(), index=index, nact=nact)  # llr_hat = -decoder output (:225)
         _, ls_hat, _ = g.residual(noise, zeros, noise_hat, zeros, want_arrays=True)
         ls_hat = ls_hat[:, :g.rows_hxp].contiguous()
         return torch.zeros_like(ls_hat), ls_hat

@@ -673,6 +673,61 @@ class TannerGraph:
                                   int(nact), _ptr(e_hat), _ptr(chosen), _stream(self.device)))
         return e_hat
 
+    # ---- OSD beyond LDS (fgnn_osd_ws) ------------------------------------------------------------------------------
+    # default slot count: slots x slot bytes within this cap, clamped to [1, 2 x CUs].  The elimination is bound by the latency of its
+    # row steps, not by bytes (57 MB moved per [[6480,1296]] sample): more concurrent samples win over a cache-sized working set
+    # (profiles/osd_large.json: 64 slots 195 ms, 128 or more 111 ms for 100 failures)
+    OSD_WS_CACHE_BYTES = 1 << 30
+
+    def osd_resident(self, side, method="osd0"):
+        """True iff the LDS-resident kernels take this side's basis: `osd0` for method "osd0", `osd` for "osd_e" / "osd_cs"."""
+        fits = C.c_int()
+        check(_lib.lib().fgnn_osd_resident(self.handle, int(side), osd_method_id(method), C.byref(fits)))
+        return bool(fits.value)
+
+    def osd_slot_bytes(self, side, method="osd0", order=0):
+        nbytes = C.c_size_t()
+        check(_lib.lib().fgnn_osd_workspace_bytes(self.handle, int(side), osd_method_id(method), int(order), 1, C.byref(nbytes)))
+        return int(nbytes.value)
+
+    def osd_default_slots(self, side, method="osd0", order=0):
+        """Slots whose slot bytes fit OSD_WS_CACHE_BYTES together, clamped to [1, 2 x CUs]."""
+        cus = torch.cuda.get_device_properties(self.device).multi_processor_count
+        return max(1, min(2 * cus, self.OSD_WS_CACHE_BYTES // self.osd_slot_bytes(side, method, order)))
+
+    def osd_workspace(self, side, method="osd0", order=0, slots=None, out=None):
+        """A uint8 device workspace for `osd_ws` with `slots` slots (None: `osd_default_slots`).  `out` (optional) is returned
+        instead when it is at least that large."""
+        if slots is None:
+            slots = self.osd_default_slots(side, method, order)
+        nbytes = C.c_size_t()
+        check(_lib.lib().fgnn_osd_workspace_bytes(self.handle, int(side), osd_method_id(method), int(order), int(slots), C.byref(nbytes)))
+        if out is not None and out.numel() >= nbytes.value:
+            return out
+        return torch.empty(int(nbytes.value), dtype=torch.uint8, device=self.device)
+
+    def osd_ws(self, side, synd, e_hat, method, order, marg=None, llr_bin=None, index=None, nact=0, chosen=None, workspace=None):
+        """`osd` (method "osd0": `osd0`) on a device workspace (`fgnn_osd_ws`): any basis with n <= 16384, the same outputs bit for
+        bit.  `workspace` (uint8, from `osd_workspace`) sets the slot count; None allocates one with the default slot count."""
+        method = osd_method_id(method)
+        B = int(synd.shape[0])
+        synd = self._chk(synd, (B, self.m_x if side == 0 else self.m_z), torch.uint8, "synd")
+        e_hat = self._chk_out(e_hat, (B, self.n), torch.uint8, "e_hat")
+        if marg is not None:
+            marg = self._chk(marg, tuple(marg.shape), torch.float32, "marg")
+        if llr_bin is not None:
+            llr_bin = self._chk(llr_bin, tuple(llr_bin.shape), torch.float32, "llr_bin")
+        if index is not None:
+            index = self._chk(index, tuple(index.shape), torch.int32, "index")
+        if chosen is not None:
+            chosen = self._chk_out(chosen, (B,), torch.int32, "chosen")
+        if workspace is None:
+            workspace = self.osd_workspace(side, method, order)
+        workspace = self._chk_out(workspace, (workspace.numel(),), torch.uint8, "workspace")
+        check(_lib.lib().fgnn_osd_ws(self.handle, int(side), method, int(order), _ptr(marg), _ptr(llr_bin), _ptr(synd), B, _ptr(index),
+                                     int(nact), _ptr(e_hat), _ptr(chosen), _ptr(workspace), workspace.numel(), _stream(self.device)))
+        return e_hat
+
     def residual_rows(self, rows_x, rows_z, ex, ez, x_hat, z_hat):
         B = int(ex.shape[0])
         ex = self._chk(ex, (B, self.n), torch.uint8, "noise_x")

@@ -304,6 +304,21 @@ int fgnn_osd0(const fgnn_graph* g, int side, const float* marg, const float* llr
 enum { FGNN_OSD_0 = 0, FGNN_OSD_E = 1, FGNN_OSD_CS = 2 };
 int fgnn_osd(const fgnn_graph* g, int side, int method, int order, const float* marg, const float* llr_bin, const uint8_t* synd, int B,
              const int32_t* index, int nact, uint8_t* e_hat, int32_t* chosen, void* stream);
+/* OSD for codes whose basis does not fit in LDS: the same inputs, candidate list, cost, tie rule and outputs as fgnn_osd (method
+ * FGNN_OSD_0: the outputs of fgnn_osd0, plus chosen[b] = 0), bit for bit, at any shape with n <= 16384 (larger n: FGNN_ERR_ARG).
+ * fgnn_osd_resident sets *fits = 1 iff the LDS-resident kernels accept this graph's side-`side` basis — fgnn_osd0 for FGNN_OSD_0,
+ * fgnn_osd for FGNN_OSD_E / FGNN_OSD_CS (the same predicate those calls refuse by).  fgnn_osd_workspace_bytes = slots times the bytes
+ * of one slot (the bit-packed augmented matrix rank x (n+1) plus the per-position tables; the order only needs to be valid).
+ * fgnn_osd_ws runs on a caller-owned device workspace of workspace_bytes (8-byte aligned): it holds workspace_bytes / slot bytes slots,
+ * and min(slots, samples) persistent workgroups each walk the sample list in one slot, so the workspace bounds the parallelism, not
+ * the batch.  It does not allocate and does not synchronise.  Accepts every shape fgnn_osd0 / fgnn_osd accept too.  A bad method or
+ * order, a NULL or misaligned workspace, a missing basis, a NULL buffer or a workspace smaller than one slot are refused before
+ * anything is written or launched.  The workspace is scratch: nothing past workspace_bytes is touched. */
+int fgnn_osd_resident(const fgnn_graph* g, int side, int method, int* fits);
+int fgnn_osd_workspace_bytes(const fgnn_graph* g, int side, int method, int order, int slots, size_t* bytes);
+int fgnn_osd_ws(const fgnn_graph* g, int side, int method, int order, const float* marg, const float* llr_bin, const uint8_t* synd,
+                int B, const int32_t* index, int nact, uint8_t* e_hat, int32_t* chosen, void* workspace, size_t workspace_bytes,
+                void* stream);
 /* index[0..*count) = ids b with (mask[b] & bit) != 0 (tf.where(err), bp_osd.py:166-171); *count (device int32) must be
  * zero on entry; ids of one 256-sample block are ascending, blocks arrive in any order. */
 int fgnn_compact(const uint8_t* mask, int bit, int B, int32_t* index, int32_t* count, void* stream);
