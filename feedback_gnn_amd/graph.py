@@ -760,6 +760,25 @@ class TannerGraph:
                                          _ptr(synd), B, _ptr(soft), _ptr(hard), _stream(self.device)))
         return soft, hard
 
+    def relay_decode(self, synd, gamma, pre_iter, leg_iter, stop_nconv, factor=1.0, llr_ch=None, llr_const=0.0, B=None):
+        """Relay-BP on the hx graph (`fgnn_relay_decode`): `gamma` [num_legs, n] float32 on the device, one row of memory strengths per
+        leg.  Returns `(hard [B,n] uint8, stats [B,4] int32 = found, weight, leg, k)`."""
+        if synd is not None:
+            B = int(synd.shape[0])
+            synd = self._chk(synd, (B, self.m_x), torch.uint8, "syndrome")
+        if llr_ch is not None:
+            B = int(llr_ch.shape[0]) if B is None else B
+            llr_ch = self._chk(llr_ch, (B, self.n), torch.float32, "llr_ch")
+        if gamma.dim() != 2 or gamma.shape[0] < 1:
+            raise ValueError("gamma must have shape [num_legs, n]")
+        gamma = self._chk(gamma, (int(gamma.shape[0]), self.n), torch.float32, "gamma")
+        hard = self._new((B, self.n), torch.uint8)
+        stats = self._new((B, 4), torch.int32)
+        check(_lib.lib().fgnn_relay_decode(self.handle, float(factor), int(pre_iter), int(gamma.shape[0]), int(leg_iter), int(stop_nconv),
+                                           _ptr(gamma), _ptr(llr_ch), float(llr_const), _ptr(synd), B, _ptr(hard), _ptr(stats),
+                                           _stream(self.device)))
+        return hard, stats
+
     def bsc_noise(self, seed, p, first_sample, B):
         e = self._new((B, self.n), torch.uint8)
         with torch.cuda.device(self.device):

@@ -265,6 +265,27 @@ int fgnn_sandwich_decode(const fgnn_graph* g, int num_layers, const int32_t* ite
  * (all-zero syndrome = ordinary decoding).  soft_out [B,n] = output logits, hard_out [B,n] = (0 < logit) (:1033-1034). */
 int fgnn_bp2_decode(const fgnn_graph* g, int cn_type, int num_iter, float normalization_factor, const float* llr_ch,
                     float llr_const, const uint8_t* synd, int B, float* soft_out, uint8_t* hard_out, void* stream);
+/* Relay-BP (Mueller et al., "Improved belief propagation is sufficient for real-time decoding of quantum memories", 2025): a chain of
+ * num_legs min-sum BP runs ("legs") on side 0 (hx) with per-bit memory strengths gamma [num_legs,n] (device float32, shared by the
+ * batch); every leg starts from the posteriors the previous one ended with, and the lowest-weight solution met is kept.  llr_ch /
+ * llr_const / synd as fgnn_bp2_decode.  All arithmetic is float32 in the order written; sums run over a bit's slots in ascending
+ * order from 0.0f.  Per codeword:
+ *     L_v = -1 * clamp(llr_v, -20, 20);  q_v = (int32) rint(1024 * L_v);  P_v = L_v;  found = 0
+ *     for r in 0 .. num_legs-1:   T = pre_iter if r == 0 else leg_iter;  mu_e = 0 on every edge;  gam_v = gamma[r, v]
+ *         for k in 0 .. T:                                   (k = finished check updates of this leg)
+ *             S_v = sum of mu_e over the bit's edges
+ *             if k > 0:  P_v = Lam_v + S_v;  d_v = (P_v < 0)
+ *                        if H d == s:  w = sum_v d_v q_v;  found += 1;  if found == 1 or w < best_w: best = (d, w, r, k);  end this leg
+ *                        if k == T: end this leg
+ *             Lam_v = (1.0f - gam_v) * L_v + gam_v * P_v     (two products, then one add)
+ *             x = S_v + Lam_v;  nu_e = x - mu_e on the bit's edges;  mu = min-sum check update of nu (clip +-20, * normalization_factor)
+ *         if found == stop_nconv: stop
+ * hard_out [B,n] = the best d if found > 0, else the d of the last test made (last leg, k = T); stats [B,4] (int32) = found, the
+ * weight w of the output d, the leg and the k of the output d.  pre_iter, num_legs, leg_iter, stop_nconv >= 1.  The messages and
+ * posteriors of a codeword stay in LDS for the whole launch; a graph they do not fit is refused (FGNN_ERR_ARG). */
+int fgnn_relay_decode(const fgnn_graph* g, float normalization_factor, int pre_iter, int num_legs, int leg_iter, int stop_nconv,
+                      const float* gamma, const float* llr_ch, float llr_const, const uint8_t* synd, int B, uint8_t* hard_out,
+                      int32_t* stats, void* stream);
 /* BinarySymmetricChannel on the all-zero word, BP_BSC_Model.call feedback_gnn.py:213-214: noise = u < p (Philox stream). */
 int fgnn_bsc_noise(uint64_t seed, float p, uint64_t first_sample, int B, int n, uint8_t* noise, void* stream);
 
