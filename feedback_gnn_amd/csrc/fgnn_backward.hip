@@ -268,10 +268,7 @@ __global__ void __launch_bounds__(256) gnn_backward_kernel(GraphDev g, WeightsDe
     extern __shared__ float lds[];
     float* gcn = lds;  // [m_x] then [m_z]: h_cn of :168-172
     const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x, n = g.n;
-    for (int c = tid; c < g.m_x; c += nt)
-        gcn[c] = a.logit_hx[(size_t)b * g.m_x + c] * ((a.synd_x[(size_t)b * g.m_x + c] & 1) ? -1.0f : 1.0f);
-    for (int c = tid; c < g.m_z; c += nt)
-        gcn[g.m_x + c] = a.logit_hz[(size_t)b * g.m_z + c] * ((a.synd_z[(size_t)b * g.m_z + c] & 1) ? -1.0f : 1.0f);
+    stage_check_features(g, a.logit_hx, a.logit_hz, a.synd_x, a.synd_z, b, gcn, tid, nt);
     __syncthreads();
     const float* in = a.llr + (size_t)b * 3 * n;
     const float* go = a.gout + (size_t)b * 3 * n;
@@ -423,10 +420,7 @@ __global__ void __launch_bounds__(256) gnn_general_backward_kernel(GraphDev g, G
     extern __shared__ float lds[];
     float* gcn = lds;  // [m_x] then [m_z]: h_cn of :168-172
     const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x, n = g.n;
-    for (int c = tid; c < g.m_x; c += nt)
-        gcn[c] = a.logit_hx[(size_t)b * g.m_x + c] * ((a.synd_x[(size_t)b * g.m_x + c] & 1) ? -1.0f : 1.0f);
-    for (int c = tid; c < g.m_z; c += nt)
-        gcn[g.m_x + c] = a.logit_hz[(size_t)b * g.m_z + c] * ((a.synd_z[(size_t)b * g.m_z + c] & 1) ? -1.0f : 1.0f);
+    stage_check_features(g, a.logit_hx, a.logit_hz, a.synd_x, a.synd_z, b, gcn, tid, nt);
     __syncthreads();
     const int D = w.D, L = w.L, rop = w.reduce_op;
     const bool extremum = rop == FGNN_REDUCE_MAX || rop == FGNN_REDUCE_MIN;

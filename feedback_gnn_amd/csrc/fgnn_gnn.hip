@@ -21,6 +21,7 @@
 // Arithmetic order = oracle/fgnn_oracle.c (gnn_edge_side / gnn_one): every dot product is an fmaf
 // chain in ascending k starting from 0, then + bias; edge messages are summed in ascending check
 // order and divided by the degree.
+#include <algorithm>
 #include <cstring>
 
 #include "fgnn_internal.h"
@@ -171,12 +172,7 @@ __global__ void __launch_bounds__(256 * CPB) FGNN_GNN_OCC gnn_mfma_kernel(GraphD
     float* gcn = lds + T_COUNT * 64 + cwl * a.lds_per_cw;
     const int n = g.n;
     for (int i = threadIdx.x; i < T_COUNT * 64; i += 256 * CPB) tabs[i] = w.lane_tab[i];
-    if (active) {
-        for (int c = tid; c < g.m_x; c += 256)
-            gcn[c] = a.logit_hx[(size_t)b * g.m_x + c] * ((a.synd_x[(size_t)b * g.m_x + c] & 1) ? -1.0f : 1.0f);
-        for (int c = tid; c < g.m_z; c += 256)
-            gcn[g.m_x + c] = a.logit_hz[(size_t)b * g.m_z + c] * ((a.synd_z[(size_t)b * g.m_z + c] & 1) ? -1.0f : 1.0f);
-    }
+    if (active) stage_check_features(g, a.logit_hx, a.logit_hz, a.synd_x, a.synd_z, b, gcn, tid, 256);
     __syncthreads();
     if (!active) return;
 
@@ -298,12 +294,7 @@ __global__ void __launch_bounds__(1024) gnn_kernel(GraphDev g, WeightsDev w, Gnn
     const int b = (active && a.index) ? a.index[slot_b] : slot_b;
     float* gcn = lds + (size_t)cwl * a.lds_per_cw;  // [m_x] g_x then [m_z] g_z  (:168-172)
     const int n = g.n;
-    if (active) {
-        for (int c = lane; c < g.m_x; c += a.tpc)
-            gcn[c] = a.logit_hx[(size_t)b * g.m_x + c] * ((a.synd_x[(size_t)b * g.m_x + c] & 1) ? -1.0f : 1.0f);
-        for (int c = lane; c < g.m_z; c += a.tpc)
-            gcn[g.m_x + c] = a.logit_hz[(size_t)b * g.m_z + c] * ((a.synd_z[(size_t)b * g.m_z + c] & 1) ? -1.0f : 1.0f);
-    }
+    if (active) stage_check_features(g, a.logit_hx, a.logit_hz, a.synd_x, a.synd_z, b, gcn, lane, a.tpc);
     __syncthreads();
     if (!active) return;
     const float* in = a.llr + (size_t)b * 3 * n;
@@ -551,10 +542,7 @@ gnn_stream_kernel(GraphDev g, WeightsDev w, GnnArgs a)
     const int b = a.index ? a.index[slot_b] : slot_b;
     float* gcn = lds;  // [m_x] g_x then [m_z] g_z  (:168-172)
     const int n = g.n;
-    for (int c = threadIdx.x; c < g.m_x; c += blockDim.x)
-        gcn[c] = a.logit_hx[(size_t)b * g.m_x + c] * ((a.synd_x[(size_t)b * g.m_x + c] & 1) ? -1.0f : 1.0f);
-    for (int c = threadIdx.x; c < g.m_z; c += blockDim.x)
-        gcn[g.m_x + c] = a.logit_hz[(size_t)b * g.m_z + c] * ((a.synd_z[(size_t)b * g.m_z + c] & 1) ? -1.0f : 1.0f);
+    stage_check_features(g, a.logit_hx, a.logit_hz, a.synd_x, a.synd_z, b, gcn, threadIdx.x, blockDim.x);
     __syncthreads();
     const float* in = a.llr + (size_t)b * 3 * n;
     float* out = a.out + (size_t)b * 3 * n;
@@ -614,12 +602,7 @@ __global__ void __launch_bounds__(1024) gnn_general_kernel(GraphDev g, GnnGenera
     const int b = (active && a.index) ? a.index[slot_b] : slot_b;
     float* gcn = lds + (size_t)cwl * a.lds_per_cw;
     const int n = g.n;
-    if (active) {
-        for (int c = lane; c < g.m_x; c += a.tpc)
-            gcn[c] = a.logit_hx[(size_t)b * g.m_x + c] * ((a.synd_x[(size_t)b * g.m_x + c] & 1) ? -1.0f : 1.0f);
-        for (int c = lane; c < g.m_z; c += a.tpc)
-            gcn[g.m_x + c] = a.logit_hz[(size_t)b * g.m_z + c] * ((a.synd_z[(size_t)b * g.m_z + c] & 1) ? -1.0f : 1.0f);
-    }
+    if (active) stage_check_features(g, a.logit_hx, a.logit_hz, a.synd_x, a.synd_z, b, gcn, lane, a.tpc);
     __syncthreads();
     if (!active) return;
     const float* in = a.llr + (size_t)b * 3 * n;
@@ -647,15 +630,7 @@ __global__ void __launch_bounds__(1024) gnn_general_kernel(GraphDev g, GnnGenera
                     cur = nxt;
                     nxt = t;
                 }
-                for (int i = 0; i < D; ++i) {  // reduce_msg (:130-150), edges in ascending check order
-                    const float m = cur[i];
-                    float r;
-                    if (e == e0) r = m;
-                    else if (w.reduce_op == FGNN_REDUCE_MAX) r = FG_MAX(acc[i], m);
-                    else if (w.reduce_op == FGNN_REDUCE_MIN) r = FG_MIN(acc[i], m);
-                    else r = acc[i] + m;
-                    acc[i] = r;
-                }
+                gg_reduce(acc, cur, D, e == e0, w.reduce_op);  // reduce_msg (:130-150), edges in ascending check order
             }
             if (w.reduce_op == FGNN_REDUCE_MEAN && e1 > e0) {
                 const float fd = (float)(e1 - e0);
@@ -759,39 +734,23 @@ extern "C" int fgnn_weights_create(const float* const host_arrays[12], int devic
     // per-lane MFMA operand tables (see the T_* enum above)
     const size_t off_tab = push((size_t)T_COUNT * 64);
     {
-        float* T = &h[off_tab];
-        auto put = [&](int entry, int lane, float val) { T[(size_t)entry * 64 + lane] = val; };
-        for (int lane = 0; lane < 64; ++lane) {
-            const int rho = lane & 15, kk = lane >> 4, qq = lane >> 4;
-            for (int s2 = 0; s2 < 2; ++s2) {
-                const float* W1 = host_arrays[2 + 4 * s2];
-                const float* B1 = host_arrays[3 + 4 * s2];
-                const float* W2 = host_arrays[4 + 4 * s2];
-                const float* B2 = host_arrays[5 + 4 * s2];
-                for (int t = 0; t < 3; ++t) {
-                    const int unit = mfma_unit(lane, t);
-                    put(T_W1 + s2 * 3 + t, lane, unit < HID ? W1[kk * HID + unit] : 0.0f);
-                }
-                for (int s = 0; s < 10; ++s) put(T_B1 + s2 * 10 + s, lane, B1[4 * s + qq]);
-                for (int u = 0; u < 2; ++u)
-                    for (int s = 0; s < 10; ++s) {
-                        const int mu = mfma_w2_col(lane, u);
-                        put(T_W2 + (s2 * 2 + u) * 10 + s, lane, mu >= 0 ? W2[(4 * s + kk) * MSG + mu] : 0.0f);
-                    }
-                for (int i = 0; i < 5; ++i) put(T_B2 + s2 * 5 + i, lane, B2[mfma_b2_row(lane, i)]);
-                for (int s = 0; s < 10; ++s) put(T_W10 + s2 * 10 + s, lane, W1[0 * HID + 4 * s + qq]);
-            }
-            for (int t = 0; t < 3; ++t)
-                for (int s = 0; s < 11; ++s) {
-                    const int unit = mfma_unit(lane, t), k = 4 * s + kk;
-                    put(T_WE + t * 11 + s, lane, (unit < HID && k < 43) ? host_arrays[10][k * HID + unit] : 0.0f);
-                }
-            for (int s = 0; s < 10; ++s) {
-                put(T_BE + s, lane, host_arrays[11][4 * s + qq]);
-                put(T_WO + s, lane, rho < 3 ? host_arrays[0][(4 * s + kk) * 3 + rho] : 0.0f);
-            }
-            for (int r = 0; r < 3; ++r) put(T_BO + r, lane, host_arrays[1][r]);
+        auto entry = [&](int e) { return &h[off_tab + (size_t)e * 64]; };
+        for (int s2 = 0; s2 < 2; ++s2) {
+            const float* W1 = host_arrays[2 + 4 * s2];
+            for (int t = 0; t < 3; ++t) mfma_fill_w1(entry(T_W1 + s2 * 3 + t), W1, 4, HID, t, 0);
+            for (int s = 0; s < 10; ++s) mfma_fill_b1(entry(T_B1 + s2 * 10 + s), host_arrays[3 + 4 * s2], s);
+            for (int u = 0; u < 2; ++u)
+                for (int s = 0; s < 10; ++s) mfma_fill_w2(entry(T_W2 + (s2 * 2 + u) * 10 + s), host_arrays[4 + 4 * s2], MSG, u, s);
+            for (int i = 0; i < 5; ++i) mfma_fill_b2(entry(T_B2 + s2 * 5 + i), host_arrays[5 + 4 * s2], i);
+            for (int s = 0; s < 10; ++s) mfma_fill_b1(entry(T_W10 + s2 * 10 + s), W1, s);  // row 0 of W1: the check feature's weights
         }
+        for (int t = 0; t < 3; ++t)
+            for (int s = 0; s < 11; ++s) mfma_fill_w1(entry(T_WE + t * 11 + s), host_arrays[10], 43, HID, t, s);
+        for (int s = 0; s < 10; ++s) {
+            mfma_fill_b1(entry(T_BE + s), host_arrays[11], s);
+            mfma_fill_wout(entry(T_WO + s), host_arrays[0], s);
+        }
+        for (int r = 0; r < 3; ++r) std::fill_n(entry(T_BO + r), 64, host_arrays[1][r]);
     }
 
     fgnn_weights* w = new fgnn_weights();
@@ -897,27 +856,16 @@ int fgnn_feedback_gnn_impl(const fgnn_graph* g, const fgnn_weights* w, const flo
     if (!llr || !logit_hx || !logit_hz || !synd_x || !synd_z || !out) return fgnn_fail(FGNN_ERR_ARG, "buffer is NULL");
     FGNN_DEVICE_GUARD(g->device);
     LaunchGeom L = fgnn_geom(g, B);
-    GnnArgs a;
-    a.B = B;
-    a.tpc = L.tpc;
-    a.cpb = L.cpb;
-    a.lds_per_cw = (g->d.m + 3) & ~3;
-    a.llr = llr;
-    a.logit_hx = logit_hx;
-    a.logit_hz = logit_hz;
-    a.synd_x = synd_x;
-    a.synd_z = synd_z;
-    a.out = out;
-    a.index = index;
-    a.nsplit = 1;
+    GnnArgs a{B, L.tpc, L.cpb, (g->d.m + 3) & ~3, llr, logit_hx, logit_hz, synd_x, synd_z, out, index, /*nsplit=*/1};
     fgnn_prof_scope prof(g, static_cast<hipStream_t>(stream));
-    if (w->general) {
-        size_t lds_gen = (size_t)a.lds_per_cw * sizeof(float) * (size_t)L.cpb;
-        const int rc = fgnn_launch(gnn_general_kernel, dim3(L.blocks), dim3(L.threads), lds_gen, static_cast<hipStream_t>(stream), g->d,
-                                   w->gen, a);
+    // the profile tag is recorded when the launch succeeded
+    auto launch = [&](auto kern, unsigned blocks, int threads, size_t lds, const auto& wdev) {
+        const int rc = fgnn_launch(kern, dim3(blocks), dim3(threads), lds, static_cast<hipStream_t>(stream), g->d, wdev, a);
         if (rc == FGNN_OK) prof.done(FGNN_PROF_TAG_GNN, B);
         return rc;
-    }
+    };
+    const size_t lds_packed = (size_t)a.lds_per_cw * sizeof(float) * (size_t)L.cpb;  // the kernels that pack L.cpb codewords per workgroup
+    if (w->general) return launch(gnn_general_kernel, L.blocks, L.threads, lds_packed, w->gen);
     // Below ~4 000 codewords the launch is latency-bound, and there the MFMA-tile kernel, which deals one codeword's tiles to many waves,
     // is up to 3x quicker (18 vs 52 us for <= 64 codewords of [[882,24]]; equal from 256 to 2 048; the streaming kernel wins from 4 096 on:
     // profiles/r3_gnn_stream_ab.txt; the literal association's streaming kernel likewise: profiles/r4_gnn_literal_stream_ab.txt) -
@@ -946,9 +894,7 @@ int fgnn_feedback_gnn_impl(const fgnn_graph* g, const fgnn_weights* w, const flo
         constexpr bool PF = FGNN_GNNS_EMBPK_FACT != 0, PL = FGNN_GNNS_EMBPK_LIT != 0;
         auto skern = g->gnn_factored ? (g->d.dvx == 3 ? gnn_stream_kernel<3, false, PF> : g->d.dvx == 4 ? gnn_stream_kernel<4, false, PF> : gnn_stream_kernel<5, false, PF>)
                                      : (g->d.dvx == 3 ? gnn_stream_kernel<3, true, PL> : g->d.dvx == 4 ? gnn_stream_kernel<4, true, PL> : gnn_stream_kernel<5, true, PL>);
-        const int rc = fgnn_launch(skern, dim3((unsigned)B), dim3(best_tpc), lds_s, static_cast<hipStream_t>(stream), g->d, w->d, a);
-        if (rc == FGNN_OK) prof.done(FGNN_PROF_TAG_GNN, B);
-        return rc;
+        return launch(skern, (unsigned)B, best_tpc, lds_s, w->d);
     }
     if (g->d.dvx == 3 && g->d.dvz == 3 && !g->force_generic) {
         // degree-regular graph: MFMA kernel, four waves per codeword, GNN_CPB codewords per workgroup
@@ -960,16 +906,9 @@ int fgnn_feedback_gnn_impl(const fgnn_graph* g, const fgnn_weights* w, const flo
         while (a.nsplit < 16 && (long long)B * a.nsplit * 2 <= 2048 && a.nsplit * 4 < ntiles) a.nsplit *= 2;
         const size_t lds_mfma = (size_t)(T_COUNT * 64 + GNN_CPB * a.lds_per_cw) * sizeof(float);
         auto kern = g->gnn_factored ? gnn_mfma_kernel<3, GNN_CPB, true> : gnn_mfma_kernel<3, GNN_CPB, false>;
-        const int rc = fgnn_launch(kern, dim3((unsigned)(((long long)B * a.nsplit + GNN_CPB - 1) / GNN_CPB)), dim3(256 * GNN_CPB),
-                                   lds_mfma, static_cast<hipStream_t>(stream), g->d, w->d, a);
-        if (rc == FGNN_OK) prof.done(FGNN_PROF_TAG_GNN, B);
-        return rc;
+        return launch(kern, (unsigned)(((long long)B * a.nsplit + GNN_CPB - 1) / GNN_CPB), 256 * GNN_CPB, lds_mfma, w->d);
     }
-    size_t lds_bytes = (size_t)a.lds_per_cw * sizeof(float) * (size_t)L.cpb;
-    const int rc = fgnn_launch(g->gnn_factored ? gnn_kernel<true> : gnn_kernel<false>, dim3(L.blocks), dim3(L.threads), lds_bytes,
-                               static_cast<hipStream_t>(stream), g->d, w->d, a);
-    if (rc == FGNN_OK) prof.done(FGNN_PROF_TAG_GNN, B);
-    return rc;
+    return launch(g->gnn_factored ? gnn_kernel<true> : gnn_kernel<false>, L.blocks, L.threads, lds_packed, w->d);
 }
 
 extern "C" int fgnn_feedback_gnn(const fgnn_graph* g, const fgnn_weights* w, const float* llr, const float* logit_hx,

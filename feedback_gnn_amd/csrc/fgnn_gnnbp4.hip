@@ -250,6 +250,84 @@ struct Args {
     float* work;      // [B,(n+m)*D]
 };
 
+// The frame every GNN_BP4 kernel decodes one codeword in: its node embeddings in the global workspace, its syndromes and marginals,
+// and the cal_logit state lx | lz | hlog in LDS at `state`.  Where that region lies — and ssg, in the kernels that keep one — is the
+// kernel's own choice.
+struct Frame {
+    float *hv, *hc;          // [n][dims], [m][dims] embeddings; a kernel's element order within a row is private to it
+    const uint8_t *sx, *sz;  // [m_x], [m_z] syndromes
+    float* llr;              // [3][n] of llr_out
+    float *lx, *lz, *hlog;   // [n] llr_x, [n] llr_z of cal_logit; [m] hx_logit then hz_logit
+};
+__device__ __forceinline__ Frame frame_of(const GraphDev& g, const Args& a, int b, int dims, float* state)
+{
+    Frame f;
+    f.hv = a.work + (size_t)b * (size_t)(g.n + g.m) * dims;
+    f.hc = f.hv + (size_t)g.n * dims;
+    f.sx = a.synd_x + (size_t)b * g.m_x;
+    f.sz = a.synd_z + (size_t)b * g.m_z;
+    f.llr = a.llr_out + (size_t)b * 3 * g.n;
+    f.lx = state;
+    f.lz = f.lx + g.n;
+    f.hlog = f.lz + g.n;
+    return f;
+}
+// hv = 1 (:396), hc = 0 (:392-393), zero logits for the first CN update (:400-401); ssg (null in the kernels without one) = the syndrome
+// signs 1 - 2 s as floats, hx checks then hz: read once from HBM, not once per edge
+__device__ __forceinline__ void frame_init(const GraphDev& g, const Frame& f, int dims, float* ssg, int tid, int T)
+{
+    for (int i = tid; i < g.n * dims; i += T) f.hv[i] = 1.0f;
+    for (int i = tid; i < g.m * dims; i += T) f.hc[i] = 0.0f;
+    for (int c = tid; c < g.m; c += T) {
+        f.hlog[c] = 0.0f;
+        if (ssg) ssg[c] = synd_sign(c < g.m_x ? f.sx[c] : f.sz[c - g.m_x]);
+    }
+}
+// The tail of a qubit update: the three LLRs, and the binary LLRs of cal_logit (:291-304)
+__device__ __forceinline__ void store_llrs(const Frame& f, int n, int v, float L0, float L1, float L2)
+{
+    f.llr[v] = L0;
+    f.llr[n + v] = L1;
+    f.llr[2 * n + v] = L2;
+    f.lz[v] = fg_softplus(-L0) - fg_lse2(-L2, -L1);
+    f.lx[v] = fg_softplus(-L2) - fg_lse2(-L0, -L1);
+}
+// Soft syndromes of iteration `it` (:306-314) into hlog and the *_logit_all outputs: hx rows use llr_z, hz rows use llr_x; logical
+// rows appended
+__device__ __forceinline__ void soft_syndromes(const GraphDev& g, const Args& a, const Frame& f, int b, int it, int tid, int T)
+{
+    const int mx = g.m_x, mz = g.m_z;
+    float* xl = a.xlog_all ? a.xlog_all + ((size_t)it * a.B + b) * (mz + g.rows[5]) : nullptr;
+    float* zl = a.zlog_all ? a.zlog_all + ((size_t)it * a.B + b) * (mx + g.rows[4]) : nullptr;
+    for (int c = tid; c < g.m; c += T) {
+        const int p0 = g.cptr[c];
+        const float vq = logit_row_gnn(c < mx ? f.lz : f.lx, g.cvn + p0, g.cptr[c + 1] - p0);
+        f.hlog[c] = vq;
+        if (c < mx) { if (zl) zl[c] = vq; }
+        else if (xl) xl[c - mx] = vq;
+    }
+    if (xl)
+        for (int r = tid; r < g.rows[5]; r += T)
+            xl[mz + r] = logit_row_gnn(f.lx, g.rcol[5] + g.rptr[5][r], g.rptr[5][r + 1] - g.rptr[5][r]);
+    if (zl)
+        for (int r = tid; r < g.rows[4]; r += T)
+            zl[mx + r] = logit_row_gnn(f.lz, g.rcol[4] + g.rptr[4][r], g.rptr[4][r + 1] - g.rptr[4][r]);
+}
+// make_hard_decision (:359-367): the smallest of X, Z, Y below 0, compared in that order, else the identity
+__device__ __forceinline__ void hard_decision(const Args& a, const Frame& f, int n, int b, int tid, int T)
+{
+    for (int v = tid; v < n; v += T) {
+        const float X = f.llr[v], Y = f.llr[n + v], Z = f.llr[2 * n + v];
+        int d = 0;
+        float best = 0.0f;
+        if (X < best) { best = X; d = 1; }
+        if (Z < best) { best = Z; d = 2; }
+        if (Y < best) { best = Y; d = 3; }
+        a.x_hat[(size_t)b * n + v] = (uint8_t)(d & 1);
+        a.z_hat[(size_t)b * n + v] = (uint8_t)(d >> 1);
+    }
+}
+
 template <bool FACT>
 __global__ void __launch_bounds__(256) gnn_bp4_kernel(GraphDev g, GnnBp4Dev w, Args a)
 {
@@ -257,26 +335,16 @@ __global__ void __launch_bounds__(256) gnn_bp4_kernel(GraphDev g, GnnBp4Dev w, A
     extern __shared__ float lds[];
     const int b = blockIdx.x, tid = threadIdx.x, T = blockDim.x;
     const int n = g.n, mx = g.m_x, m = g.m;
-    float* lx = lds;          // [n]   llr_x of cal_logit
-    float* lz = lx + n;       // [n]   llr_z
-    float* hlog = lz + n;     // [m]   hx_logit then hz_logit
-    float* hv = a.work + (size_t)b * (size_t)(n + m) * D;
-    float* hc = hv + (size_t)n * D;
-    const uint8_t* sx = a.synd_x + (size_t)b * mx;
-    const uint8_t* sz = a.synd_z + (size_t)b * g.m_z;
-    const int rxp = g.m_z + g.rows[5], rzp = g.m_x + g.rows[4];
-    for (int i = tid; i < n * D; i += T) hv[i] = 1.0f;  // (:396)
-    for (int i = tid; i < m * D; i += T) hc[i] = 0.0f;  // (:392-393)
-    for (int c = tid; c < m; c += T) hlog[c] = 0.0f;    // zero logits for the first CN update (:400-401)
+    const Frame f = frame_of(g, a, b, D, lds);
+    frame_init(g, f, D, nullptr, tid, T);
     __syncthreads();
-    float* llr = a.llr_out + (size_t)b * 3 * n;
     for (int it = -1; it < a.num_iter; ++it) {
         if (it >= 0) {
             // ---- UpdateVNEmbeddings (:714-751) + llr / binary LLRs of cal_logit (:291-304) ----
             for (int v = tid; v < n; v += T) {
                 float own[D], feat3[3 * D];
 #pragma unroll
-                for (int i = 0; i < D; ++i) own[i] = hv[(size_t)v * D + i];
+                for (int i = 0; i < D; ++i) own[i] = f.hv[(size_t)v * D + i];
 #pragma unroll
                 for (int s = 0; s < 2; ++s) {
                     const int* vptr = s ? g.vptr_z : g.vptr_x;
@@ -285,8 +353,8 @@ __global__ void __launch_bounds__(256) gnn_bp4_kernel(GraphDev g, GnnBp4Dev w, A
 #pragma unroll
                     for (int i = 0; i < D; ++i) acc[i] = 0.0f;
                     if constexpr (FACT) {
-                        msg_mean_factored(own, e1 - e0, [&](int e) { return hc + (size_t)((s ? mx : 0) + g.vchk[e0 + e]) * D; },
-                                          [&](int e) { const int c = g.vchk[e0 + e]; return ((s ? sz[c] : sx[c]) & 1) ? -1.0f : 1.0f; },
+                        msg_mean_factored(own, e1 - e0, [&](int e) { return f.hc + (size_t)((s ? mx : 0) + g.vchk[e0 + e]) * D; },
+                                          [&](int e) { const int c = g.vchk[e0 + e]; return synd_sign(s ? f.sz[c] : f.sx[c]); },
                                           w.vn_msg[s], acc);
 #pragma unroll
                         for (int i = 0; i < D; ++i) feat3[s * D + i] = acc[i];
@@ -294,12 +362,12 @@ __global__ void __launch_bounds__(256) gnn_bp4_kernel(GraphDev g, GnnBp4Dev w, A
                     }
                     for (int e = e0; e < e1; ++e) {
                         const int c = g.vchk[e];  // side-local check id
-                        const float* src = hc + (size_t)((s ? mx : 0) + c) * D;
+                        const float* src = f.hc + (size_t)((s ? mx : 0) + c) * D;
                         float feat[2 * D], msg[D];
 #pragma unroll
                         for (int i = 0; i < D; ++i) { feat[i] = src[i]; feat[D + i] = own[i]; }
                         mlp2<2 * D, 2 * D>(feat, w.vn_msg[s], msg);
-                        const float sg = ((s ? sz[c] : sx[c]) & 1) ? -1.0f : 1.0f;
+                        const float sg = synd_sign(s ? f.sz[c] : f.sx[c]);
 #pragma unroll
                         for (int i = 0; i < D; ++i) { const float mv = msg[i] * sg; acc[i] = (e == e0) ? mv : acc[i] + mv; }
                     }
@@ -318,7 +386,7 @@ __global__ void __launch_bounds__(256) gnn_bp4_kernel(GraphDev g, GnnBp4Dev w, A
                 float L[3] = {0.0f, 0.0f, 0.0f};
 #pragma unroll
                 for (int k = 0; k < D; ++k) {
-                    hv[(size_t)v * D + k] = nh[k];
+                    f.hv[(size_t)v * D + k] = nh[k];
                     L[0] = FG_FMA(nh[k], as_scalar(w.winv)[k * 4 + 0], L[0]);
                     L[1] = FG_FMA(nh[k], as_scalar(w.winv)[k * 4 + 1], L[1]);
                     L[2] = FG_FMA(nh[k], as_scalar(w.winv)[k * 4 + 2], L[2]);
@@ -326,29 +394,10 @@ __global__ void __launch_bounds__(256) gnn_bp4_kernel(GraphDev g, GnnBp4Dev w, A
                 L[0] = L[0] + w.binv[0];
                 L[1] = L[1] + w.binv[1];
                 L[2] = L[2] + w.binv[2];
-                llr[v] = L[0];
-                llr[n + v] = L[1];
-                llr[2 * n + v] = L[2];
-                lz[v] = fg_softplus(-L[0]) - fg_lse2(-L[2], -L[1]);
-                lx[v] = fg_softplus(-L[2]) - fg_lse2(-L[0], -L[1]);
+                store_llrs(f, n, v, L[0], L[1], L[2]);
             }
             __syncthreads();
-            // ---- soft syndromes (:306-314): hx rows use llr_z, hz rows use llr_x; logical rows appended ----
-            float* xl = a.xlog_all ? a.xlog_all + ((size_t)it * a.B + b) * rxp : nullptr;
-            float* zl = a.zlog_all ? a.zlog_all + ((size_t)it * a.B + b) * rzp : nullptr;
-            for (int c = tid; c < m; c += T) {
-                const int p0 = g.cptr[c];
-                const float vq = logit_row_gnn(c < mx ? lz : lx, g.cvn + p0, g.cptr[c + 1] - p0);
-                hlog[c] = vq;
-                if (c < mx) { if (zl) zl[c] = vq; }
-                else if (xl) xl[c - mx] = vq;
-            }
-            if (xl)
-                for (int r = tid; r < g.rows[5]; r += T)
-                    xl[g.m_z + r] = logit_row_gnn(lx, g.rcol[5] + g.rptr[5][r], g.rptr[5][r + 1] - g.rptr[5][r]);
-            if (zl)
-                for (int r = tid; r < g.rows[4]; r += T)
-                    zl[g.m_x + r] = logit_row_gnn(lz, g.rcol[4] + g.rptr[4][r], g.rptr[4][r + 1] - g.rptr[4][r]);
+            soft_syndromes(g, a, f, b, it, tid, T);
             __syncthreads();
             if (it == a.num_iter - 1) break;  // (:414-415)
         }
@@ -356,16 +405,16 @@ __global__ void __launch_bounds__(256) gnn_bp4_kernel(GraphDev g, GnnBp4Dev w, A
         for (int c = tid; c < m; c += T) {
             const int s = c >= mx;
             const int p0 = g.cptr[c], p1 = g.cptr[c + 1];
-            float* hto = hc + (size_t)c * D;
+            float* hto = f.hc + (size_t)c * D;
             float own[D], acc[D];
 #pragma unroll
             for (int i = 0; i < D; ++i) { own[i] = hto[i]; acc[i] = 0.0f; }
             if constexpr (FACT)
-                msg_mean_factored(own, p1 - p0, [&](int e) { return hv + (size_t)g.cvn[p0 + e] * D; }, [](int) { return 1.0f; },
+                msg_mean_factored(own, p1 - p0, [&](int e) { return f.hv + (size_t)g.cvn[p0 + e] * D; }, [](int) { return 1.0f; },
                                   w.cn_msg[s], acc);
             else
             for (int jx = p0; jx < p1; ++jx) {
-                const float* src = hv + (size_t)g.cvn[jx] * D;
+                const float* src = f.hv + (size_t)g.cvn[jx] * D;
                 float feat[2 * D], msg[D];
 #pragma unroll
                 for (int i = 0; i < D; ++i) { feat[i] = src[i]; feat[D + i] = own[i]; }
@@ -381,24 +430,14 @@ __global__ void __launch_bounds__(256) gnn_bp4_kernel(GraphDev g, GnnBp4Dev w, A
             float feat[2 * D + 1], nh[D];
 #pragma unroll
             for (int i = 0; i < D; ++i) { feat[i] = acc[i]; feat[D + i] = own[i]; }
-            const unsigned sb = (s ? sz[c - mx] : sx[c]) & 1;
-            feat[2 * D] = (it >= 0) ? hlog[c] * (sb ? -1.0f : 1.0f) : 0.0f;  // (:417-418)
+            feat[2 * D] = (it >= 0) ? f.hlog[c] * synd_sign(s ? f.sz[c - mx] : f.sx[c]) : 0.0f;  // (:417-418)
             mlp2<2 * D + 1, 2 * D + 4>(feat, w.cn_embed[s], nh);
 #pragma unroll
             for (int i = 0; i < D; ++i) hto[i] = nh[i];
         }
         __syncthreads();
     }
-    for (int v = tid; v < n; v += T) {  // make_hard_decision (:359-367)
-        const float X = llr[v], Y = llr[n + v], Z = llr[2 * n + v];
-        int d = 0;
-        float best = 0.0f;
-        if (X < best) { best = X; d = 1; }
-        if (Z < best) { best = Z; d = 2; }
-        if (Y < best) { best = Y; d = 3; }
-        a.x_hat[(size_t)b * n + v] = (uint8_t)(d & 1);
-        a.z_hat[(size_t)b * n + v] = (uint8_t)(d >> 1);
-    }
+    hard_decision(a, f, n, b, tid, T);
 }
 
 #ifndef FGNN_GNNBP4_THREADS
@@ -424,22 +463,9 @@ gnn_bp4_mfma_kernel(GraphDev g, GnnBp4Dev w, Args a, int tab_floats, int residen
     const int b = blockIdx.x, tid = threadIdx.x;
     const int n = g.n, mx = g.m_x, mz = g.m_z, m = g.m;
     float* tabs = lds;
-    float* lx = lds + tab_floats;
-    float* lz = lx + n;
-    float* hlog = lz + n;
-    float* ssg = hlog + m;  // [m] syndrome signs 1 - 2 s as floats (hx checks, then hz): read once from HBM, not once per edge
-    float* hv = a.work + (size_t)b * (size_t)(n + m) * D;
-    float* hc = hv + (size_t)n * D;
-    const uint8_t* sx = a.synd_x + (size_t)b * mx;
-    const uint8_t* sz = a.synd_z + (size_t)b * mz;
-    const int rxp = mz + g.rows[5], rzp = mx + g.rows[4];
-    for (int i = tid; i < n * D; i += T) hv[i] = 1.0f;
-    for (int i = tid; i < m * D; i += T) hc[i] = 0.0f;
-    for (int c = tid; c < m; c += T) {
-        hlog[c] = 0.0f;
-        ssg[c] = ((c < mx ? sx[c] : sz[c - mx]) & 1) ? -1.0f : 1.0f;
-    }
-    float* llr = a.llr_out + (size_t)b * 3 * n;
+    const Frame f = frame_of(g, a, b, D, lds + tab_floats);
+    float* ssg = f.hlog + m;  // [m] syndrome signs
+    frame_init(g, f, D, ssg, tid, T);
     const int l = tid & 63, wave = tid >> 6, j = l & 15, q = l >> 4;
     const float* tab_cn = tabs + l;                                                    // check-phase tables
     const float* tab = tab_cn + (resident ? (w.tab_vn_msg[0] - w.tab_cn_msg[0]) * 64 : 0);  // qubit-phase tables
@@ -461,7 +487,7 @@ gnn_bp4_mfma_kernel(GraphDev g, GnnBp4Dev w, Args a, int tab_floats, int residen
                 const bool valid = vraw < n;
                 const int v = valid ? vraw : n - 1;
                 float own[5], Bemb[15];
-                load_row5(hv + (size_t)v * D, q, own);
+                load_row5(f.hv + (size_t)v * D, q, own);
                 // all 2 x DV neighbour rows of the tile are requested before the first MLP starts: the gathers (L2-resident rows of
                 // other workgroups' making) then complete under ~1 600 cycles of MFMA work each instead of in front of it
                 // neighbour rows one edge ahead: while the MLP of edge e runs (~1 600 cycles of MFMA work) the gather of edge e + 1
@@ -472,7 +498,7 @@ gnn_bp4_mfma_kernel(GraphDev g, GnnBp4Dev w, Args a, int tab_floats, int residen
 #pragma unroll
                     for (int k = 0; k < DV; ++k) cn_of[s2][k] = g.vchk[(s2 ? g.E_x : 0) + v * DV + k];
                 float fcur[5], fnxt[5];
-                load_row5(hc + (size_t)cn_of[0][0] * D, q, fcur);
+                load_row5(f.hc + (size_t)cn_of[0][0] * D, q, fcur);
 #pragma unroll
                 for (int s2 = 0; s2 < 2; ++s2) {
                     float acc[5];
@@ -483,7 +509,7 @@ gnn_bp4_mfma_kernel(GraphDev g, GnnBp4Dev w, Args a, int tab_floats, int residen
                         for (int k = 0; k < DV; ++k) {
                             const int c = cn_of[s2][k];
                             const int e1 = s2 * DV + k + 1;  // next edge, flattened over both sides
-                            if (e1 < 2 * DV) load_row5(hc + (size_t)((e1 / DV ? mx : 0) + cn_of[e1 / DV][e1 % DV]) * D, q, fnxt);
+                            if (e1 < 2 * DV) load_row5(f.hc + (size_t)((e1 / DV ? mx : 0) + cn_of[e1 / DV][e1 % DV]) * D, q, fnxt);
                             const float sg = ssg[(s2 ? mx : 0) + c];
                             if (k == 0) msg_fact_edge<true>(tab, w.tab_vn_msg[s2] - vn_first, fcur, sg, st);
                             else msg_fact_edge<false>(tab, w.tab_vn_msg[s2] - vn_first, fcur, sg, st);
@@ -501,7 +527,7 @@ gnn_bp4_mfma_kernel(GraphDev g, GnnBp4Dev w, Args a, int tab_floats, int residen
                         float Bin[10], msg[5];
                         {
                             const int e1 = s2 * DV + k + 1;  // next edge, flattened over both sides
-                            if (e1 < 2 * DV) load_row5(hc + (size_t)((e1 / DV ? mx : 0) + cn_of[e1 / DV][e1 % DV]) * D, q, fnxt);
+                            if (e1 < 2 * DV) load_row5(f.hc + (size_t)((e1 / DV ? mx : 0) + cn_of[e1 / DV][e1 % DV]) * D, q, fnxt);
                         }
 #pragma unroll
                         for (int s = 0; s < 5; ++s) { Bin[s] = fcur[s]; Bin[5 + s] = own[s]; }
@@ -528,33 +554,15 @@ gnn_bp4_mfma_kernel(GraphDev g, GnnBp4Dev w, Args a, int tab_floats, int residen
 #pragma unroll
                 for (int s = 0; s < 5; ++s) o = mfma4(ti[s * 64], nh[s], o);
                 if (valid) {
-                    store_row5(hv + (size_t)v * D, q, nh);
+                    store_row5(f.hv + (size_t)v * D, q, nh);
                     if (q == 0) {
                         const float L0 = o[0] + ti[5 * 64], L1 = o[1] + ti[6 * 64], L2 = o[2] + ti[7 * 64];
-                        llr[v] = L0;
-                        llr[n + v] = L1;
-                        llr[2 * n + v] = L2;
-                        lz[v] = fg_softplus(-L0) - fg_lse2(-L2, -L1);
-                        lx[v] = fg_softplus(-L2) - fg_lse2(-L0, -L1);
+                        store_llrs(f, n, v, L0, L1, L2);
                     }
                 }
             }
             __syncthreads();
-            float* xl = a.xlog_all ? a.xlog_all + ((size_t)it * a.B + b) * rxp : nullptr;
-            float* zl = a.zlog_all ? a.zlog_all + ((size_t)it * a.B + b) * rzp : nullptr;
-            for (int c = tid; c < m; c += T) {
-                const int p0 = g.cptr[c];
-                const float vq = logit_row_gnn(c < mx ? lz : lx, g.cvn + p0, g.cptr[c + 1] - p0);
-                hlog[c] = vq;
-                if (c < mx) { if (zl) zl[c] = vq; }
-                else if (xl) xl[c - mx] = vq;
-            }
-            if (xl)
-                for (int r = tid; r < g.rows[5]; r += T)
-                    xl[mz + r] = logit_row_gnn(lx, g.rcol[5] + g.rptr[5][r], g.rptr[5][r + 1] - g.rptr[5][r]);
-            if (zl)
-                for (int r = tid; r < g.rows[4]; r += T)
-                    zl[mx + r] = logit_row_gnn(lz, g.rcol[4] + g.rptr[4][r], g.rptr[4][r + 1] - g.rptr[4][r]);
+            soft_syndromes(g, a, f, b, it, tid, T);
             if (it == a.num_iter - 1) break;
         }
         __syncthreads();
@@ -570,18 +578,18 @@ gnn_bp4_mfma_kernel(GraphDev g, GnnBp4Dev w, Args a, int tab_floats, int residen
             const bool valid = local < cnt;
             const int c = (s2 ? mx : 0) + (valid ? local : cnt - 1);  // combined check id
             float own[5], acc[5], Bemb[11];
-            load_row5(hc + (size_t)c * D, q, own);
+            load_row5(f.hc + (size_t)c * D, q, own);
             int vn_of[DC];
 #pragma unroll
             for (int k = 0; k < DC; ++k) vn_of[k] = g.cvn[c * DC + k];
             float fcur[5], fnxt[5];  // neighbour rows one edge ahead (see the qubit phase)
-            load_row5(hv + (size_t)vn_of[0] * D, q, fcur);
+            load_row5(f.hv + (size_t)vn_of[0] * D, q, fcur);
             if constexpr (FACT) {
                 MsgTileFact st;
                 msg_fact_begin(tab_cn, w.tab_cn_msg[s2] - cn_first, own, st);
 #pragma unroll
                 for (int k = 0; k < DC; ++k) {
-                    if (k + 1 < DC) load_row5(hv + (size_t)vn_of[k + 1] * D, q, fnxt);
+                    if (k + 1 < DC) load_row5(f.hv + (size_t)vn_of[k + 1] * D, q, fnxt);
                     if (k == 0) msg_fact_edge<true>(tab_cn, w.tab_cn_msg[s2] - cn_first, fcur, 1.0f, st);
                     else msg_fact_edge<false>(tab_cn, w.tab_cn_msg[s2] - cn_first, fcur, 1.0f, st);
 #pragma unroll
@@ -592,7 +600,7 @@ gnn_bp4_mfma_kernel(GraphDev g, GnnBp4Dev w, Args a, int tab_floats, int residen
 #pragma unroll
             for (int k = 0; k < DC; ++k) {
                 float Bin[10], msg[5];
-                if (k + 1 < DC) load_row5(hv + (size_t)vn_of[k + 1] * D, q, fnxt);
+                if (k + 1 < DC) load_row5(f.hv + (size_t)vn_of[k + 1] * D, q, fnxt);
 #pragma unroll
                 for (int s = 0; s < 5; ++s) { Bin[s] = fcur[s]; Bin[5 + s] = own[s]; }
 #pragma unroll
@@ -606,24 +614,15 @@ gnn_bp4_mfma_kernel(GraphDev g, GnnBp4Dev w, Args a, int tab_floats, int residen
             }
 #pragma unroll
             for (int i = 0; i < 5; ++i) { Bemb[i] = acc[i]; Bemb[5 + i] = own[i]; }
-            const float lg = (it >= 0) ? hlog[c] * ssg[c] : 0.0f;
+            const float lg = (it >= 0) ? f.hlog[c] * ssg[c] : 0.0f;
             Bemb[10] = (q == 0) ? lg : 0.0f;
             float nh[5];
             mlp_tile<11>(tab_cn, w.tab_cn_embed[s2] - cn_first, Bemb, nh);
-            if (valid) store_row5(hc + (size_t)c * D, q, nh);
+            if (valid) store_row5(f.hc + (size_t)c * D, q, nh);
         }
     }
     __syncthreads();
-    for (int v = tid; v < n; v += T) {
-        const float X = llr[v], Y = llr[n + v], Z = llr[2 * n + v];
-        int d = 0;
-        float best = 0.0f;
-        if (X < best) { best = X; d = 1; }
-        if (Z < best) { best = Z; d = 2; }
-        if (Y < best) { best = Y; d = 3; }
-        a.x_hat[(size_t)b * n + v] = (uint8_t)(d & 1);
-        a.z_hat[(size_t)b * n + v] = (uint8_t)(d >> 1);
-    }
+    hard_decision(a, f, n, b, tid, T);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -794,24 +793,11 @@ gnn_bp4_stream_kernel(GraphDev g, GnnBp4Dev w, Args a)
     extern __shared__ float lds[];
     constexpr int T = 256;
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int n = g.n, mx = g.m_x, mz = g.m_z, m = g.m;
-    float* lx = lds;       // [n] llr_x of cal_logit
-    float* lz = lx + n;    // [n] llr_z
-    float* hlog = lz + n;  // [m] hx_logit then hz_logit
-    float* ssg = hlog + m; // [m] syndrome signs 1 - 2 s as floats
-    float* hv = a.work + (size_t)b * (size_t)(n + m) * D;  // rows in natural element order (private to this kernel)
-    float* hc = hv + (size_t)n * D;
-    const uint8_t* sx = a.synd_x + (size_t)b * mx;
-    const uint8_t* sz = a.synd_z + (size_t)b * mz;
-    const int rxp = mz + g.rows[5], rzp = mx + g.rows[4];
-    for (int i = tid; i < n * D; i += T) hv[i] = 1.0f;  // (:396)
-    for (int i = tid; i < m * D; i += T) hc[i] = 0.0f;  // (:392-393)
-    for (int c = tid; c < m; c += T) {
-        hlog[c] = 0.0f;  // zero logits for the first CN update (:400-401)
-        ssg[c] = ((c < mx ? sx[c] : sz[c - mx]) & 1) ? -1.0f : 1.0f;
-    }
+    const int n = g.n, mx = g.m_x, m = g.m;
+    const Frame f = frame_of(g, a, b, D, lds);  // workspace rows in natural element order
+    float* ssg = f.hlog + m;                    // [m] syndrome signs
+    frame_init(g, f, D, ssg, tid, T);
     __syncthreads();
-    float* llr = a.llr_out + (size_t)b * 3 * n;
     for (int it = -1; it < a.num_iter; ++it) {
         if (it >= 0) {
             // ---- UpdateVNEmbeddings (:714-751) + llr / binary LLRs of cal_logit (:291-304) ----
@@ -819,7 +805,7 @@ gnn_bp4_stream_kernel(GraphDev g, GnnBp4Dev w, Args a)
                 f2 feat3[3 * DP];
                 {
                     f2 own[DP];
-                    load_row20(hv + (size_t)v * D, own);
+                    load_row20(f.hv + (size_t)v * D, own);
 #pragma unroll
                     for (int s = 0; s < 2; ++s) {
                         f2 mean[DP];
@@ -828,7 +814,7 @@ gnn_bp4_stream_kernel(GraphDev g, GnnBp4Dev w, Args a)
                         auto nbr = [&](int e, float& sg) {
                             const int c = cbase + chk[e];
                             sg = ssg[c];
-                            return hc + (size_t)c * D;
+                            return f.hc + (size_t)c * D;
                         };
                         if constexpr (FACT) msg_side_stream<DV, true>(own, nbr, w.vn_msg[s], mean);
                         else msg_side_literal<DV, true>(own, nbr, w.vn_msg[s], mean);
@@ -840,33 +826,14 @@ gnn_bp4_stream_kernel(GraphDev g, GnnBp4Dev w, Args a)
                 }
                 f2 nh[DP];
                 mlp_stream<3 * D>(feat3, w.vn_embed, nh);
-                store_row20(hv + (size_t)v * D, nh);
+                store_row20(f.hv + (size_t)v * D, nh);
                 f2 Lp[2] = {bc2(0.0f), bc2(0.0f)};
                 dense_pk<D, 2, 5>(nh, w.winv, 4, Lp);
                 const float L0 = Lp[0].x + as_scalar(w.binv)[0], L1 = Lp[0].y + as_scalar(w.binv)[1], L2 = Lp[1].x + as_scalar(w.binv)[2];
-                llr[v] = L0;
-                llr[n + v] = L1;
-                llr[2 * n + v] = L2;
-                lz[v] = fg_softplus(-L0) - fg_lse2(-L2, -L1);
-                lx[v] = fg_softplus(-L2) - fg_lse2(-L0, -L1);
+                store_llrs(f, n, v, L0, L1, L2);
             }
             __syncthreads();
-            // ---- soft syndromes (:306-314): hx rows use llr_z, hz rows use llr_x; logical rows appended ----
-            float* xl = a.xlog_all ? a.xlog_all + ((size_t)it * a.B + b) * rxp : nullptr;
-            float* zl = a.zlog_all ? a.zlog_all + ((size_t)it * a.B + b) * rzp : nullptr;
-            for (int c = tid; c < m; c += T) {
-                const int p0 = g.cptr[c];
-                const float vq = logit_row_gnn(c < mx ? lz : lx, g.cvn + p0, g.cptr[c + 1] - p0);
-                hlog[c] = vq;
-                if (c < mx) { if (zl) zl[c] = vq; }
-                else if (xl) xl[c - mx] = vq;
-            }
-            if (xl)
-                for (int r = tid; r < g.rows[5]; r += T)
-                    xl[mz + r] = logit_row_gnn(lx, g.rcol[5] + g.rptr[5][r], g.rptr[5][r + 1] - g.rptr[5][r]);
-            if (zl)
-                for (int r = tid; r < g.rows[4]; r += T)
-                    zl[mx + r] = logit_row_gnn(lz, g.rcol[4] + g.rptr[4][r], g.rptr[4][r + 1] - g.rptr[4][r]);
+            soft_syndromes(g, a, f, b, it, tid, T);
             __syncthreads();
             if (it == a.num_iter - 1) break;  // (:414-415)
         }
@@ -876,11 +843,11 @@ gnn_bp4_stream_kernel(GraphDev g, GnnBp4Dev w, Args a)
             f2 feat[DP + DP + 1];
             {
                 f2 own[DP], mean[DP];
-                load_row20(hc + (size_t)c * D, own);
+                load_row20(f.hc + (size_t)c * D, own);
                 const int* vns = g.cvn + c * DC;
                 auto nbr = [&](int e, float& sg) {
                     sg = 1.0f;
-                    return hv + (size_t)vns[e] * D;
+                    return f.hv + (size_t)vns[e] * D;
                 };
                 // a wave of 64 checks may straddle the hx / hz boundary, and the two sides have their own weights: each side's update
                 // runs under its own lane mask with wave-uniform (scalar) weights; a wave that holds one side skips the other pass
@@ -896,25 +863,16 @@ gnn_bp4_stream_kernel(GraphDev g, GnnBp4Dev w, Args a)
 #pragma unroll
                 for (int i = 0; i < DP; ++i) { feat[i] = mean[i]; feat[DP + i] = own[i]; }
             }
-            feat[2 * DP] = f2{(it >= 0) ? hlog[c] * ssg[c] : 0.0f, 0.0f};  // (:417-418)
+            feat[2 * DP] = f2{(it >= 0) ? f.hlog[c] * ssg[c] : 0.0f, 0.0f};  // (:417-418)
             f2 nh[DP];
 #pragma unroll 1
             for (int ss = 0; ss < 2; ++ss)
                 if (s == ss) mlp_stream<2 * D + 1>(feat, pick_mlp(w.cn_embed[0], w.cn_embed[1], __builtin_amdgcn_readfirstlane(ss)), nh);
-            store_row20(hc + (size_t)c * D, nh);
+            store_row20(f.hc + (size_t)c * D, nh);
         }
         __syncthreads();
     }
-    for (int v = tid; v < n; v += T) {  // make_hard_decision (:359-367)
-        const float X = llr[v], Y = llr[n + v], Z = llr[2 * n + v];
-        int d = 0;
-        float best = 0.0f;
-        if (X < best) { best = X; d = 1; }
-        if (Z < best) { best = Z; d = 2; }
-        if (Y < best) { best = Y; d = 3; }
-        a.x_hat[(size_t)b * n + v] = (uint8_t)(d & 1);
-        a.z_hat[(size_t)b * n + v] = (uint8_t)(d >> 1);
-    }
+    hard_decision(a, f, n, b, tid, T);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -958,38 +916,15 @@ __device__ __forceinline__ void gg_run(const GnnBp4GenDev& w, int q, const float
     }
 }
 
-__device__ __forceinline__ void gg_reduce(float* acc, const float* msg, int D, bool first, int op)
-{
-    for (int i = 0; i < D; ++i) {
-        const float m = msg[i];
-        float r;
-        if (first) r = m;
-        else if (op == FGNN_REDUCE_MAX) r = FG_MAX(acc[i], m);
-        else if (op == FGNN_REDUCE_MIN) r = FG_MIN(acc[i], m);
-        else r = acc[i] + m;
-        acc[i] = r;
-    }
-}
-
 __global__ void __launch_bounds__(256) gnn_bp4_general_kernel(GraphDev g, GnnBp4GenDev w, Args a)
 {
     FG_LOG_TAB_SETUP();
     extern __shared__ float lds[];
     const int b = blockIdx.x, tid = threadIdx.x, T = blockDim.x;
     const int n = g.n, mx = g.m_x, m = g.m, D = w.D, An = w.An, Am = w.Am;
-    float* lx = lds;
-    float* lz = lx + n;
-    float* hlog = lz + n;
-    float* hv = a.work + (size_t)b * (size_t)(n + m) * D;
-    float* hc = hv + (size_t)n * D;
-    const uint8_t* sx = a.synd_x + (size_t)b * mx;
-    const uint8_t* sz = a.synd_z + (size_t)b * g.m_z;
-    const int rxp = g.m_z + g.rows[5], rzp = g.m_x + g.rows[4];
-    for (int i = tid; i < n * D; i += T) hv[i] = 1.0f;  // (:396)
-    for (int i = tid; i < m * D; i += T) hc[i] = 0.0f;  // (:392-393)
-    for (int c = tid; c < m; c += T) hlog[c] = 0.0f;
+    const Frame f = frame_of(g, a, b, D, lds);
+    frame_init(g, f, D, nullptr, tid, T);
     __syncthreads();
-    float* llr = a.llr_out + (size_t)b * 3 * n;
     float feat[GG_MAXW], msg[GG_MAXD], bufA[GG_MAXW], bufB[GG_MAXW], acc[2][GG_MAXD];
     for (int it = -1; it < a.num_iter; ++it) {
         if (it >= 0) {
@@ -1001,12 +936,12 @@ __global__ void __launch_bounds__(256) gnn_bp4_general_kernel(GraphDev g, GnnBp4
                     for (int i = 0; i < D; ++i) acc[s][i] = 0.0f;
                     for (int e = e0; e < e1; ++e) {
                         const int c = g.vchk[e];
-                        const float* src = hc + (size_t)((s ? mx : 0) + c) * D;
-                        for (int i = 0; i < D; ++i) { feat[i] = src[i]; feat[D + i] = hv[(size_t)v * D + i]; }
+                        const float* src = f.hc + (size_t)((s ? mx : 0) + c) * D;
+                        for (int i = 0; i < D; ++i) { feat[i] = src[i]; feat[D + i] = f.hv[(size_t)v * D + i]; }
                         const float* at = w.vn_msga[s] + (size_t)(e - (s ? g.E_x : 0)) * Am;
                         for (int i = 0; i < Am; ++i) feat[2 * D + i] = at[i];
                         gg_run(w, 4 + s, feat, msg, bufA, bufB);
-                        const float sg = ((s ? sz[c] : sx[c]) & 1) ? -1.0f : 1.0f;
+                        const float sg = synd_sign(s ? f.sz[c] : f.sx[c]);
                         for (int i = 0; i < D; ++i) msg[i] = msg[i] * sg;
                         gg_reduce(acc[s], msg, D, e == e0, w.rop);
                     }
@@ -1017,11 +952,11 @@ __global__ void __launch_bounds__(256) gnn_bp4_general_kernel(GraphDev g, GnnBp4
                 }
                 for (int i = 0; i < D; ++i) { feat[i] = acc[0][i]; feat[D + i] = acc[1][i]; }
                 for (int i = 0; i < An; ++i) feat[2 * D + i] = w.vn_node[(size_t)v * An + i];
-                for (int i = 0; i < D; ++i) feat[2 * D + An + i] = hv[(size_t)v * D + i];
+                for (int i = 0; i < D; ++i) feat[2 * D + An + i] = f.hv[(size_t)v * D + i];
                 gg_run(w, 6, feat, msg, bufA, bufB);
                 float Lv[3] = {0.0f, 0.0f, 0.0f};
                 for (int k = 0; k < D; ++k) {
-                    hv[(size_t)v * D + k] = msg[k];
+                    f.hv[(size_t)v * D + k] = msg[k];
                     Lv[0] = FG_FMA(msg[k], w.winv[k * 3 + 0], Lv[0]);
                     Lv[1] = FG_FMA(msg[k], w.winv[k * 3 + 1], Lv[1]);
                     Lv[2] = FG_FMA(msg[k], w.winv[k * 3 + 2], Lv[2]);
@@ -1031,28 +966,10 @@ __global__ void __launch_bounds__(256) gnn_bp4_general_kernel(GraphDev g, GnnBp4
                     Lv[1] = Lv[1] + w.binv[1];
                     Lv[2] = Lv[2] + w.binv[2];
                 }
-                llr[v] = Lv[0];
-                llr[n + v] = Lv[1];
-                llr[2 * n + v] = Lv[2];
-                lz[v] = fg_softplus(-Lv[0]) - fg_lse2(-Lv[2], -Lv[1]);
-                lx[v] = fg_softplus(-Lv[2]) - fg_lse2(-Lv[0], -Lv[1]);
+                store_llrs(f, n, v, Lv[0], Lv[1], Lv[2]);
             }
             __syncthreads();
-            float* xl = a.xlog_all ? a.xlog_all + ((size_t)it * a.B + b) * rxp : nullptr;
-            float* zl = a.zlog_all ? a.zlog_all + ((size_t)it * a.B + b) * rzp : nullptr;
-            for (int c = tid; c < m; c += T) {
-                const int p0 = g.cptr[c];
-                const float vq = logit_row_gnn(c < mx ? lz : lx, g.cvn + p0, g.cptr[c + 1] - p0);
-                hlog[c] = vq;
-                if (c < mx) { if (zl) zl[c] = vq; }
-                else if (xl) xl[c - mx] = vq;
-            }
-            if (xl)
-                for (int r = tid; r < g.rows[5]; r += T)
-                    xl[g.m_z + r] = logit_row_gnn(lx, g.rcol[5] + g.rptr[5][r], g.rptr[5][r + 1] - g.rptr[5][r]);
-            if (zl)
-                for (int r = tid; r < g.rows[4]; r += T)
-                    zl[g.m_x + r] = logit_row_gnn(lz, g.rcol[4] + g.rptr[4][r], g.rptr[4][r + 1] - g.rptr[4][r]);
+            soft_syndromes(g, a, f, b, it, tid, T);
             __syncthreads();
             if (it == a.num_iter - 1) break;  // (:414-415)
         }
@@ -1060,10 +977,10 @@ __global__ void __launch_bounds__(256) gnn_bp4_general_kernel(GraphDev g, GnnBp4
         for (int c = tid; c < m; c += T) {
             const int s = c >= mx;
             const int p0 = g.cptr[c], p1 = g.cptr[c + 1];
-            float* hto = hc + (size_t)c * D;
+            float* hto = f.hc + (size_t)c * D;
             for (int i = 0; i < D; ++i) acc[0][i] = 0.0f;
             for (int jx = p0; jx < p1; ++jx) {
-                const float* src = hv + (size_t)g.cvn[jx] * D;
+                const float* src = f.hv + (size_t)g.cvn[jx] * D;
                 for (int i = 0; i < D; ++i) { feat[i] = src[i]; feat[D + i] = hto[i]; }
                 const float* at = w.cn_msga[s] + (size_t)(jx - (s ? g.E_x : 0)) * Am;
                 for (int i = 0; i < Am; ++i) feat[2 * D + i] = at[i];
@@ -1074,8 +991,7 @@ __global__ void __launch_bounds__(256) gnn_bp4_general_kernel(GraphDev g, GnnBp4
                 const float fd = (float)(p1 - p0);
                 for (int i = 0; i < D; ++i) acc[0][i] = acc[0][i] / fd;
             }
-            const unsigned sb = (s ? sz[c - mx] : sx[c]) & 1;
-            const float lg = (it >= 0) ? hlog[c] * (sb ? -1.0f : 1.0f) : 0.0f;  // (:417-418)
+            const float lg = (it >= 0) ? f.hlog[c] * synd_sign(s ? f.sz[c - mx] : f.sx[c]) : 0.0f;  // (:417-418)
             for (int i = 0; i < D; ++i) feat[i] = acc[0][i];
             for (int i = 0; i < An; ++i) feat[D + i] = w.cn_node[s][(size_t)(c - (s ? mx : 0)) * An + i];
             for (int i = 0; i < D; ++i) feat[D + An + i] = hto[i];
@@ -1085,16 +1001,7 @@ __global__ void __launch_bounds__(256) gnn_bp4_general_kernel(GraphDev g, GnnBp4
         }
         __syncthreads();
     }
-    for (int v = tid; v < n; v += T) {  // make_hard_decision (:359-367)
-        const float X = llr[v], Y = llr[n + v], Z = llr[2 * n + v];
-        int d = 0;
-        float best = 0.0f;
-        if (X < best) { best = X; d = 1; }
-        if (Z < best) { best = Z; d = 2; }
-        if (Y < best) { best = Y; d = 3; }
-        a.x_hat[(size_t)b * n + v] = (uint8_t)(d & 1);
-        a.z_hat[(size_t)b * n + v] = (uint8_t)(d >> 1);
-    }
+    hard_decision(a, f, n, b, tid, T);
 }
 
 }  // namespace
@@ -1146,48 +1053,21 @@ extern "C" int fgnn_gnnbp4_weights_create(const float* const host_arrays[30], in
     // per-lane MFMA operand tables
     std::vector<float> T;
     int tab_start[7], tab_inv;
-    auto entry = [&]() { size_t e = T.size() / 64; T.resize(T.size() + 64, 0.0f); return e; };
+    auto entry = [&]() { T.resize(T.size() + 64, 0.0f); return &T[T.size() - 64]; };
     for (int qm = 0; qm < 7; ++qm) {
         const float* const* a = host_arrays + 4 * qm;
         const int S1 = (nin[qm] + 3) / 4;
         tab_start[qm] = (int)(T.size() / 64);
         for (int t = 0; t < 3; ++t)
-            for (int st = 0; st < S1; ++st) {
-                size_t e = entry();
-                for (int lane = 0; lane < 64; ++lane) {
-                    const int unit = mfma_unit(lane, t), k = 4 * st + (lane >> 4);
-                    T[e * 64 + lane] = (unit < H && k < nin[qm]) ? a[0][(size_t)k * H + unit] : 0.0f;
-                }
-            }
-        for (int st = 0; st < 10; ++st) {
-            size_t e = entry();
-            for (int lane = 0; lane < 64; ++lane) T[e * 64 + lane] = a[1][4 * st + (lane >> 4)];
-        }
+            for (int st = 0; st < S1; ++st) mfma_fill_w1(entry(), a[0], nin[qm], H, t, st);
+        for (int st = 0; st < 10; ++st) mfma_fill_b1(entry(), a[1], st);
         for (int u = 0; u < 2; ++u)
-            for (int st = 0; st < 10; ++st) {
-                size_t e = entry();
-                for (int lane = 0; lane < 64; ++lane) {
-                    const int mu = mfma_w2_col(lane, u);
-                    T[e * 64 + lane] = mu >= 0 ? a[2][(size_t)(4 * st + (lane >> 4)) * D + mu] : 0.0f;
-                }
-            }
-        for (int i = 0; i < 5; ++i) {
-            size_t e = entry();
-            for (int lane = 0; lane < 64; ++lane) T[e * 64 + lane] = a[3][mfma_b2_row(lane, i)];
-        }
+            for (int st = 0; st < 10; ++st) mfma_fill_w2(entry(), a[2], D, u, st);
+        for (int i = 0; i < 5; ++i) mfma_fill_b2(entry(), a[3], i);
     }
     tab_inv = (int)(T.size() / 64);
-    for (int st = 0; st < 5; ++st) {
-        size_t e = entry();
-        for (int lane = 0; lane < 64; ++lane) {
-            const int rho = lane & 15, kk = lane >> 4;
-            T[e * 64 + lane] = rho < 3 ? host_arrays[28][(size_t)(4 * st + kk) * 3 + rho] : 0.0f;
-        }
-    }
-    for (int r = 0; r < 3; ++r) {
-        size_t e = entry();
-        for (int lane = 0; lane < 64; ++lane) T[e * 64 + lane] = host_arrays[29][r];
-    }
+    for (int st = 0; st < 5; ++st) mfma_fill_wout(entry(), host_arrays[28], st);
+    for (int r = 0; r < 3; ++r) std::fill_n(entry(), 64, host_arrays[29][r]);
     const size_t otab = push(T.size());
     std::memcpy(&h[otab], T.data(), T.size() * sizeof(float));
 
@@ -1334,24 +1214,16 @@ extern "C" int fgnn_gnnbp4_decode(const fgnn_graph* g, const fgnn_gnnbp4_weights
     if (!synd_x || !synd_z || !x_hat || !z_hat || !llr_out) return fgnn_fail(FGNN_ERR_ARG, "required buffer is NULL");
     if (!workspace || ws_bytes < fgnn_gnnbp4_weights_workspace_bytes(g, w, B)) return fgnn_fail(FGNN_ERR_ARG, "workspace too small");
     FGNN_DEVICE_GUARD(g->device);
-    Args a;
-    a.B = B;
-    a.num_iter = num_iter;
-    a.synd_x = synd_x;
-    a.synd_z = synd_z;
-    a.x_hat = x_hat;
-    a.z_hat = z_hat;
-    a.llr_out = llr_out;
-    a.xlog_all = x_logit_all;
-    a.zlog_all = z_logit_all;
-    a.work = static_cast<float*>(workspace);
+    const Args a{B, num_iter, synd_x, synd_z, x_hat, z_hat, llr_out, x_logit_all, z_logit_all, static_cast<float*>(workspace)};
     const size_t lds_bytes = (size_t)(2 * g->d.n + g->d.m) * sizeof(float);
     fgnn_prof_scope prof(g, static_cast<hipStream_t>(stream));
-    if (w->general) {
-        const int rc = fgnn_launch(gnn_bp4_general_kernel, dim3(B), dim3(256), lds_bytes, static_cast<hipStream_t>(stream), g->d, w->gen, a);
+    // one workgroup per codeword; the profile tag is recorded when the launch succeeded
+    auto launch = [&](auto kern, int threads, size_t lds, const auto& wdev, auto... extra) {
+        const int rc = fgnn_launch(kern, dim3(B), dim3(threads), lds, static_cast<hipStream_t>(stream), g->d, wdev, a, extra...);
         if (rc == FGNN_OK) prof.done(FGNN_PROF_TAG_GNNBP4, B);
         return rc;
-    }
+    };
+    if (w->general) return launch(gnn_bp4_general_kernel, 256, lds_bytes, w->gen);
     // FGNN_OPT_GNN_STREAM for GNN_BP4 on a (3,3,6)-regular graph: only the explicit value 2 ("always") runs the streaming packed-FMA kernel.
     // Measured in round 4 (profiles/r4_gnnbp4_stream_ab.txt, r4_gnnbp4_stream_pmc_summary.txt): bit-equal to the MFMA-tile kernel in both
     // associations, and slower — 180 ms against 134 ms per 16 384 x 10 in the factored order, 212 against 193 in the literal one.  The
@@ -1371,9 +1243,7 @@ extern "C" int fgnn_gnnbp4_decode(const fgnn_graph* g, const fgnn_gnnbp4_weights
             for (MlpDev* q : {&wd.cn_msg[0], &wd.cn_msg[1], &wd.cn_embed[0], &wd.cn_embed[1], &wd.vn_msg[1], &wd.vn_embed}) *q = wd.vn_msg[0];
         }
 #endif
-        const int rc = fgnn_launch(kern, dim3(B), dim3(256), lds_s, static_cast<hipStream_t>(stream), g->d, wd, a);
-        if (rc == FGNN_OK) prof.done(FGNN_PROF_TAG_GNNBP4, B);
-        return rc;
+        return launch(kern, 256, lds_s, wd);
     }
     if (g->d.dvx == 3 && g->d.dvz == 3 && g->d.dc == 6 && !g->force_generic) {
         const int cn_entries = w->d.tab_vn_msg[0] - w->d.tab_cn_msg[0], vn_entries = w->d.tab_inv + 8 - w->d.tab_vn_msg[0];
@@ -1383,12 +1253,7 @@ extern "C" int fgnn_gnnbp4_decode(const fgnn_graph* g, const fgnn_gnnbp4_weights
         const size_t lds2 = fixed + (size_t)tab_floats * sizeof(float);
         auto kern = g->gnn_factored ? gnn_bp4_mfma_kernel<3, 6, true> : gnn_bp4_mfma_kernel<3, 6, false>;
         if (lds2 > FGNN_LDS_BUDGET) return fgnn_fail(FGNN_ERR_ARG, "code too large for the GNN_BP4 MFMA kernel");
-        const int rc = fgnn_launch(kern, dim3(B), dim3(FGNN_GNNBP4_THREADS), lds2, static_cast<hipStream_t>(stream), g->d, w->d, a, tab_floats, resident);
-        if (rc == FGNN_OK) prof.done(FGNN_PROF_TAG_GNNBP4, B);
-        return rc;
+        return launch(kern, FGNN_GNNBP4_THREADS, lds2, w->d, tab_floats, resident);
     }
-    const int rc = fgnn_launch(g->gnn_factored ? gnn_bp4_kernel<true> : gnn_bp4_kernel<false>, dim3(B), dim3(256), lds_bytes,
-                               static_cast<hipStream_t>(stream), g->d, w->d, a);
-    if (rc == FGNN_OK) prof.done(FGNN_PROF_TAG_GNNBP4, B);
-    return rc;
+    return launch(g->gnn_factored ? gnn_bp4_kernel<true> : gnn_bp4_kernel<false>, 256, lds_bytes, w->d);
 }

@@ -106,6 +106,17 @@ def llr_const(p0):
     return float(np.log(np.float32(3.0) * (np.float32(1.0) - p0) / p0, dtype=np.float32))
 
 
+def gnnbp4_weights(seed):
+    """Seeded GNN_BP4 weights in the shapes of GNNBP4_SHAPES: glorot-uniform kernels, biases uniform in (-0.6, 0.6)."""
+    from feedback_gnn_amd.graph import GNNBP4_SHAPES
+    rng = np.random.RandomState(seed)
+    w = []
+    for shp in GNNBP4_SHAPES:
+        lim = 0.6 if len(shp) == 1 else np.sqrt(6.0 / (shp[0] + shp[1]))
+        w.append(rng.uniform(-lim, lim, size=shp).astype(np.float32))
+    return w
+
+
 def golden_codes():
     out = dict(np.load(os.path.join(GOLDEN, "codes.npz")))
     out.update(np.load(os.path.join(GOLDEN, "overcomplete.npz")))

@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import LIBRARY_GNN_FACTORED, WEIGHTS_882, WEIGHTS_1270, code, gpu_graph, llr_const, oracle_library_forms, to_gpu
+from helpers import LIBRARY_GNN_FACTORED, WEIGHTS_882, WEIGHTS_1270, code, gnnbp4_weights, gpu_graph, llr_const, oracle_library_forms, to_gpu
 
 pytestmark = pytest.mark.gpu
 
@@ -225,12 +225,8 @@ def test_gnn_bp4_both_orders_bit_exact(name, B, iters):
     the first Dense once per node and side; ONE last Dense on the signed sum of the hidden activations) — MFMA kernel and streaming
     packed-FMA kernel (regular graphs), runtime-degree VALU kernel (any graph), against the oracle in the same order, exactly; the two
     orders agree to rounding."""
-    from feedback_gnn_amd.graph import GNNBP4_SHAPES, GnnBp4Weights
-    rng = np.random.RandomState(11)
-    w = []
-    for shp in GNNBP4_SHAPES:
-        lim = 0.6 if len(shp) == 1 else np.sqrt(6.0 / (shp[0] + shp[1]))
-        w.append(rng.uniform(-lim, lim, size=shp).astype(np.float32))
+    from feedback_gnn_amd.graph import GnnBp4Weights
+    w = gnnbp4_weights(11)
     og0 = oracle_library_forms(name)
     ex, ez = og0.pauli_noise(SEED, 0.05, 40, B)
     sx, sz = og0.syndrome(ex, ez)
@@ -264,13 +260,9 @@ def test_gnn_bp4_streaming_kernel_equals_the_mfma_kernel_on_a_chip_filling_launc
     """FGNN_OPT_GNN_STREAM = 2 runs GNN_BP4 on the streaming packed-FMA kernel (one lane per node, v_pk_fma_f32 with scalar weight
     pairs); the default keeps the MFMA tiles, which are faster (profiles/r4_gnnbp4_stream_ab.txt).  The same float operations in the
     same order: a launch of 1 024 codewords must give the same bits on either kernel, and both equal the oracle on a sample."""
-    from feedback_gnn_amd.graph import GNNBP4_SHAPES, GnnBp4Weights
+    from feedback_gnn_amd.graph import GnnBp4Weights
     name, B, iters = "ghp882", 1024, 3
-    rng = np.random.RandomState(5)
-    w = []
-    for shp in GNNBP4_SHAPES:
-        lim = 0.6 if len(shp) == 1 else np.sqrt(6.0 / (shp[0] + shp[1]))
-        w.append(rng.uniform(-lim, lim, size=shp).astype(np.float32))
+    w = gnnbp4_weights(5)
     og, gg = oracle_library_forms(name), gpu_graph(name)
     assert gg.gnn_stream is True  # the library default
     ex, ez = gg.pauli_noise(SEED, 0.05, 0, B)

@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import (LIBRARY_BP4_SHARED_LSE, LIBRARY_GNN_FACTORED, WEIGHTS_882, WEIGHTS_1270, code, gpu_graph, llr_const,
+from helpers import (LIBRARY_BP4_SHARED_LSE, LIBRARY_GNN_FACTORED, WEIGHTS_882, WEIGHTS_1270, code, gnnbp4_weights, gpu_graph, llr_const,
                      oracle_library_forms, to_gpu)
 
 pytestmark = pytest.mark.gpu
@@ -370,16 +370,6 @@ def test_exact_shortcuts_on_runtime_degree_graphs(name, p, iters, factor, launch
         gg.set_fixed_point_exit(True)
 
 
-def _gnnbp4_weights(seed=11):
-    from feedback_gnn_amd.graph import GNNBP4_SHAPES
-    rng = np.random.RandomState(seed)
-    w = []
-    for shp in GNNBP4_SHAPES:
-        lim = 0.6 if len(shp) == 1 else np.sqrt(6.0 / (shp[0] + shp[1]))
-        w.append(rng.uniform(-lim, lim, size=shp).astype(np.float32))
-    return w
-
-
 @pytest.mark.parametrize("name,B,iters", [("gb48", 21, 5), ("rsurf5", 9, 3), ("ghp882", 6, 4), ("ghp1270", 5, 10)])
 def test_gnn_bp4_bit_exact(name, B, iters):
     """GNN_BP4 (BASELINE configs[4]) kernel vs the oracle: embeddings-derived LLRs, soft syndromes of every iteration
@@ -387,7 +377,7 @@ def test_gnn_bp4_bit_exact(name, B, iters):
     from feedback_gnn_amd.graph import GnnBp4Weights
     og, gg = oracle_library_forms(name), gpu_graph(name)
     (ex, ez, sx, sz), (gx, gz, tx, tz) = _noise_and_syndromes(name, 0.05, B)
-    w = _gnnbp4_weights()
+    w = gnnbp4_weights(11)
     o = og.gnn_bp4(w, sx, sz, iters)
     g = gg.gnn_bp4_decode(GnnBp4Weights(w, gg.device), tx, tz, iters)
     for k in ("llr", "x_logit_all", "z_logit_all", "x_hat", "z_hat"):
@@ -400,7 +390,7 @@ def test_gnn_bp4_class_contract():
     c = code("gb48")
     dec = F.GNN_BP4(c, num_embed_dims=20, num_msg_dims=20, num_hidden_units=40, num_mlp_layers=2, num_iter=3, reduce_op="mean",
                     activation="tanh", use_bias=True)
-    w = _gnnbp4_weights(3)
+    w = gnnbp4_weights(3)
     dec.set_weights(w)
     og = oracle_library_forms("gb48")
     ex, ez = og.pauli_noise(SEED, 0.05, 0, 7)
@@ -492,7 +482,7 @@ def test_gnn_bp4_mfma_and_valu_kernels_agree():
     name, B, iters = "ghp882", 5, 3
     og, gg = oracle_library_forms(name), gpu_graph(name)
     (ex, ez, sx, sz), (gx, gz, tx, tz) = _noise_and_syndromes(name, 0.05, B, first=9)
-    w = _gnnbp4_weights(21)
+    w = gnnbp4_weights(21)
     o = og.gnn_bp4(w, sx, sz, iters)
     gw = GnnBp4Weights(w, gg.device)
     a = gg.gnn_bp4_decode(gw, tx, tz, iters)
@@ -789,7 +779,7 @@ def test_config4_full_shard_gnn_bp4_properties_and_strided_oracle_check():
     from feedback_gnn_amd.graph import GnnBp4Weights
     name, B, iters = "ghp1270", 16384, 10
     og, gg = oracle_library_forms(name), gpu_graph(name)
-    w = _gnnbp4_weights(5)
+    w = gnnbp4_weights(5)
     gw = GnnBp4Weights(w, gg.device)
     ex, ez = gg.pauli_noise(SEED, 0.05, 7 * B, B)
     sx, sz = gg.syndrome(ex, ez)

@@ -10,7 +10,7 @@ import pytest
 import torch
 
 from feedback_gnn_amd.weights_io import read_weight_list
-from helpers import WEIGHTS_1270, WEIGHTS_882, code, gpu_graph, llr_const
+from helpers import WEIGHTS_1270, WEIGHTS_882, code, gnnbp4_weights, gpu_graph, llr_const
 from oracle import numpy_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -126,12 +126,8 @@ def test_gpu_feedback_gnn_vs_numpy_restatement(name, wfile):
 @pytest.mark.parametrize("name", ["gb48", "rsurf5"])
 def test_gpu_gnn_bp4_vs_numpy_restatement(name):
     """GNN_BP4 (gnn.py:383-423, repaired arity): HIP kernel vs the NumPy matmul restatement, random weights."""
-    from feedback_gnn_amd.graph import GNNBP4_SHAPES, GnnBp4Weights
-    rng = np.random.RandomState(11)
-    w = []
-    for shp in GNNBP4_SHAPES:
-        lim = 0.6 if len(shp) == 1 else np.sqrt(6.0 / (shp[0] + shp[1]))
-        w.append(rng.uniform(-lim, lim, size=shp).astype(np.float32))
+    from feedback_gnn_amd.graph import GnnBp4Weights
+    w = gnnbp4_weights(11)
     g, c, sx, sz, nsx, nsz = _gpu_case(name, 0.05, 12)
     o = _np(g.gnn_bp4_decode(GnnBp4Weights(w, g.device), sx, sz, 4))
     r = R.gnn_bp4(c, w, nsx, nsz, 4)

@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 
 from feedback_gnn_amd.weights_io import read_weight_list
-from helpers import WEIGHTS_1270, WEIGHTS_882, code, llr_const, oracle_library_forms
+from helpers import WEIGHTS_1270, WEIGHTS_882, code, gnnbp4_weights, llr_const, oracle_library_forms
 from oracle import numpy_ref as R
 
 SEED = 0x5EED
@@ -192,23 +192,13 @@ def test_rotated_surface_flagged_vs_bler():
     assert abs(bl - 0.3078) < 4 * np.sqrt(0.3078 * 0.6922 / B) * np.sqrt(2), bl
 
 
-def _gnnbp4_weights(seed=11):
-    from feedback_gnn_amd.graph import GNNBP4_SHAPES
-    rng = np.random.RandomState(seed)
-    w = []
-    for shp in GNNBP4_SHAPES:
-        lim = 0.6 if len(shp) == 1 else np.sqrt(6.0 / (shp[0] + shp[1]))
-        w.append(rng.uniform(-lim, lim, size=shp).astype(np.float32))
-    return w
-
-
 @pytest.mark.parametrize("name", ["gb48", "rsurf5"])
 def test_gnn_bp4_oracle_vs_numpy_restatement(name):
     """GNN_BP4 (gnn.py:383-423, repaired): C oracle (fmaf chains, polynomial tanh) vs NumPy matmul restatement."""
     g = oracle_library_forms(name)
     ex, ez = g.pauli_noise(SEED, 0.05, 0, 12)
     sx, sz = g.syndrome(ex, ez)
-    w = _gnnbp4_weights()
+    w = gnnbp4_weights(11)
     o = g.gnn_bp4(w, sx, sz, 4)
     r = R.gnn_bp4(code(name), w, sx, sz, 4)
     assert np.abs(o["llr"] - r["llr"]).max() <= 2e-4
