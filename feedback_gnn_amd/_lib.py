@@ -100,6 +100,8 @@ _SIGNATURES = {
                                   C.c_void_p, C.c_void_p]),
     "fgnn_relay_decode": (C.c_int, [C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float,
                                     C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fgnn_relay4_decode": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float,
+                                     C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "fgnn_bsc_noise": (C.c_int, [C.c_uint64, C.c_float, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "fgnn_residual_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 4),
     "fgnn_graph_set_basis": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),

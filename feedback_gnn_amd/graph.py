@@ -779,6 +779,37 @@ class TannerGraph:
                                            _stream(self.device)))
         return hard, stats
 
+    def relay4_decode(self, synd_x, synd_z, gamma, pre_iter, leg_iter, stop_nconv, factor=1.0, llr_ch=None, llr_const=0.0,
+                      cn_type="minsum", B=None):
+        """Relay-BP4 on both graphs (`fgnn_relay4_decode`): `gamma` [num_legs, n] float32 on the device, one row of memory strengths per
+        leg; `llr_ch` [B, 3, n] or one `llr_const` for all three LLRs of every qubit; a syndrome that is None is all-zero.  Returns
+        `(x_hat [B,n] uint8, z_hat [B,n] uint8, stats [B,4] int32 = found, weight, leg, k)`."""
+        if cn_type not in CN_TYPES:
+            raise ValueError("Unknown node type.")
+        for s in (synd_x, synd_z, llr_ch):
+            if s is not None:
+                B = int(s.shape[0])
+        if B is None:
+            raise ValueError("B is needed when neither syndromes nor llr_ch are given")
+        if synd_x is not None:
+            synd_x = self._chk(synd_x, (B, self.m_x), torch.uint8, "synd_x")
+        if synd_z is not None:
+            synd_z = self._chk(synd_z, (B, self.m_z), torch.uint8, "synd_z")
+        if llr_ch is not None:
+            llr_ch = self._chk(llr_ch, (B, 3, self.n), torch.float32, "llr_ch")
+        if gamma is not None:
+            if gamma.dim() != 2 or gamma.shape[0] < 1:
+                raise ValueError("gamma must have shape [num_legs, n]")
+            gamma = self._chk(gamma, (int(gamma.shape[0]), self.n), torch.float32, "gamma")
+        num_legs = int(gamma.shape[0]) if gamma is not None else 1
+        xh = self._new((B, self.n), torch.uint8)
+        zh = self._new((B, self.n), torch.uint8)
+        stats = self._new((B, 4), torch.int32)
+        check(_lib.lib().fgnn_relay4_decode(self.handle, CN_TYPES[cn_type], float(factor), int(pre_iter), num_legs, int(leg_iter),
+                                            int(stop_nconv), _ptr(gamma), _ptr(llr_ch), float(llr_const), _ptr(synd_x), _ptr(synd_z), B,
+                                            _ptr(xh), _ptr(zh), _ptr(stats), _stream(self.device)))
+        return xh, zh, stats
+
     def bsc_noise(self, seed, p, first_sample, B):
         e = self._new((B, self.n), torch.uint8)
         with torch.cuda.device(self.device):

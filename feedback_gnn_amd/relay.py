@@ -3,11 +3,35 @@
 Mueller et al., "Improved belief propagation is sufficient for real-time decoding of quantum memories" (2025).  The algorithm is
 stated at `fgnn_relay_decode` in include/fgnn.h; the kernel is feedback_gnn_amd/csrc/fgnn_relay.hip.  It needs no training and no
 matrix inversion and runs on any binary check matrix that fits the LDS-resident layout.
+
+Relay-BP4 (`RelayBP4Decoder`, `BP4_Relay_Model`) is the same scheme on the quaternary decoder: the memory term on each of a qubit's
+three LLRs, both Tanner graphs of a CSS code in one kernel (`fgnn_relay4_decode`, feedback_gnn_amd/csrc/fgnn_relay4.hip).
 """
 import numpy as np
 import torch
 
 from .decoding import _binary_graph
+
+
+def _relay_schedule(pre_iter, num_sets, set_max_iter, gamma_dist_interval, stop_nconv):
+    """The validation both decoder classes share; returns the interval as floats."""
+    for name, val in (("pre_iter", pre_iter), ("set_max_iter", set_max_iter), ("stop_nconv", stop_nconv)):
+        if not isinstance(val, (int, np.integer)) or val < 1:
+            raise ValueError(f"{name} must be a positive integer")
+    if not isinstance(num_sets, (int, np.integer)) or num_sets < 0:
+        raise ValueError("num_sets cannot be negative")
+    lo, hi = (float(x) for x in gamma_dist_interval)
+    if not lo <= hi:
+        raise ValueError("gamma_dist_interval must be (low, high) with low <= high")
+    return lo, hi
+
+
+def _draw_gamma(gamma0, num_sets, n, lo, hi, seed):
+    """[1 + num_sets, n] float32: gamma0 on the first leg, then uniform draws of np.random.default_rng(seed)."""
+    gamma = np.empty((1 + num_sets, n), np.float32)
+    gamma[0] = np.float32(gamma0)
+    gamma[1:] = np.random.default_rng(seed).uniform(lo, hi, size=(num_sets, n)).astype(np.float32)
+    return gamma
 
 
 class RelayBPDecoder:
@@ -26,25 +50,14 @@ class RelayBPDecoder:
         pcm = np.asarray(pcm.toarray() if hasattr(pcm, "toarray") else pcm)
         if not np.array_equal(pcm, pcm.astype(bool)):
             raise AssertionError('PC matrix must be binary.')
-        for name, val in (("pre_iter", pre_iter), ("set_max_iter", set_max_iter), ("stop_nconv", stop_nconv)):
-            if not isinstance(val, (int, np.integer)) or val < 1:
-                raise ValueError(f"{name} must be a positive integer")
-        if not isinstance(num_sets, (int, np.integer)) or num_sets < 0:
-            raise ValueError("num_sets cannot be negative")
-        lo, hi = (float(x) for x in gamma_dist_interval)
-        if not lo <= hi:
-            raise ValueError("gamma_dist_interval must be (low, high) with low <= high")
+        lo, hi = _relay_schedule(pre_iter, num_sets, set_max_iter, gamma_dist_interval, stop_nconv)
         self._pcm = pcm
         self.pre_iter, self.num_sets, self.set_max_iter, self.stop_nconv = int(pre_iter), int(num_sets), int(set_max_iter), int(stop_nconv)
         self.gamma0, self.gamma_dist_interval, self.seed = float(gamma0), (lo, hi), int(seed)
         self.normalization_factor = float(normalization_factor)
         self.graph = graph if graph is not None else _binary_graph(pcm, None, device)
         self._num_vns, self._num_cns = self.graph.n, self.graph.m_x
-        rng = np.random.default_rng(self.seed)
-        gamma = np.empty((1 + self.num_sets, self._num_vns), np.float32)
-        gamma[0] = np.float32(self.gamma0)
-        gamma[1:] = rng.uniform(lo, hi, size=(self.num_sets, self._num_vns)).astype(np.float32)
-        self.gamma = gamma
+        self.gamma = _draw_gamma(self.gamma0, self.num_sets, self._num_vns, lo, hi, self.seed)
         self.last_stats = None
 
     pcm = property(lambda self: self._pcm)
@@ -120,5 +133,104 @@ class BP2_Relay_Model:
         self.last_num_unsolved = int((stats[:, 0] == 0).sum().item())
         s_hat, ls_hat, _ = g.residual(noise, zeros, noise_hat, zeros, want_arrays=True)
         return s_hat[:, :g.m_z].contiguous(), ls_hat[:, :g.rows_hxp].contiguous()
+
+    call = __call__
+
+
+class RelayBP4Decoder:
+    """``RelayBP4Decoder(code, gamma0=0.125, pre_iter=80, num_sets=60, set_max_iter=60, gamma_dist_interval=(-0.24, 0.66),
+    stop_nconv=1, normalization_factor=1.0, seed=0)``: Relay-BP on the quaternary decoder.  The schedule and the memory strengths are
+    `RelayBPDecoder`'s (one strength per qubit and leg, applied to the qubit's three LLRs); every leg is min-sum BP4 on both Tanner
+    graphs of ``code``.  Decoding stops after ``stop_nconv`` solutions (estimates that reproduce both syndromes) and keeps the one of
+    lowest weight.
+
+    Call ``decoder((llr_ch[bs,3,n], syndrome_x[m_x,bs], syndrome_z[m_z,bs]))`` as ``QLDPCBPDecoder``: the result is
+    ``(x_hat, z_hat)`` [bs,n] in its dtypes (int64 and float64).  ``last_stats[bs,4]`` (int32) = solutions found, weight of the estimate
+    (sum over the qubits of rint(1024 * clipped channel LLR) of the decided Pauli), its leg and its iteration within the leg."""
+
+    def __init__(self, code, gamma0=0.125, pre_iter=80, num_sets=60, set_max_iter=60, gamma_dist_interval=(-0.24, 0.66), stop_nconv=1,
+                 normalization_factor=1.0, seed=0, device=None, graph=None):
+        lo, hi = _relay_schedule(pre_iter, num_sets, set_max_iter, gamma_dist_interval, stop_nconv)
+        self._code = code
+        self.pre_iter, self.num_sets, self.set_max_iter, self.stop_nconv = int(pre_iter), int(num_sets), int(set_max_iter), int(stop_nconv)
+        self.gamma0, self.gamma_dist_interval, self.seed = float(gamma0), (lo, hi), int(seed)
+        self.normalization_factor = float(normalization_factor)
+        if graph is None:
+            from .graph import TannerGraph
+            graph = TannerGraph(code, stage_one=False, device=device)
+        self.graph = graph
+        self._num_vns, self._num_cns_x, self._num_cns_z = self.graph.n, self.graph.m_x, self.graph.m_z
+        self.gamma = _draw_gamma(self.gamma0, self.num_sets, self._num_vns, lo, hi, self.seed)
+        self.last_stats = None
+
+    code = property(lambda self: self._code)
+    num_vns = property(lambda self: self._num_vns)
+    num_legs = property(lambda self: 1 + self.num_sets)
+    gamma = RelayBPDecoder.gamma
+
+    def decode(self, synd_x, synd_z, llr_ch=None, llr_const=0.0):
+        """Estimates and stats for syndromes [B, m_x] / [B, m_z] (uint8, device) under ``llr_ch`` [B, 3, n] or one LLR for everything."""
+        x_hat, z_hat, stats = self.graph.relay4_decode(synd_x, synd_z, self._gamma, self.pre_iter, self.set_max_iter, self.stop_nconv,
+                                                       self.normalization_factor, llr_ch=llr_ch, llr_const=llr_const)
+        self.last_stats = stats
+        return x_hat, z_hat, stats
+
+    def __call__(self, inputs):
+        g = self.graph
+        llr_ch, syndrome_x, syndrome_z = inputs
+        llr_ch = torch.as_tensor(llr_ch, device=g.device)
+        if llr_ch.dtype != torch.float32:
+            raise TypeError('Invalid input dtype.')
+        if llr_ch.shape[-1] != self._num_vns:
+            raise ValueError('Last dimension must be of length n.')
+        if llr_ch.dim() != 3 or llr_ch.shape[1] != 3:
+            raise ValueError('llr_ch must have shape [batch_size, 3, n].')
+        synd = []
+        for s, rows in ((syndrome_x, self._num_cns_x), (syndrome_z, self._num_cns_z)):
+            s = torch.as_tensor(s, device=g.device)
+            if s.dim() != 2 or s.shape[0] != rows:
+                raise ValueError(f"syndrome must have shape [{rows}, batch_size], got {tuple(s.shape)}")
+            if s.shape[1] != llr_ch.shape[0]:
+                raise ValueError('batch sizes of llr_ch and the syndromes differ.')
+            synd.append((s.to(torch.int64) & 1).to(torch.uint8).t().contiguous())
+        x_hat, z_hat, _ = self.decode(synd[0], synd[1], llr_ch=llr_ch.contiguous())
+        return x_hat.to(torch.int64), z_hat.to(torch.float64)
+
+    call = __call__
+
+
+class BP4_Relay_Model:
+    """``BP4_Relay_Model(code, relay_decoder, p0=None)``; ``model(batch_size, p)`` → ``(s_hat[bs, m_z+m_x], ls_hat[bs,
+    rows(hx_perp)+rows(hz_perp)])``, shaped like ``Sandwich_BP_GNN_Evaluation_Model``: depolarizing noise of rate ``p``, its two
+    syndromes, Relay-BP4 with the prior ``log(3(1-p0)/p0)`` (``p0=None``: of ``p`` itself).  ``s_hat`` is non-zero exactly on the samples
+    for which no solution was found.  After a call ``last_noise_x``, ``last_noise_z``, ``last_x_hat``, ``last_z_hat`` (uint8 [bs,n]),
+    ``last_stats`` (int32 [bs,4]) and ``last_num_unsolved`` describe that batch.  ``rank`` / ``world_size`` shard the sample stream."""
+
+    def __init__(self, code, relay_decoder, p0=None, *, seed=0x5EED, rank=0, world_size=1):
+        self.code, self.relay_decoder, self.p0 = code, relay_decoder, p0
+        self.graph = relay_decoder.graph
+        self.seed, self.rank, self.world_size, self._next = int(seed), int(rank), int(world_size), 0
+        self.last_noise_x = self.last_noise_z = self.last_x_hat = self.last_z_hat = self.last_stats = None
+        self.last_num_unsolved = 0
+
+    def next_sample_range(self, batch_size):
+        """``(first, last)``: the half-open range of global sample indices this rank's next batch will draw."""
+        first = self._next + self.rank * int(batch_size)
+        return first, first + int(batch_size)
+
+    def __call__(self, batch_size, ebno_db=None, **kw):
+        p = float(kw.get("p", ebno_db))
+        B, g, d = int(batch_size), self.graph, self.relay_decoder
+        first = self._next + self.rank * B
+        self._next += self.world_size * B
+        p0 = np.float32(p if self.p0 is None else self.p0)
+        llr_const = float(np.log(np.float32(3.0) * (np.float32(1.0) - p0) / p0, dtype=np.float32))
+        ex, ez = g.pauli_noise(self.seed, p, first, B)
+        sx, sz = g.syndrome(ex, ez)
+        x_hat, z_hat, stats = d.decode(sx, sz, llr_const=llr_const)
+        self.last_noise_x, self.last_noise_z, self.last_x_hat, self.last_z_hat, self.last_stats = ex, ez, x_hat, z_hat, stats
+        self.last_num_unsolved = int((stats[:, 0] == 0).sum().item())
+        s_hat, ls_hat, _ = g.residual(ex, ez, x_hat, z_hat, want_arrays=True)
+        return s_hat, ls_hat
 
     call = __call__

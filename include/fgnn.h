@@ -286,6 +286,33 @@ int fgnn_bp2_decode(const fgnn_graph* g, int cn_type, int num_iter, float normal
 int fgnn_relay_decode(const fgnn_graph* g, float normalization_factor, int pre_iter, int num_legs, int leg_iter, int stop_nconv,
                       const float* gamma, const float* llr_ch, float llr_const, const uint8_t* synd, int B, uint8_t* hard_out,
                       int32_t* stats, void* stream);
+/* Relay-BP4: Relay-BP's memory term applied to each of a qubit's three LLRs of the quaternary decoder — a chain of num_legs min-sum BP4
+ * runs ("legs") on both Tanner graphs with per-qubit memory strengths gamma [num_legs,n] (device float32, shared by the batch); every
+ * leg starts from the marginals the previous one ended with, and the lowest-weight solution met is kept.  No paper states this form.
+ * llr_ch [B,3,n] (X, Y, Z) or NULL (= llr_const for all three), synd_x [B,m_x] / synd_z [B,m_z] as fgnn_bp4_decode (NULL = all-zero).
+ * All arithmetic is float32 in the order written; sums run over a qubit's slots in ascending order from 0.0f, exactly as
+ * fgnn_bp4_decode.  Per codeword, with lam^W_v the channel LLRs (W = X, Y, Z):
+ *     q^W_v = (int32) rint(1024 * clamp(lam^W_v, -20, 20)),  q^I_v = 0;   M^W_v = lam^W_v;   found = 0
+ *     for r in 0 .. num_legs-1:   T = pre_iter if r == 0 else leg_iter;  all c->v messages = 0;  gam_v = gamma[r,v]
+ *         for k in 0 .. T:                                   (k = finished check updates of this leg)
+ *             Sx_v, Sz_v = sums of the hx / hz messages at qubit v
+ *             if k > 0:  M^X = Sz + Lam^X;  M^Z = Sx + Lam^Z;  M^Y = (Sz + Sx) + Lam^Y        (BP4's marginals, on the Lam of the previous step)
+ *                        d_v = argmin(0, M^X, M^Z, M^Y), first minimum wins (BP4's rule);  x_v = d_v & 1;  z_v = d_v >> 1
+ *                        if hz.x == synd_z and hx.z == synd_x:  w = sum_v q^{d_v}_v  (d = 1: X, 2: Z, 3: Y);  found += 1;
+ *                             if found == 1 or w < best_w: best = (x, z, w, r, k);   end this leg
+ *                        if k == T: end this leg
+ *             Lam^W_v = (1.0f - gam_v) * lam^W_v + gam_v * M^W_v   for W = X, Y, Z      (two products, then one add)
+ *             qubit update of BP4 with Lam in place of the channel LLRs, literal form (one log-sum-exp per edge; option 5 is ignored)
+ *             min-sum check update on both graphs (clip +-20, * normalization_factor)
+ *         if found == stop_nconv: stop
+ * x_hat, z_hat [B,n] = the best pair if found > 0, else the pair of the last test made (last leg, k = T); stats [B,4] (int32) = found,
+ * the weight of the output pair, its leg, its k.  pre_iter, num_legs, leg_iter, stop_nconv >= 1.  cn_type must be FGNN_CN_MINSUM
+ * (anything else: FGNN_ERR_ARG).  With gamma = 0, Lam = 1 * lam + 0 * M = lam bit for bit: one leg is then min-sum fgnn_bp4_decode
+ * that stops at its first solution.  The messages, marginals and decisions of a codeword stay in LDS for the whole launch; a graph
+ * they do not fit is refused (FGNN_ERR_ARG), there is no global-memory variant. */
+int fgnn_relay4_decode(const fgnn_graph* g, int cn_type, float normalization_factor, int pre_iter, int num_legs, int leg_iter,
+                       int stop_nconv, const float* gamma, const float* llr_ch, float llr_const, const uint8_t* synd_x,
+                       const uint8_t* synd_z, int B, uint8_t* x_hat, uint8_t* z_hat, int32_t* stats, void* stream);
 /* BinarySymmetricChannel on the all-zero word, BP_BSC_Model.call feedback_gnn.py:213-214: noise = u < p (Philox stream). */
 int fgnn_bsc_noise(uint64_t seed, float p, uint64_t first_sample, int B, int n, uint8_t* noise, void* stream);
 
