@@ -18,6 +18,12 @@
 //
 // Summation order is the canonical one of the oracle (ascending neighbour index) and every
 // float op is the one the oracle executes, so results are bit-identical to oracle/fgnn_oracle.c.
+//
+// Iteration 0 of a decode without initial messages is uniform by its launch arguments, and the degree-regular kernels — the fixed
+// dataflow included — evaluate it as such: in closed form, once per thread, with one constant channel LLR and the phi rule; with one
+// log-sum-exp per qubit and side instead of one per edge with per-qubit channel LLRs.  Argument dependent, not data dependent: the
+// operation count per codeword stays a constant, and every float that reaches a message is produced by the operations the oracle
+// executes for it (see first_closed / first_peeled in bp4_kernel).
 
 #include "fgnn_internal.h"
 #include "fgnn_math.h"
@@ -346,14 +352,26 @@ bp4_kernel(GraphDev g, BpArgs a)
     float* Lch = msg + a.lch_off;  // [3n], only when llr_ch != null
     const int n = g.n;
 
-    // Closed-form first iteration (exact; product default only): with zero initial messages and one constant channel LLR every
-    // qubit sends the same v->c value in iteration 0, so a check's six outputs differ by the syndrome sign alone.
-    const bool first_closed = OPT && REGULAR && CN_TYPE == FGNN_CN_BOXPLUS_PHI && opt_shortcut && !a.llr_ch && !a.msg_init_x &&
-                              !a.msg_init_z && a.num_iter > 0;
-    if (active && !first_closed) {
-        for (int e = lane; e < g.E_x; e += a.tpc) msg[e] = a.msg_init_x ? a.msg_init_x[(size_t)b * g.E_x + e] : 0.0f;
-        for (int e = lane; e < g.E_z; e += a.tpc)
-            msg[g.E_x + e] = a.msg_init_z ? a.msg_init_z[(size_t)b * g.E_z + e] : 0.0f;
+    // Iteration 0 of a decode that starts from zero messages repeats itself, and the LAUNCH ARGUMENTS say so (msg_init_x == msg_init_z
+    // == null: every decoder of every sandwich) — a property of the arguments, not of the data, so the fixed dataflow takes it too and
+    // its operation count per codeword stays a constant.  Degree-regular graphs, not the trace variant (trace slot 0 and tape slot 0
+    // are read from the zero messages in LDS):
+    //  - closed form (phi rule, one constant channel LLR): every qubit sends the same v->c value, so a check's outputs differ by the
+    //    syndrome sign alone — the float operations of iteration 0 once per thread instead of once per edge;
+    //  - peeled qubit phase (per-qubit channel LLRs): the three edges of a side see the same totals, so one log-sum-exp per side gives
+    //    the qubit's messages; the check phase of iteration 0 is not uniform and runs as always.
+    // Either way no slot is read before it is written: no zero fill of the message area.
+    constexpr bool CLOSED_OK = REGULAR && CN_TYPE == FGNN_CN_BOXPLUS_PHI && !LREG && !TRACE;
+    const bool zero_start = REGULAR && !TRACE && !a.msg_init_x && !a.msg_init_z && a.num_iter > 0;
+    const bool first_closed = CLOSED_OK && zero_start && !a.llr_ch;
+    const bool first_peeled = zero_start && a.llr_ch != nullptr;
+    const bool fill = !first_closed && !first_peeled;
+    if (active) {
+        if (fill) {
+            for (int e = lane; e < g.E_x; e += a.tpc) msg[e] = a.msg_init_x ? a.msg_init_x[(size_t)b * g.E_x + e] : 0.0f;
+            for (int e = lane; e < g.E_z; e += a.tpc)
+                msg[g.E_x + e] = a.msg_init_z ? a.msg_init_z[(size_t)b * g.E_z + e] : 0.0f;
+        }
         if (a.llr_ch && !LREG)
             for (int i = lane; i < 3 * n; i += a.tpc) Lch[i] = a.llr_ch[(size_t)b * 3 * n + i];
     }
@@ -367,7 +385,7 @@ bp4_kernel(GraphDev g, BpArgs a)
             for (int c = 0; c < 3; ++c) lreg[c][i] = in ? a.llr_ch[(size_t)b * 3 * n + c * n + v] : 0.0f;
         }
     }
-    __syncthreads();
+    if (fill || (a.llr_ch && !LREG)) __syncthreads();  // workgroup-uniform: nothing was written to LDS otherwise
 
     const uint8_t* sx = a.synd_x + (size_t)b * g.m_x;
     const uint8_t* sz = a.synd_z + (size_t)b * g.m_z;
@@ -383,13 +401,13 @@ bp4_kernel(GraphDev g, BpArgs a)
     int* flags = reinterpret_cast<int*>(sigw + n);
     bool a1 = false, a2 = false;
     if (opt_exit) {
-        // (closed-form start: the sign words iteration 0 would have recorded are those of the all-zero messages)
-        for (int v = lane; v < n; v += a.tpc) sigw[v] = first_closed ? 0u : 0xffffffffu;
+        // (closed-form or peeled start: the sign words iteration 0 would have recorded are those of the all-zero messages)
+        for (int v = lane; v < n; v += a.tpc) sigw[v] = fill ? 0xffffffffu : 0u;
         if (lane < 4) flags[lane] = 0;
         __syncthreads();
     }
     int it_begin = 0;
-    if constexpr (OPT && REGULAR && CN_TYPE == FGNN_CN_BOXPLUS_PHI) {
+    if constexpr (CLOSED_OK) {
         if (first_closed) {
             // the float operations of iteration 0, evaluated once per thread instead of once per edge: totals of zero messages
             // (:244-248), v->c (:254-273), then the phi rule on six equal inputs (:376-431) in the summation order of cn_phi_regular
@@ -416,7 +434,8 @@ bp4_kernel(GraphDev g, BpArgs a)
 #pragma unroll
                     for (int j = 0; j < DC; ++j) slot_ref(msg, (int)((w[j >> 1] >> ((j & 1) * 16)) & 0xffffu)) = val;
                 }
-            a1 = FG_ABS(nu_x) >= FG_PHI_MAX && FG_ABS(nu_z) >= FG_PHI_MAX;  // "iteration 0's check phase was all-saturated"
+            // "iteration 0's check phase was all-saturated": only the fixed-point detector asks
+            if (opt_exit) a1 = FG_ABS(nu_x) >= FG_PHI_MAX && FG_ABS(nu_z) >= FG_PHI_MAX;
             it_begin = 1;
             __syncthreads();
         }
@@ -469,6 +488,44 @@ bp4_kernel(GraphDev g, BpArgs a)
         // the binary LLRs are next written one iteration (two barriers) later: no barrier needed here
     };
     if constexpr (TRACE) trace_step(0);
+    if constexpr (REGULAR && !TRACE) {
+        if (first_peeled && active) {
+            // the qubit phase of iteration 0 on zero messages, which it does not read: the totals by the same additions with literal
+            // zeros (:244-248), then ONE log-sum-exp per side — the edges of a side subtract the same zero from the same totals, so
+            // their results are the same floats — stored to every slot of the side
+            auto vn_first = [&](const int v, const float lx, const float ly, const float lz) __attribute__((always_inline)) {
+                const float Y = (0.0f + 0.0f) + ly;
+                const float X = 0.0f + lx;
+                const float Z = 0.0f + lz;
+                const float numx = MX::softplus(-X);
+                const float numz = MX::softplus(-Z);
+                const float Ze = Z - 0.0f, Xe = X - 0.0f, Ye = Y - 0.0f;
+                float ox, oz;
+                if (shl) {
+                    ox = numx - (MX::lse2_corr(-Z, -Y) + FG_MAX(-Ze, -Ye));
+                    oz = numz - (MX::lse2_corr(-X, -Y) + FG_MAX(-Xe, -Ye));
+                } else {
+                    ox = numx - MX::lse2(-Ze, -Ye);
+                    oz = numz - MX::lse2(-Xe, -Ye);
+                }
+                float* px = msg + v * DVX;
+                float* pz = msg + g.E_x + v * DVZ;
+#pragma unroll
+                for (int k = 0; k < DVX; ++k) px[k] = ox;
+#pragma unroll
+                for (int k = 0; k < DVZ; ++k) pz[k] = oz;
+            };
+            if constexpr (LREG) {
+#pragma unroll
+                for (int i = 0; i < NQ; ++i) {
+                    const int v = lane + i * a.tpc;
+                    if (v < n) vn_first(v, lreg[0][i], lreg[1][i], lreg[2][i]);
+                }
+            } else {
+                for (int v = lane; v < n; v += a.tpc) vn_first(v, Lch[v], Lch[n + v], Lch[2 * n + v]);
+            }
+        }
+    }
     for (int it = it_begin; it < a.num_iter; ++it) {
         bool changed = false, cn_slow = false;
         // ---- variable nodes: _vn_update (:227-275) ----
@@ -621,7 +678,7 @@ bp4_kernel(GraphDev g, BpArgs a)
                     }
                 }
             };
-        if (active) {
+        if (active && !(first_peeled && it == 0)) {  // (peeled: iteration 0's qubit phase ran above)
             if constexpr (LREG) {
 #pragma unroll
                 for (int i = 0; i < NQ; ++i) {
