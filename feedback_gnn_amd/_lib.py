@@ -126,6 +126,13 @@ _SIGNATURES = {
     "fgnn_feedback_gnn_backward": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 9),
     "fgnn_feedback_gnn_backward_general": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 3
                                            + [C.c_int, C.c_void_p]),
+    "fgnn_gnnbp4_grad_count": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
+    "fgnn_gnnbp4_tape_bytes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "fgnn_gnnbp4_backward_workspace_bytes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_size_t)]),
+    "fgnn_gnnbp4_forward_tape": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_size_t, C.c_void_p]),
+    "fgnn_gnnbp4_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
 ABI_SYMBOLS = tuple(_SIGNATURES)

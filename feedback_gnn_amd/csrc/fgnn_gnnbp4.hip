@@ -1185,6 +1185,25 @@ extern "C" int fgnn_gnnbp4_weights_create_general(const fgnn_graph* g, const fgn
     return FGNN_OK;
 }
 
+bool fgnn_gnnbp4_weights_train_view(const fgnn_gnnbp4_weights* w, fgnn_gnnbp4_train_view* out)
+{
+    if (!w || !out || !w->general) return false;
+    const GnnBp4GenDev& G = w->gen;
+    out->device = w->device;
+    out->D = G.D; out->H = G.H; out->L = G.L; out->reduce_op = G.rop; out->act = G.act; out->bias = G.bias;
+    out->use_attributes = (G.An > 0 || G.Am > 0) ? 1 : 0;
+    for (int q = 0; q < 7; ++q)
+        for (int k = 0; k < 4; ++k) {
+            out->W[q][k] = G.W[q][k];
+            out->b[q][k] = G.b[q][k];
+            out->K[q][k] = G.K[q][k];
+            out->J[q][k] = G.J[q][k];
+        }
+    out->winv = G.winv;
+    out->binv = G.binv;
+    return true;
+}
+
 extern "C" size_t fgnn_gnnbp4_weights_workspace_bytes(const fgnn_graph* g, const fgnn_gnnbp4_weights* w, int B)
 {
     if (!g || !w || B <= 0) return 0;

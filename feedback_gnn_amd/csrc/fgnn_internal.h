@@ -101,6 +101,20 @@ struct fgnn_weights {
     GnnGeneralDev gen;
 };
 
+// What the GNN_BP4 tape forward and reverse pass (fgnn_gnnbp4_backward.hip) read of a weight handle made by
+// fgnn_gnnbp4_weights_create_general: the configuration and the device arrays W[q][l] [K][J], b[q][l] [J] (null without bias) of MLP
+// q = cn_msg_x, cn_msg_z, cn_embed_x, cn_embed_z, vn_msg_x, vn_msg_z, vn_embed, and _llr_inv_embed.  Returns false for a handle of
+// fgnn_gnnbp4_weights_create (its arrays are laid out for the MFMA kernel).
+struct fgnn_gnnbp4_train_view {
+    int device, D, H, L, reduce_op, act, bias, use_attributes;
+    const float* W[7][4];
+    const float* b[7][4];
+    int K[7][4], J[7][4];
+    const float* winv;  // [D][3]
+    const float* binv;  // [3] or null
+};
+bool fgnn_gnnbp4_weights_train_view(const fgnn_gnnbp4_weights* w, fgnn_gnnbp4_train_view* out);
+
 void fgnn_set_error(const std::string& s);
 int fgnn_fail(int code, const std::string& s);
 #define FGNN_HIP_CHECK(expr)                                                                          \

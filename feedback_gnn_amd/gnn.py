@@ -65,6 +65,38 @@ class MLP:
     call = __call__
 
 
+def gnnbp4_label_rows(code, device="cpu"):
+    """The row matrices of the GNN_BP4 training labels as float32 tensors: [hz; lz] for the x_logit rows, [hx; lx] for the z_logit rows."""
+    rows = lambda a, b: torch.from_numpy(np.concatenate([np.asarray(a), np.asarray(b)], 0).astype(np.float32)).to(device)
+    return rows(code.hz, code.lz), rows(code.hx, code.lx)
+
+
+def gnnbp4_labels(label_rows, noise):
+    """The training labels of ``GNN_BP4.loss_and_grads``, 1 - parity as in Second_Stage_GNN_BP_Model: for the x_logit rows the parities
+    of noise_x on the hz rows (= syndrome_z) then the lz rows, for the z_logit rows those of noise_z on the hx rows then the lx rows.
+    ``noise`` = (noise_x[bs, n], noise_z[bs, n]); returns float32 tensors (gt_x[bs, m_z + k], gt_z[bs, m_x + k])."""
+    out = []
+    for e, mat in zip(noise, label_rows):
+        e = torch.as_tensor(e, device=mat.device)
+        if e.dim() != 2 or e.shape[1] != mat.shape[1]:
+            raise ValueError(f"noise must have shape [batch_size, {mat.shape[1]}], got {tuple(e.shape)}")
+        par = torch.remainder((e.to(torch.int64) & 1).to(torch.float32) @ mat.t(), 2.0)  # exact: the counts stay below 2^24
+        out.append(1.0 - par)
+    return out[0], out[1]
+
+
+def split_flat_grads(flat, shapes):
+    """The flat gradient of fgnn_gnnbp4_backward as a list of views in weight-list order and shapes."""
+    grads, pos = [], 0
+    for shp in shapes:
+        cnt = int(np.prod(shp))
+        grads.append(flat[pos:pos + cnt].view(tuple(shp)))
+        pos += cnt
+    if pos != flat.numel():
+        raise ValueError(f"gradient holds {flat.numel()} values, the weight list {pos}")
+    return grads
+
+
 class GNN_BP4:
     """``decoder((syndrome_x[bs,m_x], syndrome_z[bs,m_z]))`` → ``(llr_hat, x_hat[n,bs], z_hat[n,bs])`` where ``llr_hat`` is a
     list with one ``(x_perp_logit[m_z+k,bs], z_perp_logit[m_x+k,bs])`` pair per iteration (gnn.py:409)."""
@@ -118,6 +150,45 @@ class GNN_BP4:
 
     def set_weights(self, weights):
         self._weights = GnnBp4Weights(list(weights), self.graph.device, config=self.config, graph=self.graph)
+        self._train_weights = None  # the runtime-shaped copy loss_and_grads runs on (built on first use)
+
+    def labels(self, noise):
+        """``gnnbp4_labels`` of this decoder's code, on its device (the row matrices are uploaded once)."""
+        if getattr(self, "_label_rows", None) is None:
+            self._label_rows = gnnbp4_label_rows(self.graph.code, self.graph.device)
+        return gnnbp4_labels(self._label_rows, noise)
+
+    def loss_and_grads(self, inputs, noise, loss_from=0):
+        """One training step's loss and gradients on the GPU: the tape forward (fgnn_gnnbp4_forward_tape), BCE-with-logits of every
+        iteration ``loss_from .. num_iter-1`` against ``labels(noise)`` (mean-reduced, both sides, summed; torch ops on the GPU logits)
+        and the hand-written reverse pass (fgnn_gnnbp4_backward).  Returns ``(loss, grads)`` with ``grads`` a list of tensors in
+        ``get_weights()`` order and shapes.  reduce_op max / min and use_attributes are not differentiable here."""
+        g = self.graph
+        if self.config[3] in ("max", "min"):
+            raise NotImplementedError(f"reduce_op {self.config[3]!r} is not differentiable here: loss_and_grads implements sum and mean")
+        if self.config[6]:
+            raise NotImplementedError("use_attributes=True is not differentiable here")
+        syndrome_x, syndrome_z = inputs
+        prep = lambda t: (torch.as_tensor(t, device=g.device).to(torch.int64) & 1).to(torch.uint8).contiguous()
+        sx, sz = prep(syndrome_x), prep(syndrome_z)
+        gt_x, gt_z = self.labels(noise)
+        T = self._num_iter
+        if not 0 <= int(loss_from) < T:
+            raise ValueError(f"loss_from must be in [0, {T}), got {loss_from}")
+        if self._weights.general:
+            W = self._weights
+        else:  # the MFMA handle's arrays are laid out for its kernel: the tape runs on a runtime-shaped copy of the same arrays
+            if self._train_weights is None:
+                self._train_weights = GnnBp4Weights(self._weights.arrays, g.device, config=self.config, graph=g, force_general=True)
+            W = self._train_weights
+        fwd = g.gnn_bp4_forward_tape(W, sx, sz, T)
+        xl = fwd["x_logit_all"].requires_grad_(True)
+        zl = fwd["z_logit_all"].requires_grad_(True)
+        bce = torch.nn.functional.binary_cross_entropy_with_logits
+        loss = sum(bce(xl[i], gt_x) + bce(zl[i], gt_z) for i in range(int(loss_from), T))
+        loss.backward()
+        flat = g.gnn_bp4_backward(W, sx, sz, T, fwd["tape"], xl.grad, zl.grad)
+        return float(loss.detach()), split_flat_grads(flat, [a.shape for a in self._weights.arrays])
 
     def __call__(self, inputs):
         syndrome_x, syndrome_z = inputs

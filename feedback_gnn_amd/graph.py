@@ -835,6 +835,66 @@ class TannerGraph:
                                             _stream(self.device)))
         return dict(x_hat=xh, z_hat=zh, llr=llr, x_logit_all=xl, z_logit_all=zl)
 
+    def _gnn_bp4_trainable(self, weights):
+        """The reverse pass exists for runtime-shaped handles with sum / mean and no attributes; anything else is refused here,
+        before any kernel is launched."""
+        if weights.config[3] in ("max", "min"):
+            raise NotImplementedError(f"reduce_op {weights.config[3]!r} is not differentiable here: the GNN_BP4 reverse pass implements sum and mean")
+        if weights.config[6]:
+            raise NotImplementedError("use_attributes=True is not differentiable here: the GNN_BP4 reverse pass has no attribute gradients")
+        if not weights.general:
+            raise ValueError("the GNN_BP4 tape and reverse pass take a runtime-shaped weight set: GnnBp4Weights(..., force_general=True)")
+
+    def gnn_bp4_tape_bytes(self, weights, num_iter, B):
+        self._gnn_bp4_trainable(weights)
+        nbytes = C.c_size_t()
+        check(_lib.lib().fgnn_gnnbp4_tape_bytes(self.handle, weights.handle, int(num_iter), int(B), C.byref(nbytes)))
+        return int(nbytes.value)
+
+    def gnn_bp4_backward_workspace_bytes(self, weights, B):
+        self._gnn_bp4_trainable(weights)
+        nbytes = C.c_size_t()
+        check(_lib.lib().fgnn_gnnbp4_backward_workspace_bytes(self.handle, weights.handle, int(B), C.byref(nbytes)))
+        return int(nbytes.value)
+
+    def gnn_bp4_forward_tape(self, weights, synd_x, synd_z, num_iter, tape=None):
+        """GNN_BP4.call with a tape for `gnn_bp4_backward` (fgnn_gnnbp4_forward_tape): the soft syndromes of `gnn_bp4_decode` on the
+        same runtime-shaped weight set, bit for bit, and the activation tape (a float32 tensor; pass one to reuse it)."""
+        self._gnn_bp4_trainable(weights)
+        B, T = int(synd_x.shape[0]), int(num_iter)
+        synd_x = self._chk(synd_x, (B, self.m_x), torch.uint8, "synd_x")
+        synd_z = self._chk(synd_z, (B, self.m_z), torch.uint8, "synd_z")
+        if tape is None:
+            tape = self._new((self.gnn_bp4_tape_bytes(weights, T, B) // 4,), torch.float32)
+        xl = self._new((T, B, self.m_z + self.rows_lz), torch.float32)
+        zl = self._new((T, B, self.m_x + self.rows_lx), torch.float32)
+        with torch.cuda.device(self.device):
+            check(_lib.lib().fgnn_gnnbp4_forward_tape(self.handle, weights.handle, T, _ptr(synd_x), _ptr(synd_z), B, _ptr(xl), _ptr(zl),
+                                                      _ptr(tape), tape.numel() * 4, _stream(self.device)))
+        return dict(x_logit_all=xl, z_logit_all=zl, tape=tape)
+
+    def gnn_bp4_backward(self, weights, synd_x, synd_z, num_iter, tape, grad_x_logit_all, grad_z_logit_all, workspace=None):
+        """d loss / d (every Dense array of `weights`), summed over the batch, from d loss / d (x_logit_all, z_logit_all) of
+        `gnn_bp4_forward_tape` (either may be None) — fgnn_gnnbp4_backward.  Returns one flat float32 tensor in weight-list order."""
+        self._gnn_bp4_trainable(weights)
+        B, T = int(synd_x.shape[0]), int(num_iter)
+        synd_x = self._chk(synd_x, (B, self.m_x), torch.uint8, "synd_x")
+        synd_z = self._chk(synd_z, (B, self.m_z), torch.uint8, "synd_z")
+        if grad_x_logit_all is not None:
+            grad_x_logit_all = self._chk(grad_x_logit_all, (T, B, self.m_z + self.rows_lz), torch.float32, "grad_x_logit_all")
+        if grad_z_logit_all is not None:
+            grad_z_logit_all = self._chk(grad_z_logit_all, (T, B, self.m_x + self.rows_lx), torch.float32, "grad_z_logit_all")
+        count = C.c_int()
+        check(_lib.lib().fgnn_gnnbp4_grad_count(self.handle, weights.handle, C.byref(count)))
+        if workspace is None:
+            workspace = self._new((self.gnn_bp4_backward_workspace_bytes(weights, B),), torch.uint8)
+        grad = self._new((count.value,), torch.float32)
+        with torch.cuda.device(self.device):
+            check(_lib.lib().fgnn_gnnbp4_backward(self.handle, weights.handle, T, _ptr(synd_x), _ptr(synd_z), B, _ptr(tape),
+                                                  tape.numel() * 4, _ptr(grad_x_logit_all), _ptr(grad_z_logit_all), _ptr(grad),
+                                                  count.value, _ptr(workspace), workspace.numel(), _stream(self.device)))
+        return grad
+
 
 GNNBP4_SHAPES = ([(40, 40), (40,), (40, 20), (20,)] * 2 + [(41, 40), (40,), (40, 20), (20,)] * 2 + [(40, 40), (40,), (40, 20), (20,)] * 2
                  + [(60, 40), (40,), (40, 20), (20,)] + [(20, 3), (3,)])

@@ -16,7 +16,7 @@ tensor work.
 import numpy as np
 import torch
 
-__all__ = ["Adam", "clip_by_value", "compute_bler", "harvest_failures", "train_second_stage"]
+__all__ = ["Adam", "clip_by_value", "compute_bler", "harvest_failures", "train_second_stage", "train_gnn_bp4"]
 
 
 def clip_by_value(t, lo, hi):
@@ -97,4 +97,25 @@ def train_second_stage(model_stage_one, model_stage_two, dataset_x, dataset_z, b
                 log(f"Iteration {it}/{steps}. Current loss: {float(loss):3f} bler: {bler:.4f} flagged bler: {flagged:.4f}")
             grads = [clip_by_value(g, -clip_value_grad, clip_value_grad) for g in grads]
             opt.apply_gradients(zip(grads, model_stage_two.trainable_weights))
+    return history
+
+
+def train_gnn_bp4(decoder, p, batch_size, steps, learning_rate, seed, loss_from=0, on_step=None):
+    """Train a `GNN_BP4` decoder on depolarizing noise of strength ``p``: per step a fresh batch from ``graph.pauli_noise`` (the
+    first sample advances by ``batch_size``, so no error pattern repeats), its syndromes, ``decoder.loss_and_grads`` (tape forward,
+    BCE, hand-written reverse pass), Keras ``Adam`` and ``decoder.set_weights``.  ``on_step(step, loss)`` is called after every step.
+    Returns the loss history."""
+    g = decoder.graph
+    opt = Adam(learning_rate)
+    params = [torch.from_numpy(a).to(g.device) for a in decoder.get_weights()]
+    history = []
+    for step in range(int(steps)):
+        ex, ez = g.pauli_noise(int(seed), p, step * int(batch_size), int(batch_size))
+        sx, sz = g.syndrome(ex, ez)
+        loss, grads = decoder.loss_and_grads((sx, sz), (ex, ez), loss_from=loss_from)
+        opt.apply_gradients(zip(grads, params))
+        decoder.set_weights([t.cpu().numpy() for t in params])
+        history.append(loss)
+        if on_step is not None:
+            on_step(step, loss)
     return history

@@ -441,6 +441,34 @@ int fgnn_feedback_gnn_backward_general(const fgnn_graph* g, const fgnn_weights* 
                                        const float* logit_hz, const uint8_t* synd_x, const uint8_t* synd_z, int B,
                                        const float* grad_out, float* const* acts, float* const* deltas, int num_layers, void* stream);
 
+/* ---- training GNN_BP4 -------------------------------------------------------------------------------------------------
+ * A forward pass that records a tape and the reverse pass through GNN_BP4.call, for weights made by
+ * fgnn_gnnbp4_weights_create_general with reduce_op sum or mean and use_attributes = 0 (max / min and attributes: FGNN_ERR_ARG
+ * naming the setting).  D = 20, H = 40, L = 2, tanh, mean, bias runs kernels with compile-time widths (unless
+ * fgnn_graph_force_generic is on), every other setting runtime-shaped ones.
+ *
+ * fgnn_gnnbp4_forward_tape: x_logit_all / z_logit_all as fgnn_gnnbp4_decode writes them for the same handle, bit for bit, and
+ * the tape [B][num_iter][(n + m) D + m] floats: per codeword and iteration h_vn [n][D] after the VN update, h_cn [m][D] that
+ * update read, and the hx then hz logits [m] that feed the next CN update.  The embeddings live in the tape: no workspace.
+ *
+ * fgnn_gnnbp4_backward: grad_x_logit_all [num_iter,B,m_z+rows(lz)] / grad_z_logit_all [num_iter,B,m_x+rows(lx)] = d loss / d of
+ * the arrays the forward returned (either may be NULL: that side contributes nothing).  grad_weights [grad_count] receives the
+ * gradient of every Dense array, summed over the batch, in the order of host_arrays (7 MLPs x L layers {W (, b)}, then
+ * _llr_inv_embed {W (, b)}); grad_count = fgnn_gnnbp4_grad_count.  workspace: fgnn_gnnbp4_backward_workspace_bytes, caller-owned
+ * (per-node and per-edge gradient state and one partial gradient per workgroup).  No floating-point atomics: the same inputs
+ * give the same bits.  A tape or workspace smaller than needed is refused with both byte counts in the message.
+ * Conventions as fgnn_bp4_backward: constant sign products, clip_by_value's gradient inside phi, |x|' = sign(x). */
+int fgnn_gnnbp4_grad_count(const fgnn_graph* g, const fgnn_gnnbp4_weights* w, int* count);
+int fgnn_gnnbp4_tape_bytes(const fgnn_graph* g, const fgnn_gnnbp4_weights* w, int num_iter, int B, size_t* bytes);
+int fgnn_gnnbp4_backward_workspace_bytes(const fgnn_graph* g, const fgnn_gnnbp4_weights* w, int B, size_t* bytes);
+int fgnn_gnnbp4_forward_tape(const fgnn_graph* g, const fgnn_gnnbp4_weights* w, int num_iter, const uint8_t* synd_x,
+                             const uint8_t* synd_z, int B, float* x_logit_all, float* z_logit_all, float* tape, size_t tape_bytes,
+                             void* stream);
+int fgnn_gnnbp4_backward(const fgnn_graph* g, const fgnn_gnnbp4_weights* w, int num_iter, const uint8_t* synd_x,
+                         const uint8_t* synd_z, int B, const float* tape, size_t tape_bytes, const float* grad_x_logit_all,
+                         const float* grad_z_logit_all, float* grad_weights, int grad_count, void* workspace, size_t ws_bytes,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif
