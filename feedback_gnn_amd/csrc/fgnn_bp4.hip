@@ -9,8 +9,8 @@
 // The reference streams every [E,bs] message tensor through HBM ~10 times per half-iteration.
 // Here a codeword's state (E floats of messages, 21 KB for [[882,24]], in LDS; per-qubit channel LLRs in registers for the
 // benchmark codes, else 3n more floats of LDS) never leaves the CU: HBM sees the syndromes once and the results once.  The kernel is therefore bound
-// by VALU issue (about 830 fma-class ops per qubit-iteration for the exact exp/log of
-// fgnn_math.h), not by HBM; DESIGN.md §4 gives the accounting next to the streaming-model figure.
+// by VALU issue (about 800 VALU instructions per node-iteration for the exact exp/log of
+// fgnn_math.h, all but the six slot unpacks per check inside the float routines), not by HBM; DESIGN.md §4 gives the accounting next to the streaming-model figure.
 //
 // Message layout in LDS: slot e in [0,E_x) = hx edges, [E_x,E) = hz edges, both sorted by
 // (qubit, check).  The VN phase reads/writes a contiguous run per qubit; the CN phase gathers its
@@ -25,8 +25,11 @@
 // operation count per codeword stays a constant, and every float that reaches a message is produced by the operations the oracle
 // executes for it (see first_closed / first_peeled in bp4_kernel).
 
+#include <type_traits>
+
 #include "fgnn_internal.h"
 #include "fgnn_math.h"
+#include "fgnn_math_ranged.h"
 #include "fgnn_cn.h"
 
 #ifndef FGNN_BP4_WAVES
@@ -70,6 +73,7 @@ struct BpArgs {
     int trace_off;            // float offset of the 2n binary LLRs the per-iteration soft syndromes are formed from
     float* tape_x;            // TRACE variant, optional: [num_iter+1, B, E_x] c->v messages before iteration k (k = num_iter: after the last),
     float* tape_z;            //                          [num_iter+1, B, E_z] — the tape fgnn_bp4_backward reads
+    int nt;                   // 4 / 5: first decoder with compile-time trips (kernel variant NT = nt), 0: the runtime loops
     int shared_lse;           // 1: the (a - b)-dependent part of the qubit update's log-sum-exp once per qubit and side (FGNN_OPT_BP4_SHARED_LSE)
 };
 
@@ -81,8 +85,10 @@ struct BpArgs {
 template <bool HWT>
 struct Mx {
     static __device__ __forceinline__ float softplus(float t) { return fg_softplus(t); }
-    static __device__ __forceinline__ float lse2(float a, float b) { return fg_lse2(a, b); }
-    static __device__ __forceinline__ float lse2_corr(float a, float b) { return fg_lse2_corr(a, b); }
+    // the log of a log-sum-exp sees 1 + exp(-min(d, 20)) in [1, 2]: fgnn_math_ranged.h forms its exponent term without the half-rate
+    // int -> float conversion of fg_log — the same bits (tests/test_math_ranged.py, exhaustive)
+    static __device__ __forceinline__ float lse2(float a, float b) { return fg_lse2_ranged(a, b); }
+    static __device__ __forceinline__ float lse2_corr(float a, float b) { return fg_lse2_corr_ranged(a, b); }
     static __device__ __forceinline__ float phi(float x) { return fg_phi(x); }
 };
 template <>
@@ -193,16 +199,17 @@ __device__ __forceinline__ void phi_n(const float (&x)[N], float (&out)[N])
 // configurations without the LDS round trip of the runtime-degree version.  Same float ops, same order.
 // Signs are carried as integer sign words: neg = (synd << 31) ^ bits(v_0) ^ ... (bit 31 = the parity of :398-399), and the
 // outgoing sign of edge j is bit 31 of neg ^ bits(v_j) — one xor per edge in, one xor + one bit-field insert per edge out.
+// `neg0` = a word whose bit 31 is the check's syndrome bit (its other bits never reach a result: only bit 31 of `neg` is used).
 // `sl` = BYTE offsets of the check's slots from `msg` (the packed rows of g.cslot16 hold 4 * slot); F1 = the normalisation factor is
 // exactly 1 (feedback_gnn.py / n882.py: every paper run), so the product with it — the identity on every float — is not issued.
 template <int DC, bool HWT = false, bool F1 = false>
-__device__ __forceinline__ bool cn_phi_regular(float* msg, const int (&sl)[DC], unsigned synd, float factor, float phi0,
+__device__ __forceinline__ bool cn_phi_regular(float* msg, const int (&sl)[DC], uint32_t neg0, float factor, float phi0,
                                                bool shortcut)
 {
     constexpr int H = (DC % FGNN_PHI_STAGE == 0) ? FGNN_PHI_STAGE : DC / 2;
     static_assert(DC % H == 0, "a phi stage must take a whole fraction of a check");
     float v[DC], aa[DC];
-    uint32_t neg = synd << 31;
+    uint32_t neg = neg0;
     bool sat = true;
 #pragma unroll
     for (int j = 0; j < DC; ++j) {
@@ -314,7 +321,8 @@ __device__ __forceinline__ float softplus_saturated(float t)
 // NQ > 0: per-qubit channel LLRs (llr_ch != null: every decoder of a sandwich but the first) live in REGISTERS, 3 x NQ per thread
 // for the at most NQ qubits lane, lane + tpc, ... a thread owns, instead of 3n floats of LDS: the workgroup then needs the message
 // area only and 7 instead of 4 ([[882,24]]) / 5 instead of 3 ([[1270,28]]) workgroups share a CU; the register budget is that of
-// 6 waves per SIMD.  The launch picks NQ = 4 when a thread owns at most 4 qubits (ceil(n / tpc) <= 4) and NQ = 5 when it owns 5.
+// 6 waves per SIMD.  The launch picks NQ = 4 when a thread owns at most 4 qubits and at most 4 checks (ceil(max(n, m) / tpc) <= 4) and NQ = 5 when it
+// owns 5: NQ is also the compile-time trip count of the check phase.
 // TRACE: the `trainable` / `stage_two` return mode of the reference (decoding_q.py:743-746, 779-781): the soft syndromes of the
 // marginals are recorded after EVERY iteration (and before the first) by the kernel itself, from 2n binary LLRs in their own LDS
 // area — one launch instead of num_iter + 1 chained one-iteration launches with the messages going through HBM in between.  Same
@@ -326,7 +334,13 @@ __device__ __forceinline__ float softplus_saturated(float t)
 // library default), 1 = once per qubit and side (FGNN_OPT_BP4_SHARED_LSE), both compiled in for the (3,3,6)-regular phi kernels; 2 = either,
 // chosen by a.shared_lse at run time (every other instantiation).  The compile-time forms run at the speed of the runtime flag (44.8 / 39.5
 // ms either way); what they buy is one kernel SYMBOL per form, so that a rocprofv3 trace or PMC pass prices each form by itself.
-template <int CN_TYPE, int DVX, int DVZ, int DC, bool OPT, bool HWT = false, int NQ = 0, bool TRACE = false, bool GMEM = false, int LSE = 2>
+// NT > 0 (NQ = 0, one constant channel LLR, one codeword per workgroup of 256 threads): a thread owns exactly NT qubits and NT checks
+// (ceil(n / 256) == ceil(m / 256) == NT, from the launch plan), the last of each only if it exists.  The trips of both phases are
+// unrolled at compile time: a qubit's slots are one per-thread LDS base plus an immediate offset, a check's packed row is a scalar base
+// plus one per-thread offset, and no counter, pointer or bounds test is carried through the iteration loop.  The NQ > 0 kernels run
+// their checks the same way with NQ trips, each guarded (their threads-per-codeword is a launch argument).
+template <int CN_TYPE, int DVX, int DVZ, int DC, bool OPT, bool HWT = false, int NQ = 0, bool TRACE = false, bool GMEM = false, int LSE = 2,
+          int NT = 0>
 __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(NQ > 0 ? FGNN_BP4_WAVES - 1 : FGNN_BP4_WAVES)))
 bp4_kernel(GraphDev g, BpArgs a)
 {
@@ -337,17 +351,21 @@ bp4_kernel(GraphDev g, BpArgs a)
     constexpr bool REGULAR = DVX > 0;
     constexpr bool LREG = NQ > 0;
     constexpr int NQA = LREG ? NQ : 1;
+    static_assert(NT == 0 || (DVX > 0 && CN_TYPE == FGNN_CN_BOXPLUS_PHI && !LREG && !TRACE && !GMEM), "compile-time trips: the regular phi kernel");
+    constexpr int CT = LREG ? NQ : NT;  // compile-time trips of the check phase (0: the runtime loop)
+    const int tpc = NT > 0 ? 256 : a.tpc;
     const bool opt_shortcut = OPT && a.shortcut != 0;
     const bool opt_exit = OPT && a.early_exit != 0;
     const bool shl = LSE == 2 ? a.shared_lse != 0 : LSE == 1;  // workgroup-uniform; a compile-time constant for LSE = 0 / 1
     extern __shared__ float lds[];
-    const int cwl = threadIdx.x / a.tpc;
-    const int lane = threadIdx.x - cwl * a.tpc;
-    const int slot_b = blockIdx.x * a.cpb + cwl;
+    const int cwl = NT > 0 ? 0 : threadIdx.x / tpc;
+    const int lane = threadIdx.x - cwl * tpc;
+    const int slot_b = NT > 0 ? blockIdx.x : blockIdx.x * a.cpb + cwl;
     const bool active = slot_b < a.B;  // padding codewords of the last block only keep the barriers company
     const int b = (active && a.index) ? a.index[slot_b] : slot_b;
     float* msg;
     if constexpr (GMEM) msg = a.gmem + (size_t)slot_b * a.lds_per_cw;
+    else if constexpr (NT > 0) msg = lds;
     else msg = lds + (size_t)cwl * a.lds_per_cw;
     float* Lch = msg + a.lch_off;  // [3n], only when llr_ch != null
     const int n = g.n;
@@ -368,18 +386,18 @@ bp4_kernel(GraphDev g, BpArgs a)
     const bool fill = !first_closed && !first_peeled;
     if (active) {
         if (fill) {
-            for (int e = lane; e < g.E_x; e += a.tpc) msg[e] = a.msg_init_x ? a.msg_init_x[(size_t)b * g.E_x + e] : 0.0f;
-            for (int e = lane; e < g.E_z; e += a.tpc)
+            for (int e = lane; e < g.E_x; e += tpc) msg[e] = a.msg_init_x ? a.msg_init_x[(size_t)b * g.E_x + e] : 0.0f;
+            for (int e = lane; e < g.E_z; e += tpc)
                 msg[g.E_x + e] = a.msg_init_z ? a.msg_init_z[(size_t)b * g.E_z + e] : 0.0f;
         }
         if (a.llr_ch && !LREG)
-            for (int i = lane; i < 3 * n; i += a.tpc) Lch[i] = a.llr_ch[(size_t)b * 3 * n + i];
+            for (int i = lane; i < 3 * n; i += tpc) Lch[i] = a.llr_ch[(size_t)b * 3 * n + i];
     }
     float lreg[3][NQA];  // LREG: channel LLRs of qubits lane + i * tpc
     if constexpr (LREG) {
 #pragma unroll
         for (int i = 0; i < NQ; ++i) {
-            const int v = lane + i * a.tpc;
+            const int v = lane + i * tpc;
             const bool in = active && v < n;
 #pragma unroll
             for (int c = 0; c < 3; ++c) lreg[c][i] = in ? a.llr_ch[(size_t)b * 3 * n + c * n + v] : 0.0f;
@@ -389,7 +407,7 @@ bp4_kernel(GraphDev g, BpArgs a)
 
     const uint8_t* sx = a.synd_x + (size_t)b * g.m_x;
     const uint8_t* sz = a.synd_z + (size_t)b * g.m_z;
-    const int lane_c = lane + (a.tpc >> 1) < a.tpc ? lane + (a.tpc >> 1) : lane - a.tpc + (a.tpc >> 1);
+    const int lane_c = lane + (tpc >> 1) < tpc ? lane + (tpc >> 1) : lane - tpc + (tpc >> 1);
 
     const float phi0 = MX::phi(0.0f);  // = phi(clip min) = 16.6355324, the saturated message magnitude
     (void)phi0;
@@ -402,7 +420,7 @@ bp4_kernel(GraphDev g, BpArgs a)
     bool a1 = false, a2 = false;
     if (opt_exit) {
         // (closed-form or peeled start: the sign words iteration 0 would have recorded are those of the all-zero messages)
-        for (int v = lane; v < n; v += a.tpc) sigw[v] = fill ? 0xffffffffu : 0u;
+        for (int v = lane; v < n; v += tpc) sigw[v] = fill ? 0xffffffffu : 0u;
         if (lane < 4) flags[lane] = 0;
         __syncthreads();
     }
@@ -416,7 +434,7 @@ bp4_kernel(GraphDev g, BpArgs a)
             const float nu_x = MX::softplus(-X) - MX::lse2(-(Z - 0.0f), -(Y - 0.0f));
             const float nu_z = MX::softplus(-Z) - MX::lse2(-(X - 0.0f), -(Y - 0.0f));
             if (active)
-                for (int c = lane_c; c < g.m; c += a.tpc) {
+                for (int c = lane_c; c < g.m; c += tpc) {
                     const unsigned synd = (c < g.m_x ? sx[c] : sz[c - g.m_x]) & 1u;
                     const uint4 pk = reinterpret_cast<const uint4*>(g.cslot16)[c];
                     const unsigned w[4] = {pk.x, pk.y, pk.z, pk.w};
@@ -445,9 +463,10 @@ bp4_kernel(GraphDev g, BpArgs a)
     unsigned synd_bits = 0;
     if (active) {
         int i = 0;
-        for (int c = lane_c; c < g.m && i < 32; c += a.tpc, ++i) synd_bits |= ((c < g.m_x ? sx[c] : sz[c - g.m_x]) & 1u) << i;
+        for (int c = lane_c; c < g.m && i < 32; c += tpc, ++i) synd_bits |= ((c < g.m_x ? sx[c] : sz[c - g.m_x]) & 1u) << i;
     }
-    const bool synd_in_reg = (g.m + a.tpc - 1) / a.tpc <= 32;
+    const bool synd_in_reg = (g.m + tpc - 1) / tpc <= 32;
+    unsigned row_off = 16u * (unsigned)lane_c;  // CT > 0: byte offset of the thread's packed check rows from each trip's base
     // TRACE: soft syndromes of the current messages into slot k of the trace (cal_logit :455-471 on the totals of :244-248)
     auto trace_step = [&](const int k) __attribute__((always_inline)) {
         float* tlx = msg + a.trace_off;  // [n] llr_x of cal_logit, then [n] llr_z
@@ -455,11 +474,11 @@ bp4_kernel(GraphDev g, BpArgs a)
         if (active && a.tape_x) {
             float* px = a.tape_x + ((size_t)k * a.B + b) * g.E_x;
             float* pz = a.tape_z + ((size_t)k * a.B + b) * g.E_z;
-            for (int e = lane; e < g.E_x; e += a.tpc) px[e] = msg[e];
-            for (int e = lane; e < g.E_z; e += a.tpc) pz[e] = msg[g.E_x + e];
+            for (int e = lane; e < g.E_x; e += tpc) px[e] = msg[e];
+            for (int e = lane; e < g.E_z; e += tpc) pz[e] = msg[g.E_x + e];
         }
         if (active)
-            for (int v = lane; v < n; v += a.tpc) {
+            for (int v = lane; v < n; v += tpc) {
                 const int x0 = g.vptr_x[v], x1 = g.vptr_x[v + 1], z0 = g.vptr_z[v], z1 = g.vptr_z[v + 1];
                 float Sz = 0.0f, Sx = 0.0f;
                 for (int e = z0; e < z1; ++e) Sz = Sz + msg[e];
@@ -475,12 +494,12 @@ bp4_kernel(GraphDev g, BpArgs a)
         __syncthreads();
         if (active) {
             float* tx = a.trace_x + ((size_t)k * a.B + b) * g.rows[0];
-            for (int r = lane; r < g.rows[0]; r += a.tpc) {
+            for (int r = lane; r < g.rows[0]; r += tpc) {
                 const int p0 = g.rptr[0][r];
                 tx[r] = logit_row<Mx<HWT>>(tlx, g.rcol[0] + p0, g.rptr[0][r + 1] - p0);
             }
             float* tz = a.trace_z + ((size_t)k * a.B + b) * g.rows[1];
-            for (int r = lane; r < g.rows[1]; r += a.tpc) {
+            for (int r = lane; r < g.rows[1]; r += tpc) {
                 const int p0 = g.rptr[1][r];
                 tz[r] = logit_row<Mx<HWT>>(tlz, g.rcol[1] + p0, g.rptr[1][r + 1] - p0);
             }
@@ -518,11 +537,11 @@ bp4_kernel(GraphDev g, BpArgs a)
             if constexpr (LREG) {
 #pragma unroll
                 for (int i = 0; i < NQ; ++i) {
-                    const int v = lane + i * a.tpc;
+                    const int v = lane + i * tpc;
                     if (v < n) vn_first(v, lreg[0][i], lreg[1][i], lreg[2][i]);
                 }
             } else {
-                for (int v = lane; v < n; v += a.tpc) vn_first(v, Lch[v], Lch[n + v], Lch[2 * n + v]);
+                for (int v = lane; v < n; v += tpc) vn_first(v, Lch[v], Lch[n + v], Lch[2 * n + v]);
             }
         }
     }
@@ -682,11 +701,18 @@ bp4_kernel(GraphDev g, BpArgs a)
             if constexpr (LREG) {
 #pragma unroll
                 for (int i = 0; i < NQ; ++i) {
-                    const int v = lane + i * a.tpc;
+                    const int v = lane + i * tpc;
                     if (v < n) vn_body(v, lreg[0][i], lreg[1][i], lreg[2][i]);
                 }
+            } else if constexpr (NT > 0) {
+                // qubits lane, lane + 256, ...: the slots of trip i are the thread's base + 12 * 256 * i bytes, an immediate offset
+#pragma unroll
+                for (int i = 0; i < NT; ++i) {
+                    const int v = lane + i * 256;
+                    if (i + 1 < NT || v < n) vn_body(v, a.llr_const, a.llr_const, a.llr_const);
+                }
             } else {
-                for (int v = lane; v < n; v += a.tpc) {
+                for (int v = lane; v < n; v += tpc) {
                     if (a.llr_ch) vn_body(v, Lch[v], Lch[n + v], Lch[2 * n + v]);
                     else vn_body(v, a.llr_const, a.llr_const, a.llr_const);
                 }
@@ -701,9 +727,44 @@ bp4_kernel(GraphDev g, BpArgs a)
         }
         // checks are dealt to the threads half a workgroup out of phase with the qubits: with 882 nodes on 4 waves two waves get
         // 4 slices of 64 and two get 3 — the qubit phase gives the extra slice to the low waves, the check phase to the high ones
-        if (active) {
+        if constexpr (REGULAR && CT > 0 && CN_TYPE == FGNN_CN_BOXPLUS_PHI) {
+            // Compile-time trips (one codeword per workgroup: the message area starts at the base of the dynamic LDS).  The packed row
+            // of check lane_c + i * tpc is read from a scalar base, bumped per trip by scalar adds, plus the thread's byte offset
+            // 16 * lane_c, formed once per launch; its syndrome bit is moved to bit 31 by one shift with a constant count; the two
+            // copies of the update (factor == 1 / != 1) are chosen once per iteration, not once per check.  The rows are read again
+            // every iteration: four or five of them resident would cost 16 to 20 registers, and the load is not the cost.
+            auto cn_trips = [&](auto f1) __attribute__((always_inline)) {
+                constexpr bool F1 = decltype(f1)::value;
+                const char* rows = reinterpret_cast<const char*>(g.cslot16);
+#pragma unroll
+                for (int i = 0; i < CT; ++i) {
+                    const bool in = (!LREG && i + 1 < CT) || lane_c + i * tpc < g.m;
+                    if (in) {
+                        // The row is read at scalar base + 32-bit thread offset.  Left alone the optimiser forms the CT 64-bit row
+                        // addresses once per launch and keeps them in 2 * CT registers, or folds a compile-time stride into a 64-bit
+                        // vector add per row; the two empty statements make the offset and the trip's base opaque to it right here and
+                        // emit nothing.  (A pointer that went through one is generic: the cast says again that it is global memory.)
+                        const char* base = rows + (size_t)i * (size_t)(16u * (unsigned)tpc);
+                        asm volatile("" : "+v"(row_off));
+                        if constexpr (NT > 0) asm volatile("" : "+s"(base));
+                        typedef unsigned Row __attribute__((ext_vector_type(4)));
+                        const Row pk = *(const __attribute__((address_space(1))) Row*)(base + row_off);
+                        const unsigned w[4] = {pk.x, pk.y, pk.z, pk.w};
+                        int sl[DC];  // byte offsets
+#pragma unroll
+                        for (int j = 0; j < DC; ++j) sl[j] = (int)((w[j >> 1] >> ((j & 1) * 16)) & 0xffffu);
+                        const bool fast = cn_phi_regular<DC, HWT, F1>(lds, sl, synd_bits << (31 - i), F1 ? 1.0f : a.factor, phi0, opt_shortcut);
+                        cn_slow = !fast || cn_slow;
+                    }
+                }
+            };
+            if (active) {
+                if (cn_f1) cn_trips(std::true_type{});
+                else cn_trips(std::false_type{});
+            }
+        } else if (active) {
             int ci = 0;
-            for (int c = lane_c; c < g.m; c += a.tpc, ++ci) {
+            for (int c = lane_c; c < g.m; c += tpc, ++ci) {
                 const unsigned synd = synd_in_reg ? (synd_bits >> ci) & 1u : (c < g.m_x ? sx[c] : sz[c - g.m_x]) & 1u;
                 if constexpr (REGULAR) {
                     const uint4 pk = reinterpret_cast<const uint4*>(g.cslot16)[c];
@@ -715,9 +776,9 @@ bp4_kernel(GraphDev g, BpArgs a)
                         // one codeword per workgroup: the message area starts at the (compile-time) base of the dynamic LDS, so the
                         // byte offsets are the LDS addresses up to an immediate; factor 1: no product
                         bool fast;
-                        if (cn_one && cn_f1) fast = cn_phi_regular<DC, HWT, true>(lds, sl, synd, 1.0f, phi0, opt_shortcut);
-                        else if (cn_one) fast = cn_phi_regular<DC, HWT, false>(lds, sl, synd, a.factor, phi0, opt_shortcut);
-                        else fast = cn_phi_regular<DC, HWT, false>(msg, sl, synd, a.factor, phi0, opt_shortcut);
+                        if (cn_one && cn_f1) fast = cn_phi_regular<DC, HWT, true>(lds, sl, synd << 31, 1.0f, phi0, opt_shortcut);
+                        else if (cn_one) fast = cn_phi_regular<DC, HWT, false>(lds, sl, synd << 31, a.factor, phi0, opt_shortcut);
+                        else fast = cn_phi_regular<DC, HWT, false>(msg, sl, synd << 31, a.factor, phi0, opt_shortcut);
                         cn_slow = !fast || cn_slow;
                     } else if constexpr (CN_TYPE == FGNN_CN_MINSUM) {
                         cn_minsum_regular<DC>(msg, sl, DC, synd, a.factor);
@@ -746,9 +807,9 @@ bp4_kernel(GraphDev g, BpArgs a)
     // ---- marginals (:777), hard decision (:783-790), binary LLRs of cal_logit (:455-464) ----
     if (active) {
         if (a.msg_out_x)
-            for (int e = lane; e < g.E_x; e += a.tpc) a.msg_out_x[(size_t)b * g.E_x + e] = msg[e];
+            for (int e = lane; e < g.E_x; e += tpc) a.msg_out_x[(size_t)b * g.E_x + e] = msg[e];
         if (a.msg_out_z)
-            for (int e = lane; e < g.E_z; e += a.tpc) a.msg_out_z[(size_t)b * g.E_z + e] = msg[g.E_x + e];
+            for (int e = lane; e < g.E_z; e += tpc) a.msg_out_z[(size_t)b * g.E_z + e] = msg[g.E_x + e];
     }
     // The binary LLRs go to LDS where the messages were; totals are computed first by every thread,
     // parked in global memory (llr_out), and only then may the message area be overwritten.
@@ -776,11 +837,11 @@ bp4_kernel(GraphDev g, BpArgs a)
         if constexpr (LREG) {
 #pragma unroll
             for (int i = 0; i < NQ; ++i) {
-                const int v = lane + i * a.tpc;
+                const int v = lane + i * tpc;
                 if (v < n) total_body(v, lreg[0][i], lreg[1][i], lreg[2][i]);
             }
         } else {
-            for (int v = lane; v < n; v += a.tpc) {
+            for (int v = lane; v < n; v += tpc) {
                 if (a.llr_ch) total_body(v, Lch[v], Lch[n + v], Lch[2 * n + v]);
                 else total_body(v, a.llr_const, a.llr_const, a.llr_const);
             }
@@ -795,14 +856,14 @@ bp4_kernel(GraphDev g, BpArgs a)
         unsigned* fword = reinterpret_cast<unsigned*>(dec + ((n + 3) & ~3));
         __syncthreads();
         if (active)
-            for (int v = lane; v < n; v += a.tpc) {  // the thread's own decisions again, from its own writes
+            for (int v = lane; v < n; v += tpc) {  // the thread's own decisions again, from its own writes
                 dec[v] = (uint8_t)(a.x_hat[(size_t)b * n + v] | (a.z_hat[(size_t)b * n + v] << 1));
             }
         if (lane == 0) *fword = 0u;
         __syncthreads();
         unsigned mine = 0;
         if (active)
-            for (int c = lane; c < g.m; c += a.tpc) {
+            for (int c = lane; c < g.m; c += tpc) {
                 const int sh = c < g.m_x ? 1 : 0;
                 unsigned par = (c < g.m_x ? sx[c] : sz[c - g.m_x]) & 1u;
                 for (int e = g.cptr[c]; e < g.cptr[c + 1]; ++e) par ^= (dec[g.cvn[e]] >> sh) & 1u;
@@ -817,7 +878,7 @@ bp4_kernel(GraphDev g, BpArgs a)
     float* llx = msg;      // [n] llr_x of cal_logit
     float* llz = msg + n;  // [n] llr_z
     if (active)
-        for (int v = lane; v < n; v += a.tpc) {
+        for (int v = lane; v < n; v += tpc) {
             const float* o = a.llr_out + (size_t)b * 3 * n;
             const float X = o[v], Y = o[n + v], Z = o[2 * n + v];  // own writes: visible to this thread
             // same exact shortcut as in the qubit phase: softplus beyond its threshold, log(1 + exp(-d)) = log 1 = 0 for d >= 20
@@ -834,12 +895,12 @@ bp4_kernel(GraphDev g, BpArgs a)
     __syncthreads();
     if (active) {
         if (a.x_logit)
-            for (int r = lane; r < g.rows[0]; r += a.tpc) {
+            for (int r = lane; r < g.rows[0]; r += tpc) {
                 const int p0 = g.rptr[0][r];
                 a.x_logit[(size_t)b * g.rows[0] + r] = logit_row_opt<HWT>(llx, g.rcol[0] + p0, g.rptr[0][r + 1] - p0, phi0, opt_shortcut);
             }
         if (a.z_logit)
-            for (int r = lane; r < g.rows[1]; r += a.tpc) {
+            for (int r = lane; r < g.rows[1]; r += tpc) {
                 const int p0 = g.rptr[1][r];
                 a.z_logit[(size_t)b * g.rows[1] + r] = logit_row_opt<HWT>(llz, g.rcol[1] + p0, g.rptr[1][r + 1] - p0, phi0, opt_shortcut);
             }
@@ -850,12 +911,17 @@ using Bp4Kernel = void (*)(GraphDev, BpArgs);
 
 // The benchmark codes' kernels carry the form of the qubit update as a compile-time argument (LSE = 0 literal / 1 shared):
 // the (3,3,6) phi kernels indexed by [lreg 0 / 4 / 5][shortcut][LSE].
-template <int NQ, bool OPT, int LSE>
-constexpr Bp4Kernel bp4_lse_kernel = bp4_kernel<FGNN_CN_BOXPLUS_PHI, 3, 3, 6, OPT, false, NQ, false, false, LSE>;
+template <int NQ, bool OPT, int LSE, int NT = 0>
+constexpr Bp4Kernel bp4_lse_kernel = bp4_kernel<FGNN_CN_BOXPLUS_PHI, 3, 3, 6, OPT, false, NQ, false, false, LSE, NT>;
 constexpr Bp4Kernel bp4_lse_kernels[3][2][2] = {
     {{bp4_lse_kernel<0, false, 0>, bp4_lse_kernel<0, false, 1>}, {bp4_lse_kernel<0, true, 0>, bp4_lse_kernel<0, true, 1>}},
     {{bp4_lse_kernel<4, false, 0>, bp4_lse_kernel<4, false, 1>}, {bp4_lse_kernel<4, true, 0>, bp4_lse_kernel<4, true, 1>}},
     {{bp4_lse_kernel<5, false, 0>, bp4_lse_kernel<5, false, 1>}, {bp4_lse_kernel<5, true, 0>, bp4_lse_kernel<5, true, 1>}}};
+
+// first decoder (one constant channel LLR) with compile-time trips: [nt 4 / 5][shortcut][LSE]
+constexpr Bp4Kernel bp4_nt_kernels[2][2][2] = {
+    {{bp4_lse_kernel<0, false, 0, 4>, bp4_lse_kernel<0, false, 1, 4>}, {bp4_lse_kernel<0, true, 0, 4>, bp4_lse_kernel<0, true, 1, 4>}},
+    {{bp4_lse_kernel<0, false, 0, 5>, bp4_lse_kernel<0, false, 1, 5>}, {bp4_lse_kernel<0, true, 0, 5>, bp4_lse_kernel<0, true, 1, 5>}}};
 
 template <int CN_TYPE, int DVX, int DVZ, int DC>
 int launch_bp4_k(const fgnn_graph* g, const BpArgs& a, const LaunchGeom& L, size_t lds_bytes, hipStream_t st)
@@ -868,6 +934,7 @@ int launch_bp4_k(const fgnn_graph* g, const BpArgs& a, const LaunchGeom& L, size
         if (a.hwt) kern = bp4_kernel<CN_TYPE, DVX, DVZ, DC, false, true>;  // opt-in, fixed dataflow (fgnn_graph_set_option 3)
         if constexpr (DVX == 3 && DVZ == 3 && DC == 6) {
             if (!a.trace_x && !a.hwt) kern = bp4_lse_kernels[a.lreg ? a.lreg - 3 : 0][a.shortcut][a.shared_lse];
+            if (!a.trace_x && !a.hwt && a.nt) kern = bp4_nt_kernels[a.nt - 4][a.shortcut][a.shared_lse];
         }
     }
     return fgnn_launch(kern, dim3(L.blocks), dim3(L.threads), lds_bytes, st, g->d, a);
@@ -893,7 +960,7 @@ int launch_bp4(const fgnn_graph* g, const BpArgs& a, const LaunchGeom& L, const 
     return launch_bp4_k<CN_TYPE, 0, 0, 0>(g, a, L, p.lds_bytes, st);
 }
 
-// Fills the layout and variant fields of `a` (lch_off, lreg, trace_off, sig_off, early_exit, flag_off, lds_per_cw, shortcut, hwt,
+// Fills the layout and variant fields of `a` (lch_off, lreg, nt, trace_off, sig_off, early_exit, flag_off, lds_per_cw, shortcut, hwt,
 // shared_lse) from the graph, its options and the optional buffers set in `a`.  A codeword whose state does not fit a CU's LDS is
 // planned again with gmem = true: no LDS budget, one global-memory workspace row per codeword.
 Bp4Plan plan_bp4(const fgnn_graph* g, int cn_type, const LaunchGeom& L, BpArgs& a, bool gmem = false)
@@ -909,9 +976,15 @@ Bp4Plan plan_bp4(const fgnn_graph* g, int cn_type, const LaunchGeom& L, BpArgs& 
     // floats per codeword: messages (>= 2n so the epilogue's binary LLRs fit) + channel LLRs (unless they fit the registers of
     // the NQ variant: regular (3,3,6) graph, phi rule, exact math, one codeword per workgroup, 4 or 5 qubits per thread)
     a.lch_off = d.E > 2 * n ? d.E : 2 * n;
-    const int per_thread = (n + L.tpc - 1) / L.tpc;
+    const int per_thread = (n + L.tpc - 1) / L.tpc, per_thread_c = (d.m + L.tpc - 1) / L.tpc;  // qubits / checks a thread owns
+    const int trips = per_thread > per_thread_c ? per_thread : per_thread_c;
     const bool r336 = d.cslot16 && !g->force_generic && d.dvx == 3 && d.dvz == 3 && d.dc == 6;
-    a.lreg = (a.llr_ch && !trace && !a.hwt && !gmem && phi && L.cpb == 1 && r336 && per_thread <= 5) ? (per_thread <= 4 ? 4 : 5) : 0;
+    const bool fixed_trips = !trace && !a.hwt && !gmem && phi && L.cpb == 1 && r336;
+    // (NQ counts the check trips too, so the larger of the two decides: a (3,3,6) graph with more checks than 5 * tpc keeps its channel
+    // LLRs in LDS even when its qubits alone would fit the registers)
+    a.lreg = (a.llr_ch && fixed_trips && trips <= 5) ? (trips <= 4 ? 4 : 5) : 0;
+    // one constant channel LLR, 256 threads, as many checks as qubits per thread and the last trip the only partial one
+    a.nt = (!a.llr_ch && fixed_trips && L.tpc == 256 && per_thread == per_thread_c && (trips == 4 || trips == 5)) ? trips : 0;
     int per = a.lch_off + ((a.llr_ch && !a.lreg) ? 3 * n : 0);
     a.trace_off = 0;
     if (trace) {  // 2n binary LLRs of the per-iteration soft syndromes, behind the messages and the channel LLRs
