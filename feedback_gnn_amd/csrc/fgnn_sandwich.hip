@@ -118,8 +118,10 @@ extern "C" int fgnn_sandwich_decode(const fgnn_graph* g, int num_layers, const i
     int rc;
     // decoders[0] on the constant channel LLR (feedback_gnn.py:311-313,321)
     const bool only = num_layers == 1;  // no feedback round: nobody reads the soft syndromes
-    // One codeword per workgroup (every code of >= 256 nodes): the decoders' epilogues compute the flag test of the next round
-    // (does the estimate reproduce the syndrome?), so no separate pass re-reads x_hat / z_hat.  errors_1 = all-true & flagged (:322-330).
+    // One codeword per workgroup (the default launch of every code of >= 64 nodes): the decoders' epilogues compute the flag test of the
+    // next round (does the estimate reproduce the syndrome?), so no separate pass re-reads x_hat / z_hat.  errors_1 = all-true & flagged
+    // (:322-330).  Smaller codes, and any code after fgnn_graph_set_launch(.., cpb >= 2), pack several codewords into a workgroup and
+    // take fill_u8 + fgnn_flag_update instead.
     const bool fuse = g->cpb == 1;
     rc = fgnn_bp4_decode_impl(g, cn_types[0], iters[0], factors[0], nullptr, llr_const, synd_x, synd_z, B, nullptr, nullptr,
                               ws.llr_a, x_hat, z_hat, only ? nullptr : ws.xlogit, only ? nullptr : ws.zlogit, nullptr, nullptr,

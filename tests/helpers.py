@@ -117,6 +117,25 @@ def gnnbp4_weights(seed):
     return w
 
 
+# Feedback_GNN constructor settings (num_msg_dims, num_hidden_units, num_mlp_layers, reduce_op, activation, use_bias): the shipped one
+# first, then settings only the runtime-shaped kernel takes
+GEN_CONFIGS = [(20, 40, 2, "mean", "tanh", True), (8, 16, 1, "max", "relu", False), (12, 24, 3, "sum", "sigmoid", True),
+               (5, 7, 2, "min", None, True), (32, 96, 4, "mean", "relu", False)]
+
+
+def gen_weights(cfg, seed=3):
+    """Seeded uniform(-0.5, 0.5) Feedback_GNN weights in the shapes of one constructor setting."""
+    from feedback_gnn_amd.graph import gnn_weight_shapes
+    rng = np.random.RandomState(seed)
+    return [rng.uniform(-0.5, 0.5, size=s).astype(np.float32) for s in gnn_weight_shapes(cfg[0], cfg[1], cfg[2], cfg[5])]
+
+
+def gen_cfg_codes(cfg):
+    """The integer-coded setting `OracleGraph.feedback_gnn_general` takes."""
+    from feedback_gnn_amd.graph import ACTIVATIONS, REDUCE_OPS
+    return (cfg[0], cfg[1], cfg[2], REDUCE_OPS[cfg[3]], ACTIVATIONS[cfg[4]], int(cfg[5]))
+
+
 def golden_codes():
     out = dict(np.load(os.path.join(GOLDEN, "codes.npz")))
     out.update(np.load(os.path.join(GOLDEN, "overcomplete.npz")))

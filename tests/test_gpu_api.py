@@ -445,10 +445,13 @@ def test_options_round_trip_and_unknown_ids_are_refused():
     """fgnn_graph_set_option: every documented id is accepted with 0 and 1 on a live graph, anything else is an argument error whose text
     says so; the wrappers keep their mirror attributes in step."""
     from feedback_gnn_amd import _lib
-    from helpers import gpu_graph
+    from helpers import LIBRARY_BP4_SHARED_LSE, LIBRARY_GNN_FACTORED, gpu_graph
     g = gpu_graph("gb48")
     L = _lib.lib()
-    defaults = {1: 1, 2: 1, 3: 0, 4: 1, 5: 1, 6: 1}
+    # the library's defaults (fgnn_internal.h): the raw calls bypass the wrappers' mirror attributes and the graph is shared by the whole
+    # session, so each option must be LEFT at its default — options 4 and 5 at 0, the reference's formulas term by term
+    defaults = {1: 1, 2: 1, 3: 0, 4: int(LIBRARY_GNN_FACTORED), 5: int(LIBRARY_BP4_SHARED_LSE), 6: 1}
+    assert defaults[4] == 0 and defaults[5] == 0
     for opt, dflt in defaults.items():
         for v in (0, 1, dflt):
             assert L.fgnn_graph_set_option(g.handle, opt, v) == 0, opt

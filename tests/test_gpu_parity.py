@@ -13,6 +13,7 @@ import torch
 
 from helpers import (LIBRARY_BP4_SHARED_LSE, LIBRARY_GNN_FACTORED, WEIGHTS_882, WEIGHTS_1270, code, gnnbp4_weights, gpu_graph, llr_const,
                      oracle_library_forms, to_gpu)
+from helpers import GEN_CONFIGS, gen_cfg_codes as _cfg_codes, gen_weights as _gen_weights
 
 pytestmark = pytest.mark.gpu
 
@@ -846,21 +847,6 @@ def test_published_rows_plain_bp4(name, iters, factor, p0, p, flagged, block, to
         r = pub / total
         sigma = np.sqrt(r * (1 - r) * (1 / total + 1 / n))
         assert abs(got / n - r) < 4 * sigma + 2 / total, (name, p, got / n, r)
-
-
-GEN_CONFIGS = [(20, 40, 2, "mean", "tanh", True), (8, 16, 1, "max", "relu", False), (12, 24, 3, "sum", "sigmoid", True),
-               (5, 7, 2, "min", None, True), (32, 96, 4, "mean", "relu", False)]
-
-
-def _gen_weights(cfg, seed=3):
-    from feedback_gnn_amd.graph import gnn_weight_shapes
-    rng = np.random.RandomState(seed)
-    return [rng.uniform(-0.5, 0.5, size=s).astype(np.float32) for s in gnn_weight_shapes(cfg[0], cfg[1], cfg[2], cfg[5])]
-
-
-def _cfg_codes(cfg):
-    from feedback_gnn_amd.graph import ACTIVATIONS, REDUCE_OPS
-    return (cfg[0], cfg[1], cfg[2], REDUCE_OPS[cfg[3]], ACTIVATIONS[cfg[4]], int(cfg[5]))
 
 
 @pytest.mark.parametrize("cfg", GEN_CONFIGS)
