@@ -71,6 +71,8 @@ _SIGNATURES = {
     "fgnn_graph_force_generic": (C.c_int, [C.c_void_p, C.c_int]),
     "fgnn_graph_info": (C.c_int, [C.c_void_p, C.c_void_p]),
     "fgnn_graph_edges": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "fgnn_check_rows": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p]),
     "fgnn_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "fgnn_profile_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "fgnn_bp4_decode": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p,

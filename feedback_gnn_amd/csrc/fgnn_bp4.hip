@@ -10,7 +10,7 @@
 // Here a codeword's state (E floats of messages, 21 KB for [[882,24]], in LDS; per-qubit channel LLRs in registers for the
 // benchmark codes, else 3n more floats of LDS) never leaves the CU: HBM sees the syndromes once and the results once.  The kernel is therefore bound
 // by VALU issue (about 800 VALU instructions per node-iteration for the exact exp/log of
-// fgnn_math.h, all but the six slot unpacks per check inside the float routines), not by HBM; DESIGN.md §4 gives the accounting next to the streaming-model figure.
+// fgnn_math.h, in the benchmark's kernels all of them inside the float routines), not by HBM; DESIGN.md §4 gives the accounting next to the streaming-model figure.
 //
 // Message layout in LDS: slot e in [0,E_x) = hx edges, [E_x,E) = hz edges, both sorted by
 // (qubit, check).  The VN phase reads/writes a contiguous run per qubit; the CN phase gathers its
@@ -43,6 +43,9 @@
 #endif
 
 namespace {
+
+// static LDS of every bp4_kernel: the log table of fgnn_math.h (FG_LOG_TAB_SETUP) and nothing else, so the dynamic LDS starts here
+constexpr int BP4_STATIC_LDS = 64 * (int)sizeof(float);
 
 struct BpArgs {
     int B, num_iter, tpc, cpb, lds_per_cw, lch_off;  // per-codeword LDS floats; offset of the channel LLRs
@@ -146,6 +149,26 @@ __device__ __forceinline__ float logit_row_opt(const float* llr, const int* __re
     return logit_row<Mx<HWT>>(llr, col, deg);
 }
 
+// The same row from phi(|llr[v]|) evaluated once per qubit and parked in `phis`: a qubit sits in several rows, and its phi is the same
+// float in each.  The sum runs over the row's entries in the same order and the sign parity still comes from the binary LLRs, so the
+// result — exact shortcut included — is logit_row_opt's bit for bit.
+__device__ __forceinline__ float logit_row_ready(const float* llr, const float* phis, const int* __restrict__ col, int deg, float phi0,
+                                                 bool shortcut)
+{
+    unsigned neg = 0;
+    bool sat = true;
+    float T = 0.0f;
+    for (int j = 0; j < deg; ++j) {
+        const int c = col[j];
+        const float v = llr[c];
+        neg ^= (v < 0.0f);
+        sat = sat && (FG_ABS(v) >= FG_PHI_MAX);
+        T = T + phis[c];
+    }
+    if (shortcut && __all(sat)) return with_sign(phi0, neg);
+    return with_sign(Mx<false>::phi(T), neg);
+}
+
 // N evaluations of fg_phi (fgnn_math.h) with the work of the N lanes-worth of values laid out in three stages, so that the 2N table
 // reads of the logs are in flight together instead of one read - wait - use per log: (A) clamp, exp, the two log arguments and
 // their table addresses; (B) the 2N two-dword LDS reads; (C) remainders, polynomials, assembly.  Every value goes through exactly
@@ -202,7 +225,18 @@ __device__ __forceinline__ void phi_n(const float (&x)[N], float (&out)[N])
 // `neg0` = a word whose bit 31 is the check's syndrome bit (its other bits never reach a result: only bit 31 of `neg` is used).
 // `sl` = BYTE offsets of the check's slots from `msg` (the packed rows of g.cslot16 hold 4 * slot); F1 = the normalisation factor is
 // exactly 1 (feedback_gnn.py / n882.py: every paper run), so the product with it — the identity on every float — is not issued.
-template <int DC, bool HWT = false, bool F1 = false>
+// LDSB >= 0: `sl` counts from the base of the workgroup's dynamic LDS, which LDSB bytes of static LDS precede (`msg` is not used):
+// the slot is addressed as LDS address sl + LDSB, so the loaded offset is the instruction's address operand as it is and the base its
+// immediate offset.  (Written as lds + sl the compiler adds the base to every offset with a vector instruction of its own: to it the
+// address of the dynamic LDS is a symbol until after instruction selection.)  The launch checks LDSB against the kernel's attributes.
+typedef __attribute__((address_space(3))) float lds_float;
+template <int LDSB, typename IDX>
+__device__ __forceinline__ decltype(auto) cn_slot(float* msg, IDX byte_off)
+{
+    if constexpr (LDSB >= 0) return *(lds_float*)(uintptr_t)((unsigned)byte_off + (unsigned)LDSB);
+    else return slot_ref(msg, byte_off);
+}
+template <int DC, bool HWT = false, bool F1 = false, int LDSB = -1>
 __device__ __forceinline__ bool cn_phi_regular(float* msg, const int (&sl)[DC], uint32_t neg0, float factor, float phi0,
                                                bool shortcut)
 {
@@ -213,7 +247,7 @@ __device__ __forceinline__ bool cn_phi_regular(float* msg, const int (&sl)[DC], 
     bool sat = true;
 #pragma unroll
     for (int j = 0; j < DC; ++j) {
-        v[j] = slot_ref(msg, sl[j]);
+        v[j] = cn_slot<LDSB>(msg, sl[j]);
         neg ^= fg_f2u(v[j]);
         sat = sat && (FG_ABS(v[j]) >= FG_PHI_MAX);
     }
@@ -224,7 +258,7 @@ __device__ __forceinline__ bool cn_phi_regular(float* msg, const int (&sl)[DC], 
 #pragma unroll
         for (int j = 0; j < DC; ++j) {
             const float o = fg_u2f(fg_f2u(phi0) | ((neg ^ fg_f2u(v[j])) & 0x80000000u));
-            slot_ref(msg, sl[j]) = F1 ? o : o * factor;
+            cn_slot<LDSB>(msg, sl[j]) = F1 ? o : o * factor;
         }
         return true;
     }
@@ -249,7 +283,7 @@ __device__ __forceinline__ bool cn_phi_regular(float* msg, const int (&sl)[DC], 
 #pragma unroll
         for (int j = 0; j < H; ++j) {
             const float o = fg_u2f(fg_f2u(oa[j]) | ((neg ^ fg_f2u(v[g0 + j])) & 0x80000000u));
-            slot_ref(msg, sl[g0 + j]) = F1 ? o : o * factor;
+            cn_slot<LDSB>(msg, sl[g0 + j]) = F1 ? o : o * factor;
         }
     }
     return false;
@@ -315,7 +349,8 @@ __device__ __forceinline__ float softplus_saturated(float t)
 
 // DVX/DVZ/DC > 0: every qubit has exactly DVX hx-edges and DVZ hz-edges and every check DC edges, so a
 // qubit's slots are v*DVX+k / E_x+v*DVZ+k (no index loads) and a check's DC slots come as one packed
-// 16-byte row of g.cslot16.  DVX = 0: runtime degrees through the CSR tables.
+// 16-byte row of g.cslot16 — in the kernels with compile-time trips (NQ, NT below) as a row of g.cslot32, unpacked at the upload.  DVX = 0:
+// runtime degrees through the CSR tables.
 // OPT = false compiles the exact optimisations (saturation shortcut, fixed-point detector) out: the fixed-dataflow
 // variant bench.py's headline times carries none of their tests.
 // NQ > 0: per-qubit channel LLRs (llr_ch != null: every decoder of a sandwich but the first) live in REGISTERS, 3 x NQ per thread
@@ -336,7 +371,7 @@ __device__ __forceinline__ float softplus_saturated(float t)
 // ms either way); what they buy is one kernel SYMBOL per form, so that a rocprofv3 trace or PMC pass prices each form by itself.
 // NT > 0 (NQ = 0, one constant channel LLR, one codeword per workgroup of 256 threads): a thread owns exactly NT qubits and NT checks
 // (ceil(n / 256) == ceil(m / 256) == NT, from the launch plan), the last of each only if it exists.  The trips of both phases are
-// unrolled at compile time: a qubit's slots are one per-thread LDS base plus an immediate offset, a check's packed row is a scalar base
+// unrolled at compile time: a qubit's slots are one per-thread LDS base plus an immediate offset, a check's row is a scalar base
 // plus one per-thread offset, and no counter, pointer or bounds test is carried through the iteration loop.  The NQ > 0 kernels run
 // their checks the same way with NQ trips, each guarded (their threads-per-codeword is a launch argument).
 template <int CN_TYPE, int DVX, int DVZ, int DC, bool OPT, bool HWT = false, int NQ = 0, bool TRACE = false, bool GMEM = false, int LSE = 2,
@@ -353,6 +388,9 @@ bp4_kernel(GraphDev g, BpArgs a)
     constexpr int NQA = LREG ? NQ : 1;
     static_assert(NT == 0 || (DVX > 0 && CN_TYPE == FGNN_CN_BOXPLUS_PHI && !LREG && !TRACE && !GMEM), "compile-time trips: the regular phi kernel");
     constexpr int CT = LREG ? NQ : NT;  // compile-time trips of the check phase (0: the runtime loop)
+    // these kernels (one codeword per workgroup, a thread owns at most CT qubits, the graph carries g.cslot32 and g.cvn16) also run the
+    // epilogue on ready-made rows: decisions kept in registers, a check's qubits from its g.cvn16 row, phi(|llr|) once per qubit
+    constexpr bool READY = REGULAR && CT > 0 && CN_TYPE == FGNN_CN_BOXPLUS_PHI && !HWT;
     const int tpc = NT > 0 ? 256 : a.tpc;
     const bool opt_shortcut = OPT && a.shortcut != 0;
     const bool opt_exit = OPT && a.early_exit != 0;
@@ -466,7 +504,7 @@ bp4_kernel(GraphDev g, BpArgs a)
         for (int c = lane_c; c < g.m && i < 32; c += tpc, ++i) synd_bits |= ((c < g.m_x ? sx[c] : sz[c - g.m_x]) & 1u) << i;
     }
     const bool synd_in_reg = (g.m + tpc - 1) / tpc <= 32;
-    unsigned row_off = 16u * (unsigned)lane_c;  // CT > 0: byte offset of the thread's packed check rows from each trip's base
+    unsigned row_off = 32u * (unsigned)lane_c;  // CT > 0: byte offset of the thread's check rows (g.cslot32) from each trip's base
     // TRACE: soft syndromes of the current messages into slot k of the trace (cal_logit :455-471 on the totals of :244-248)
     auto trace_step = [&](const int k) __attribute__((always_inline)) {
         float* tlx = msg + a.trace_off;  // [n] llr_x of cal_logit, then [n] llr_z
@@ -728,14 +766,14 @@ bp4_kernel(GraphDev g, BpArgs a)
         // checks are dealt to the threads half a workgroup out of phase with the qubits: with 882 nodes on 4 waves two waves get
         // 4 slices of 64 and two get 3 — the qubit phase gives the extra slice to the low waves, the check phase to the high ones
         if constexpr (REGULAR && CT > 0 && CN_TYPE == FGNN_CN_BOXPLUS_PHI) {
-            // Compile-time trips (one codeword per workgroup: the message area starts at the base of the dynamic LDS).  The packed row
-            // of check lane_c + i * tpc is read from a scalar base, bumped per trip by scalar adds, plus the thread's byte offset
-            // 16 * lane_c, formed once per launch; its syndrome bit is moved to bit 31 by one shift with a constant count; the two
+            // Compile-time trips (one codeword per workgroup: the message area starts at the base of the dynamic LDS).  The g.cslot32
+            // row of check lane_c + i * tpc is read from a scalar base, bumped per trip by scalar adds, plus the thread's byte offset
+            // 32 * lane_c, formed once per launch; its syndrome bit is moved to bit 31 by one shift with a constant count; the two
             // copies of the update (factor == 1 / != 1) are chosen once per iteration, not once per check.  The rows are read again
             // every iteration: four or five of them resident would cost 16 to 20 registers, and the load is not the cost.
             auto cn_trips = [&](auto f1) __attribute__((always_inline)) {
                 constexpr bool F1 = decltype(f1)::value;
-                const char* rows = reinterpret_cast<const char*>(g.cslot16);
+                const char* rows = reinterpret_cast<const char*>(g.cslot32);
 #pragma unroll
                 for (int i = 0; i < CT; ++i) {
                     const bool in = (!LREG && i + 1 < CT) || lane_c + i * tpc < g.m;
@@ -744,16 +782,21 @@ bp4_kernel(GraphDev g, BpArgs a)
                         // addresses once per launch and keeps them in 2 * CT registers, or folds a compile-time stride into a 64-bit
                         // vector add per row; the two empty statements make the offset and the trip's base opaque to it right here and
                         // emit nothing.  (A pointer that went through one is generic: the cast says again that it is global memory.)
-                        const char* base = rows + (size_t)i * (size_t)(16u * (unsigned)tpc);
+                        // The row holds the slots' byte offsets as 32-bit values, which is what the LDS instructions take as their address
+                        // (the base of the dynamic LDS is their immediate offset): the loaded dwords go to cn_phi_regular as they are.
+                        static_assert(DC > 4 && DC <= 8, "a cslot32 row is read as four dwords and two or four more");
+                        const char* base = rows + (size_t)i * (size_t)(32u * (unsigned)tpc);
                         asm volatile("" : "+v"(row_off));
                         if constexpr (NT > 0) asm volatile("" : "+s"(base));
-                        typedef unsigned Row __attribute__((ext_vector_type(4)));
-                        const Row pk = *(const __attribute__((address_space(1))) Row*)(base + row_off);
-                        const unsigned w[4] = {pk.x, pk.y, pk.z, pk.w};
+                        typedef unsigned Row4 __attribute__((ext_vector_type(4)));
+                        typedef unsigned Row2 __attribute__((ext_vector_type(2)));
+                        typedef std::conditional_t<(DC > 6), Row4, Row2> RowT;
+                        const Row4 pk = *(const __attribute__((address_space(1))) Row4*)(base + row_off);
+                        const RowT pt = *(const __attribute__((address_space(1))) RowT*)(base + row_off + 16);
                         int sl[DC];  // byte offsets
 #pragma unroll
-                        for (int j = 0; j < DC; ++j) sl[j] = (int)((w[j >> 1] >> ((j & 1) * 16)) & 0xffffu);
-                        const bool fast = cn_phi_regular<DC, HWT, F1>(lds, sl, synd_bits << (31 - i), F1 ? 1.0f : a.factor, phi0, opt_shortcut);
+                        for (int j = 0; j < DC; ++j) sl[j] = (int)(j < 4 ? pk[j] : pt[j - 4]);
+                        const bool fast = cn_phi_regular<DC, HWT, F1, BP4_STATIC_LDS>(lds, sl, synd_bits << (31 - i), F1 ? 1.0f : a.factor, phi0, opt_shortcut);
                         cn_slow = !fast || cn_slow;
                     }
                 }
@@ -832,13 +875,22 @@ bp4_kernel(GraphDev g, BpArgs a)
             if (Y < best) { best = Y; d = 3; }
             a.x_hat[(size_t)b * n + v] = (uint8_t)(d & 1);
             a.z_hat[(size_t)b * n + v] = (uint8_t)(d >> 1);
+            return (unsigned)d;
     };
+    unsigned dbits = 0;  // READY: the decisions of the thread's qubits lane + i * tpc, two bits each (x_hat | z_hat << 1)
+    (void)dbits;
     if (active) {
         if constexpr (LREG) {
 #pragma unroll
             for (int i = 0; i < NQ; ++i) {
                 const int v = lane + i * tpc;
-                if (v < n) total_body(v, lreg[0][i], lreg[1][i], lreg[2][i]);
+                if (v < n) dbits |= total_body(v, lreg[0][i], lreg[1][i], lreg[2][i]) << (2 * i);
+            }
+        } else if constexpr (NT > 0) {
+#pragma unroll
+            for (int i = 0; i < NT; ++i) {
+                const int v = lane + i * 256;
+                if (i + 1 < NT || v < n) dbits |= total_body(v, a.llr_const, a.llr_const, a.llr_const) << (2 * i);
             }
         } else {
             for (int v = lane; v < n; v += tpc) {
@@ -855,10 +907,19 @@ bp4_kernel(GraphDev g, BpArgs a)
         uint8_t* dec = reinterpret_cast<uint8_t*>(msg + a.flag_off);
         unsigned* fword = reinterpret_cast<unsigned*>(dec + ((n + 3) & ~3));
         __syncthreads();
-        if (active)
+        if constexpr (READY) {
+            if (active) {  // the thread's own decisions, still in its registers
+#pragma unroll
+                for (int i = 0; i < CT; ++i) {
+                    const int v = lane + i * tpc;
+                    if (v < n) dec[v] = (uint8_t)((dbits >> (2 * i)) & 3u);
+                }
+            }
+        } else if (active) {
             for (int v = lane; v < n; v += tpc) {  // the thread's own decisions again, from its own writes
                 dec[v] = (uint8_t)(a.x_hat[(size_t)b * n + v] | (a.z_hat[(size_t)b * n + v] << 1));
             }
+        }
         if (lane == 0) *fword = 0u;
         __syncthreads();
         unsigned mine = 0;
@@ -866,7 +927,16 @@ bp4_kernel(GraphDev g, BpArgs a)
             for (int c = lane; c < g.m; c += tpc) {
                 const int sh = c < g.m_x ? 1 : 0;
                 unsigned par = (c < g.m_x ? sx[c] : sz[c - g.m_x]) & 1u;
-                for (int e = g.cptr[c]; e < g.cptr[c + 1]; ++e) par ^= (dec[g.cvn[e]] >> sh) & 1u;
+                if constexpr (READY) {  // the check's qubits as one 16-byte row
+                    const uint4 pk = reinterpret_cast<const uint4*>(g.cvn16)[c];
+                    const unsigned w[4] = {pk.x, pk.y, pk.z, pk.w};
+                    unsigned acc = 0;
+#pragma unroll
+                    for (int j = 0; j < DC; ++j) acc ^= dec[(w[j >> 1] >> ((j & 1) * 16)) & 0xffffu];
+                    par ^= (acc >> sh) & 1u;
+                } else {
+                    for (int e = g.cptr[c]; e < g.cptr[c + 1]; ++e) par ^= (dec[g.cvn[e]] >> sh) & 1u;
+                }
                 mine |= par;
             }
         if (mine) atomicOr(fword, 1u);
@@ -877,6 +947,8 @@ bp4_kernel(GraphDev g, BpArgs a)
     __syncthreads();  // every thread is done reading messages
     float* llx = msg;      // [n] llr_x of cal_logit
     float* llz = msg + n;  // [n] llr_z
+    float* plx = msg + 2 * n;  // READY: [n] phi(|llr_x|), [n] phi(|llr_z|) beside them (the message area holds E >= 4n floats; the
+    float* plz = msg + 3 * n;  // decision bytes of the flag test, which may lie here, were last read before the barrier above)
     if (active)
         for (int v = lane; v < n; v += tpc) {
             const float* o = a.llr_out + (size_t)b * 3 * n;
@@ -884,25 +956,39 @@ bp4_kernel(GraphDev g, BpArgs a)
             // same exact shortcut as in the qubit phase: softplus beyond its threshold, log(1 + exp(-d)) = log 1 = 0 for d >= 20
             const bool sat = opt_shortcut && FG_ABS(X) > FG_SOFTPLUS_THRESH && FG_ABS(Z) > FG_SOFTPLUS_THRESH &&
                              FG_ABS((-Z) - (-Y)) >= 20.0f && FG_ABS((-X) - (-Y)) >= 20.0f;
+            float lzv, lxv;
             if (opt_shortcut && __all(sat)) {
-                llz[v] = softplus_saturated(-X) - (0.0f + FG_MAX(-Z, -Y));
-                llx[v] = softplus_saturated(-Z) - (0.0f + FG_MAX(-X, -Y));
-                continue;
+                lzv = softplus_saturated(-X) - (0.0f + FG_MAX(-Z, -Y));
+                lxv = softplus_saturated(-Z) - (0.0f + FG_MAX(-X, -Y));
+            } else {
+                lzv = MX::softplus(-X) - MX::lse2(-Z, -Y);
+                lxv = MX::softplus(-Z) - MX::lse2(-X, -Y);
             }
-            llz[v] = MX::softplus(-X) - MX::lse2(-Z, -Y);
-            llx[v] = MX::softplus(-Z) - MX::lse2(-X, -Y);
+            llz[v] = lzv;
+            llx[v] = lxv;
+            if constexpr (READY) {  // the qubit's two phi values, staged as a pair like the hot loop's
+                const float xa[2] = {FG_ABS(lxv), FG_ABS(lzv)};
+                float oa[2];
+                phi_n<2, false>(xa, oa);
+                plx[v] = oa[0];
+                plz[v] = oa[1];
+            }
         }
     __syncthreads();
+    auto soft_row = [&](const float* llr, const float* phis, const int* col, const int deg) __attribute__((always_inline)) {
+        if constexpr (READY) return logit_row_ready(llr, phis, col, deg, phi0, opt_shortcut);
+        else return logit_row_opt<HWT>(llr, col, deg, phi0, opt_shortcut);
+    };
     if (active) {
         if (a.x_logit)
             for (int r = lane; r < g.rows[0]; r += tpc) {
                 const int p0 = g.rptr[0][r];
-                a.x_logit[(size_t)b * g.rows[0] + r] = logit_row_opt<HWT>(llx, g.rcol[0] + p0, g.rptr[0][r + 1] - p0, phi0, opt_shortcut);
+                a.x_logit[(size_t)b * g.rows[0] + r] = soft_row(llx, plx, g.rcol[0] + p0, g.rptr[0][r + 1] - p0);
             }
         if (a.z_logit)
             for (int r = lane; r < g.rows[1]; r += tpc) {
                 const int p0 = g.rptr[1][r];
-                a.z_logit[(size_t)b * g.rows[1] + r] = logit_row_opt<HWT>(llz, g.rcol[1] + p0, g.rptr[1][r + 1] - p0, phi0, opt_shortcut);
+                a.z_logit[(size_t)b * g.rows[1] + r] = soft_row(llz, plz, g.rcol[1] + p0, g.rptr[1][r + 1] - p0);
             }
     }
 }
@@ -935,6 +1021,15 @@ int launch_bp4_k(const fgnn_graph* g, const BpArgs& a, const LaunchGeom& L, size
         if constexpr (DVX == 3 && DVZ == 3 && DC == 6) {
             if (!a.trace_x && !a.hwt) kern = bp4_lse_kernels[a.lreg ? a.lreg - 3 : 0][a.shortcut][a.shared_lse];
             if (!a.trace_x && !a.hwt && a.nt) kern = bp4_nt_kernels[a.nt - 4][a.shortcut][a.shared_lse];
+            if (!a.trace_x && !a.hwt && (a.nt || a.lreg)) {
+                // these address their check slots as dynamic-LDS offset + BP4_STATIC_LDS (cn_phi_regular<..., LDSB>): hold the
+                // compiled kernel to it (a compiler that lays the static LDS out differently must not decode silently wrong)
+                hipFuncAttributes fa;
+                FGNN_HIP_CHECK(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(kern)));
+                if (fa.sharedSizeBytes != (size_t)BP4_STATIC_LDS)
+                    return fgnn_fail(FGNN_ERR_STATE, "bp4_kernel: static LDS is " + std::to_string(fa.sharedSizeBytes) + " bytes, built for " +
+                                                         std::to_string(BP4_STATIC_LDS));
+            }
         }
     }
     return fgnn_launch(kern, dim3(L.blocks), dim3(L.threads), lds_bytes, st, g->d, a);
@@ -978,7 +1073,7 @@ Bp4Plan plan_bp4(const fgnn_graph* g, int cn_type, const LaunchGeom& L, BpArgs& 
     a.lch_off = d.E > 2 * n ? d.E : 2 * n;
     const int per_thread = (n + L.tpc - 1) / L.tpc, per_thread_c = (d.m + L.tpc - 1) / L.tpc;  // qubits / checks a thread owns
     const int trips = per_thread > per_thread_c ? per_thread : per_thread_c;
-    const bool r336 = d.cslot16 && !g->force_generic && d.dvx == 3 && d.dvz == 3 && d.dc == 6;
+    const bool r336 = d.cslot16 && d.cslot32 && d.cvn16 && !g->force_generic && d.dvx == 3 && d.dvz == 3 && d.dc == 6;
     const bool fixed_trips = !trace && !a.hwt && !gmem && phi && L.cpb == 1 && r336;
     // (NQ counts the check trips too, so the larger of the two decides: a (3,3,6) graph with more checks than 5 * tpc keeps its channel
     // LLRs in LDS even when its qubits alone would fit the registers)

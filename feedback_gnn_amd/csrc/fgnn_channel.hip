@@ -84,7 +84,9 @@ __device__ __forceinline__ unsigned row_parity(const uint8_t* x, const int* __re
 }
 
 // syndrome_x = hx noise_z ; syndrome_z = hz noise_x  (feedback_gnn.py:305-309)
-__global__ void __launch_bounds__(1024) syndrome_kernel(GraphDev g, int B, int tpc, int cpb, const uint8_t* __restrict__ ex,
+// use_rows: the graph is check-regular and carries g.cvn16 — a check's qubits come as ONE 16-byte load instead of two row pointers and
+// g.dc index loads; the CSR loop is the fallback (irregular graphs, fgnn_graph_force_generic)
+__global__ void __launch_bounds__(1024) syndrome_kernel(GraphDev g, int B, int tpc, int cpb, int use_rows, const uint8_t* __restrict__ ex,
                                                         const uint8_t* __restrict__ ez, uint8_t* __restrict__ sx,
                                                         uint8_t* __restrict__ sz)
 {
@@ -101,6 +103,21 @@ __global__ void __launch_bounds__(1024) syndrome_kernel(GraphDev g, int B, int t
         }
     __syncthreads();
     if (!active) return;
+    if (use_rows) {
+        const int dc = g.dc;
+        for (int c = lane; c < g.m; c += tpc) {
+            const uint4 pk = reinterpret_cast<const uint4*>(g.cvn16)[c];
+            const unsigned w[4] = {pk.x, pk.y, pk.z, pk.w};
+            const uint8_t* x = c < g.m_x ? lz : lx;
+            unsigned par = 0;
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                if (j < dc) par ^= x[(w[j >> 1] >> ((j & 1) * 16)) & 0xffffu];
+            if (c < g.m_x) sx[(size_t)b * g.m_x + c] = (uint8_t)(par & 1u);
+            else sz[(size_t)b * g.m_z + (c - g.m_x)] = (uint8_t)(par & 1u);
+        }
+        return;
+    }
     for (int c = lane; c < g.m; c += tpc) {
         const int p0 = g.cptr[c], p1 = g.cptr[c + 1];
         if (c < g.m_x) sx[(size_t)b * g.m_x + c] = (uint8_t)row_parity(lz, g.cvn, p0, p1);
@@ -393,7 +410,7 @@ extern "C" int fgnn_syndrome(const fgnn_graph* g, const uint8_t* noise_x, const 
     LaunchGeom L = fgnn_geom(g, B);
     size_t lds = (size_t)L.cpb * 2 * g->d.n;
     return fgnn_launch(syndrome_kernel, dim3(L.blocks), dim3(L.threads), lds, static_cast<hipStream_t>(stream), g->d, B, L.tpc,
-                       L.cpb, noise_x, noise_z, synd_x, synd_z);
+                       L.cpb, (g->d.cvn16 && !g->force_generic) ? 1 : 0, noise_x, noise_z, synd_x, synd_z);
 }
 
 int fgnn_flag_update_impl(const fgnn_graph* g, const uint8_t* x_hat, const uint8_t* z_hat, const uint8_t* synd_x,

@@ -446,11 +446,18 @@ __device__ __forceinline__ void side_stream_literal(scalar_fp rows, scalar_fp b2
     // the 40 -> 20 Dense of an edge as ten v_pk_fma_f32 per hidden unit: two consecutive message elements per instruction, their
     // weights W2[j][2i], W2[j][2i + 1] one SGPR pair (rows are 32 floats, W2 at float 8: 8-byte aligned), the per-lane tanh value
     // broadcast to both halves — each half an IEEE fma in the oracle's order (ascending j from 0)
+    // `e` is wave-uniform (a scalar loop counter), so what depends on it is a scalar branch, not a per-lane select: the first edge
+    // ASSIGNS feat where the later ones add (no sum is formed to be thrown away), and an edge's gv[e] arrives by one move.  The empty
+    // statements keep the branches branches: a block that holds one is not turned back into selects.
 #pragma unroll 1
     for (int e = 0; e < DV; ++e) {
         float ge = gv[0];
 #pragma unroll
-        for (int k = 1; k < DV; ++k) ge = e == k ? gv[k] : ge;
+        for (int k = 1; k < DV; ++k)
+            if (e == k) {
+                ge = gv[k];
+                asm volatile("" : "+v"(ge));
+            }
         f2 m[MSG / 2];
 #pragma unroll
         for (int i = 0; i < MSG / 2; ++i) m[i] = bc2(0.0f);
@@ -467,11 +474,20 @@ __device__ __forceinline__ void side_stream_literal(scalar_fp rows, scalar_fp b2
 #pragma unroll
             for (int i = 0; i < MSG / 2; ++i) m[i] = pk_fma(h, w2[i], m[i]);
         }
+        if (e == 0) {
 #pragma unroll
-        for (int i = 0; i < MSG / 2; ++i) {
-            const float m0 = m[i].x + b2[2 * i], m1 = m[i].y + b2[2 * i + 1];
-            feat[2 * i] = (e == 0) ? m0 : feat[2 * i] + m0;
-            feat[2 * i + 1] = (e == 0) ? m1 : feat[2 * i + 1] + m1;
+            for (int i = 0; i < MSG / 2; ++i) {
+                feat[2 * i] = m[i].x + b2[2 * i];
+                feat[2 * i + 1] = m[i].y + b2[2 * i + 1];
+            }
+            asm volatile("" : "+v"(feat[0]));
+        } else {
+#pragma unroll
+            for (int i = 0; i < MSG / 2; ++i) {
+                const float m0 = m[i].x + b2[2 * i], m1 = m[i].y + b2[2 * i + 1];
+                feat[2 * i] = feat[2 * i] + m0;
+                feat[2 * i + 1] = feat[2 * i + 1] + m1;
+            }
         }
     }
 #pragma unroll

@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <cstring>
 #include <numeric>
+#include <optional>
 
 #include "fgnn_internal.h"
 
@@ -25,6 +26,10 @@ namespace {
 template <typename T>
 int upload(fgnn_graph* g, const std::vector<T>& h, const T** dst)
 {
+    if (g->host_only) {  // fgnn_check_rows: the tables are built and kept on the host, no device is touched
+        *dst = nullptr;
+        return FGNN_OK;
+    }
     void* p = nullptr;
     size_t bytes = std::max<size_t>(h.size(), 1) * sizeof(T);
     FGNN_HIP_CHECK(hipMalloc(&p, bytes));
@@ -101,8 +106,9 @@ LaunchGeom fgnn_geom(const fgnn_graph* g, int B)
     return L;
 }
 
-extern "C" int fgnn_graph_create(int n, int m_x, int m_z, int nnz_x, const int32_t* chk_x, const int32_t* var_x,
-                                 int nnz_z, const int32_t* chk_z, const int32_t* var_z, int device, fgnn_graph** out)
+// fgnn_graph_create; host_only: build every table on the host and upload none (fgnn_check_rows)
+static int graph_build(int n, int m_x, int m_z, int nnz_x, const int32_t* chk_x, const int32_t* var_x, int nnz_z,
+                       const int32_t* chk_z, const int32_t* var_z, int device, bool host_only, fgnn_graph** out)
 {
     if (!out) return fgnn_fail(FGNN_ERR_ARG, "out is NULL");
     if (n <= 0 || m_x <= 0 || m_z <= 0 || nnz_x <= 0 || nnz_z <= 0)
@@ -115,8 +121,14 @@ extern "C" int fgnn_graph_create(int n, int m_x, int m_z, int nnz_x, const int32
         for (int i = 0; i < nnz[s]; ++i)
             if (chk[s][i] < 0 || chk[s][i] >= m[s] || var[s][i] < 0 || var[s][i] >= n)
                 return fgnn_fail(FGNN_ERR_ARG, "edge index out of range");
-    FGNN_DEVICE_GUARD(device);
+    std::optional<fgnn_device_guard> dev_guard;
+    if (!host_only) {
+        dev_guard.emplace(device);
+        if (dev_guard->err != hipSuccess)
+            return fgnn_fail(FGNN_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(dev_guard->err));
+    }
     fgnn_graph* g = new fgnn_graph();
+    g->host_only = host_only;
     std::memset(&g->d, 0, sizeof(g->d));
     std::memset(g->row_alloc, 0, sizeof(g->row_alloc));
     g->device = device;
@@ -188,6 +200,26 @@ extern "C" int fgnn_graph_create(int n, int m_x, int m_z, int nnz_x, const int32
             fgnn_graph_destroy(g);
             return rc;
         }
+        // the same offsets as 32-bit values, one row of 8 per check: what an LDS instruction takes as its address operand when the
+        // message area starts at the base of the dynamic LDS (the base is the instruction's immediate offset) — no unpack in the loop
+        std::vector<uint32_t> wide((size_t)d.m * 8, 0);
+        for (size_t i = 0; i < wide.size(); ++i) wide[i] = pk[i];
+        g->h_cslot32 = wide;
+        if ((rc = upload(g, wide, &d.cslot32))) {
+            fgnn_graph_destroy(g);
+            return rc;
+        }
+    }
+    if (d.dc > 0 && d.dc <= 8 && n < 65536) {
+        // a check's qubits as one 16-byte row: the byte kernels and the fused flag test read it with one load
+        std::vector<uint16_t> qv((size_t)d.m * 8, 0);
+        for (int c = 0; c < d.m; ++c)
+            for (int j = 0; j < d.dc; ++j) qv[(size_t)c * 8 + j] = (uint16_t)cvn[cptr[c] + j];
+        g->h_cvn16 = qv;
+        if ((rc = upload(g, qv, &d.cvn16))) {
+            fgnn_graph_destroy(g);
+            return rc;
+        }
     }
     if ((rc = upload(g, vptr_x, &d.vptr_x)) || (rc = upload(g, vptr_z, &d.vptr_z)) || (rc = upload(g, vchk, &d.vchk)) ||
         (rc = upload(g, cptr, &d.cptr)) || (rc = upload(g, cslot, &d.cslot)) || (rc = upload(g, cvn, &d.cvn))) {
@@ -199,9 +231,19 @@ extern "C" int fgnn_graph_create(int n, int m_x, int m_z, int nnz_x, const int32
     return FGNN_OK;
 }
 
+extern "C" int fgnn_graph_create(int n, int m_x, int m_z, int nnz_x, const int32_t* chk_x, const int32_t* var_x,
+                                 int nnz_z, const int32_t* chk_z, const int32_t* var_z, int device, fgnn_graph** out)
+{
+    return graph_build(n, m_x, m_z, nnz_x, chk_x, var_x, nnz_z, chk_z, var_z, device, false, out);
+}
+
 extern "C" void fgnn_graph_destroy(fgnn_graph* g)
 {
     if (!g) return;
+    if (g->host_only) {
+        delete g;
+        return;
+    }
     fgnn_device_guard _dg(g->device);
     for (hipEvent_t e : g->prof_ev) (void)hipEventDestroy(e);
     for (void* p : g->basis_dev)
@@ -326,6 +368,21 @@ extern "C" int fgnn_graph_edges(const fgnn_graph* g, int side, int32_t* chk, int
     if (!g || side < 0 || side > 1 || !chk || !var) return fgnn_fail(FGNN_ERR_ARG, "bad arguments");
     std::copy(g->h_chk[side].begin(), g->h_chk[side].end(), chk);
     std::copy(g->h_var[side].begin(), g->h_var[side].end(), var);
+    return FGNN_OK;
+}
+
+extern "C" int fgnn_check_rows(int n, int m_x, int m_z, int nnz_x, const int32_t* chk_x, const int32_t* var_x, int nnz_z,
+                               const int32_t* chk_z, const int32_t* var_z, int32_t have[2], uint32_t* cslot32, uint16_t* cvn16)
+{
+    if (!have) return fgnn_fail(FGNN_ERR_ARG, "have is NULL");
+    fgnn_graph* g = nullptr;
+    const int rc = graph_build(n, m_x, m_z, nnz_x, chk_x, var_x, nnz_z, chk_z, var_z, 0, true, &g);
+    if (rc) return rc;
+    have[0] = !g->h_cslot32.empty();
+    have[1] = !g->h_cvn16.empty();
+    if (cslot32) std::copy(g->h_cslot32.begin(), g->h_cslot32.end(), cslot32);
+    if (cvn16) std::copy(g->h_cvn16.begin(), g->h_cvn16.end(), cvn16);
+    fgnn_graph_destroy(g);
     return FGNN_OK;
 }
 

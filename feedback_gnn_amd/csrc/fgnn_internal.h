@@ -19,6 +19,8 @@ struct GraphDev {
     const int* cslot;   // [E]   message slot of the k-th edge of a check (ascending qubit)
     const int* cvn;     // [E]   qubit of that edge
     const uint16_t* cslot16;  // [m][8] packed rows of slot BYTE offsets (4 * slot) for DC-regular graphs with DC <= 8 and 4E < 65536, else null
+    const uint32_t* cslot32;  // [m][8] the same BYTE offsets as 32-bit values (the LDS address operand of the one-codeword-per-workgroup kernels), null where cslot16 is
+    const uint16_t* cvn16;    // [m][8] packed rows of a check's qubits for DC-regular graphs with DC <= 8 and n < 65536, else null
     // CSR row sets (fgnn_graph_set_rows)
     int rows[6];
     const int* rptr[6];
@@ -49,6 +51,10 @@ struct fgnn_graph {
     std::vector<void*> allocs;
     // host copies of the canonical edge lists (fgnn_graph_edges)
     std::vector<int32_t> h_chk[2], h_var[2];
+    // host copies of the uploaded check rows (fgnn_check_rows builds a graph with host_only set to read them back without a device)
+    bool host_only = false;
+    std::vector<uint32_t> h_cslot32;
+    std::vector<uint16_t> h_cvn16;
     void* row_alloc[6][4];
     void* basis_dev[2] = {nullptr, nullptr};  // pivot rows of hx / hz (fgnn_graph_set_basis, OSD)
     int basis_rank[2] = {0, 0};

@@ -133,6 +133,13 @@ int fgnn_graph_force_generic(fgnn_graph* g, int on);
 int fgnn_graph_info(const fgnn_graph* g, int32_t info[16]);
 /* canonical (qubit, check)-sorted edge lists, host output: chk[E_s], var[E_s] for side 0 (hx) / 1 (hz) */
 int fgnn_graph_edges(const fgnn_graph* g, int side, int32_t* chk, int32_t* var);
+/* The per-check row tables fgnn_graph_create builds and uploads for a check-regular graph (check degree <= 8), formed on the HOST from the
+ * same edge lists by the same code — no device is touched, so a test can hold them to the parity-check matrices without a GPU:
+ * cslot32[m][8] = byte offsets (4 * slot) of a check's message slots (also needs degree-regular qubits and 4 E < 65536), cvn16[m][8] = its
+ * qubits (needs n < 65536), both in ascending qubit order and zero padded; hx checks first, then hz.  have[0], have[1] = whether a graph of
+ * these edges carries each table (a table it does not carry is not written; either output pointer may be NULL). */
+int fgnn_check_rows(int n, int m_x, int m_z, int nnz_x, const int32_t* chk_x, const int32_t* var_x, int nnz_z, const int32_t* chk_z,
+                    const int32_t* var_z, int32_t have[2], uint32_t* cslot32, uint16_t* cvn16);
 
 /* Per-launch timing of the BP4 and feedback-GNN kernels (no reference equivalent; sim_ber only has wall-clock per point,
  * misc.py:639,696): HIP events are recorded on the launch stream right before and after every BP4 / feedback-GNN launch,
