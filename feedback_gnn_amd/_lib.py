@@ -32,9 +32,9 @@ def build(force=False, verbose=False):
 # Which sources make which kernel: profiles/traffic.json (rocprofv3 PMC counts taken offline) records the fingerprint of the
 # sources its counts were measured on, and bench.py quotes a count only while the tree still matches it.
 KERNEL_SOURCES = {
-    "bp4": ("fgnn_bp4.hip", "fgnn_math.h", "fgnn_math_ranged.h", "fgnn_internal.h", "fgnn_rng.h", "fgnn_cn.h", "Makefile"),
+    "bp4": ("fgnn_bp4.hip", "fgnn_math.h", "fgnn_math_ranged.h", "fgnn_internal.h", "fgnn_rng.h", "fgnn_cn.h", "fgnn_vn.h", "Makefile"),
     "gnn": ("fgnn_gnn.hip", "fgnn_math.h", "fgnn_internal.h", "fgnn_pk.h", "fgnn_mlp.h", "Makefile"),
-    "gnnbp4": ("fgnn_gnnbp4.hip", "fgnn_math.h", "fgnn_internal.h", "fgnn_pk.h", "fgnn_mlp.h", "Makefile"),
+    "gnnbp4": ("fgnn_gnnbp4.hip", "fgnn_math.h", "fgnn_internal.h", "fgnn_pk.h", "fgnn_mlp.h", "fgnn_vn.h", "Makefile"),
 }
 
 

@@ -21,6 +21,7 @@
 #include "fgnn_internal.h"
 #include "fgnn_math.h"
 #include "fgnn_mlp.h"
+#include "fgnn_vn.h"
 
 namespace {
 
@@ -107,22 +108,21 @@ __global__ void __launch_bounds__(256) bp4_backward_kernel(GraphDev g, BwArgs a)
             for (int e = tid; e < g.E_z; e += nt) mu[g.E_x + e] = tz[e];
         }
         __syncthreads();
-        // P1: totals (and the binary LLRs the soft syndromes are taken from)
+        // P1: totals (and the binary LLRs the soft syndromes are taken from), the rules of fgnn_vn.h
         for (int v = tid; v < n; v += nt) {
-            float Sz = 0.0f, Sx = 0.0f;
+            // (the sums stay written out, z side first as vn_sums has them: with its four bounds loaded ahead of the loops this kernel
+            // takes 61 VGPRs instead of 57)
+            float Sz = 0.0f, Sx = 0.0f, X, Y, Z;
             for (int e = g.vptr_z[v]; e < g.vptr_z[v + 1]; ++e) Sz = Sz + mu[e];
             for (int e = g.vptr_x[v]; e < g.vptr_x[v + 1]; ++e) Sx = Sx + mu[e];
-            const float X = Sz + L[v], Y = (Sz + Sx) + L[n + v], Z = Sx + L[2 * n + v];
+            vn_totals(Sz, Sx, L[v], L[n + v], L[2 * n + v], X, Y, Z);
             tot[v] = X;
             tot[n + v] = Y;
             tot[2 * n + v] = Z;
             dtot[v] = 0.0f;
             dtot[n + v] = 0.0f;
             dtot[2 * n + v] = 0.0f;
-            if (has_g) {
-                llz[v] = fg_softplus(-X) - fg_lse2(-Z, -Y);
-                llx[v] = fg_softplus(-Z) - fg_lse2(-X, -Y);
-            }
+            if (has_g) vn_binary_llrs<VnMath>(X, Y, Z, llx[v], llz[v]);
         }
         if (has_g) {
             __syncthreads();
@@ -170,12 +170,12 @@ __global__ void __launch_bounds__(256) bp4_backward_kernel(GraphDev g, BwArgs a)
         }
         if (has_it) {
             __syncthreads();  // llx/llz are dead, nu may be written
-            // P4: v->c messages of iteration k (_vn_update)
+            // P4: v->c messages of iteration k (_vn_update: vn_edge of fgnn_vn.h)
             for (int v = tid; v < n; v += nt) {
                 const float X = tot[v], Y = tot[n + v], Z = tot[2 * n + v];
-                const float numx = fg_softplus(-X), numz = fg_softplus(-Z);
-                for (int e = g.vptr_x[v]; e < g.vptr_x[v + 1]; ++e) nu[e] = numx - fg_lse2(-(Z - mu[e]), -(Y - mu[e]));
-                for (int e = g.vptr_z[v]; e < g.vptr_z[v + 1]; ++e) nu[e] = numz - fg_lse2(-(X - mu[e]), -(Y - mu[e]));
+                const float numx = VnMath::softplus(-X), numz = VnMath::softplus(-Z);
+                for (int e = g.vptr_x[v]; e < g.vptr_x[v + 1]; ++e) nu[e] = vn_edge<VnMath>(numx, Z, Y, mu[e]);
+                for (int e = g.vptr_z[v]; e < g.vptr_z[v + 1]; ++e) nu[e] = vn_edge<VnMath>(numz, X, Y, mu[e]);
             }
             __syncthreads();
             // P5: check nodes: d loss / d mu^{k+1}  ->  d loss / d nu   (in place in dmu)

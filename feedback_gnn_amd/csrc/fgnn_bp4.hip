@@ -31,6 +31,7 @@
 #include "fgnn_math.h"
 #include "fgnn_math_ranged.h"
 #include "fgnn_cn.h"
+#include "fgnn_vn.h"
 
 #ifndef FGNN_BP4_WAVES
 #define FGNN_BP4_WAVES 7  // waves per SIMD the register allocator must leave room for (LDS admits 5-7 workgroups of 4 waves per CU)
@@ -517,17 +518,12 @@ bp4_kernel(GraphDev g, BpArgs a)
         }
         if (active)
             for (int v = lane; v < n; v += tpc) {
-                const int x0 = g.vptr_x[v], x1 = g.vptr_x[v + 1], z0 = g.vptr_z[v], z1 = g.vptr_z[v + 1];
-                float Sz = 0.0f, Sx = 0.0f;
-                for (int e = z0; e < z1; ++e) Sz = Sz + msg[e];
-                for (int e = x0; e < x1; ++e) Sx = Sx + msg[e];
                 const float lx = a.llr_ch ? Lch[v] : a.llr_const, ly = a.llr_ch ? Lch[n + v] : a.llr_const,
                             lz = a.llr_ch ? Lch[2 * n + v] : a.llr_const;
-                const float Y = (Sz + Sx) + ly;
-                const float X = Sz + lx;
-                const float Z = Sx + lz;
-                tlz[v] = MX::softplus(-X) - MX::lse2(-Z, -Y);
-                tlx[v] = MX::softplus(-Z) - MX::lse2(-X, -Y);
+                float Sz, Sx, X, Y, Z;
+                vn_sums(msg, g.vptr_z[v], g.vptr_z[v + 1], g.vptr_x[v], g.vptr_x[v + 1], Sz, Sx);
+                vn_totals(Sz, Sx, lx, ly, lz, X, Y, Z);
+                vn_binary_llrs<MX>(X, Y, Z, tlx[v], tlz[v]);
             }
         __syncthreads();
         if (active) {
@@ -586,6 +582,7 @@ bp4_kernel(GraphDev g, BpArgs a)
     for (int it = it_begin; it < a.num_iter; ++it) {
         bool changed = false, cn_slow = false;
         // ---- variable nodes: _vn_update (:227-275) ----
+        // (fgnn_vn.h states these rules; the regular branch keeps its own copy, as its seven-waves allocation has no slack for a new schedule)
         auto vn_body = [&](const int v, const float lx, const float ly, const float lz) __attribute__((always_inline)) {
                 if constexpr (REGULAR) {
                     float* px = msg + v * DVX;
@@ -668,12 +665,9 @@ bp4_kernel(GraphDev g, BpArgs a)
                     }
                 } else {
                     const int x0 = g.vptr_x[v], x1 = g.vptr_x[v + 1], z0 = g.vptr_z[v], z1 = g.vptr_z[v + 1];
-                    float Sz = 0.0f, Sx = 0.0f;
-                    for (int e = z0; e < z1; ++e) Sz = Sz + msg[e];
-                    for (int e = x0; e < x1; ++e) Sx = Sx + msg[e];
-                    const float Y = (Sz + Sx) + ly;
-                    const float X = Sz + lx;
-                    const float Z = Sx + lz;
+                    float Sz, Sx, X, Y, Z;
+                    vn_sums(msg, z0, z1, x0, x1, Sz, Sx);
+                    vn_totals(Sz, Sx, lx, ly, lz, X, Y, Z);
                     if (opt_shortcut) {  // same exact shortcut (and sign words) as the regular path, runtime degrees
                         bool sat = FG_ABS(X) > FG_SOFTPLUS_THRESH && FG_ABS(Z) > FG_SOFTPLUS_THRESH;
                         if (shl) sat = sat && FG_ABS((-Z) - (-Y)) >= 20.0f && FG_ABS((-X) - (-Y)) >= 20.0f;
@@ -711,28 +705,12 @@ bp4_kernel(GraphDev g, BpArgs a)
                     const float numz = MX::softplus(-Z);
                     if (shl) {
                         const float cx = MX::lse2_corr(-Z, -Y), cz = MX::lse2_corr(-X, -Y);
-                        for (int e = x0; e < x1; ++e) {
-                            float m = msg[e];
-                            float Ze = Z - m, Ye = Y - m;
-                            msg[e] = numx - (cx + FG_MAX(-Ze, -Ye));
-                        }
-                        for (int e = z0; e < z1; ++e) {
-                            float m = msg[e];
-                            float Xe = X - m, Ye = Y - m;
-                            msg[e] = numz - (cz + FG_MAX(-Xe, -Ye));
-                        }
+                        for (int e = x0; e < x1; ++e) msg[e] = vn_edge_shared(numx, cx, Z, Y, msg[e]);
+                        for (int e = z0; e < z1; ++e) msg[e] = vn_edge_shared(numz, cz, X, Y, msg[e]);
                         return;
                     }
-                    for (int e = x0; e < x1; ++e) {
-                        float m = msg[e];
-                        float Ze = Z - m, Ye = Y - m;
-                        msg[e] = numx - MX::lse2(-Ze, -Ye);
-                    }
-                    for (int e = z0; e < z1; ++e) {
-                        float m = msg[e];
-                        float Xe = X - m, Ye = Y - m;
-                        msg[e] = numz - MX::lse2(-Xe, -Ye);
-                    }
+                    for (int e = x0; e < x1; ++e) msg[e] = vn_edge<MX>(numx, Z, Y, msg[e]);
+                    for (int e = z0; e < z1; ++e) msg[e] = vn_edge<MX>(numz, X, Y, msg[e]);
                 }
             };
         if (active && !(first_peeled && it == 0)) {  // (peeled: iteration 0's qubit phase ran above)

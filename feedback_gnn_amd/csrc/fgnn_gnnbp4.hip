@@ -20,6 +20,7 @@
 #include "fgnn_math.h"
 #include "fgnn_mlp.h"
 #include "fgnn_pk.h"
+#include "fgnn_vn.h"
 
 namespace {
 
@@ -289,8 +290,7 @@ __device__ __forceinline__ void store_llrs(const Frame& f, int n, int v, float L
     f.llr[v] = L0;
     f.llr[n + v] = L1;
     f.llr[2 * n + v] = L2;
-    f.lz[v] = fg_softplus(-L0) - fg_lse2(-L2, -L1);
-    f.lx[v] = fg_softplus(-L2) - fg_lse2(-L0, -L1);
+    vn_binary_llrs<VnMath>(L0, L1, L2, f.lx[v], f.lz[v]);
 }
 // Soft syndromes of iteration `it` (:306-314) into hlog and the *_logit_all outputs: hx rows use llr_z, hz rows use llr_x; logical
 // rows appended
@@ -313,16 +313,12 @@ __device__ __forceinline__ void soft_syndromes(const GraphDev& g, const Args& a,
         for (int r = tid; r < g.rows[4]; r += T)
             zl[mx + r] = logit_row_gnn(f.lz, g.rcol[4] + g.rptr[4][r], g.rptr[4][r + 1] - g.rptr[4][r]);
 }
-// make_hard_decision (:359-367): the smallest of X, Z, Y below 0, compared in that order, else the identity
+// make_hard_decision (:359-367): vn_decide of fgnn_vn.h
 __device__ __forceinline__ void hard_decision(const Args& a, const Frame& f, int n, int b, int tid, int T)
 {
     for (int v = tid; v < n; v += T) {
         const float X = f.llr[v], Y = f.llr[n + v], Z = f.llr[2 * n + v];
-        int d = 0;
-        float best = 0.0f;
-        if (X < best) { best = X; d = 1; }
-        if (Z < best) { best = Z; d = 2; }
-        if (Y < best) { best = Y; d = 3; }
+        const int d = vn_decide(X, Y, Z);
         a.x_hat[(size_t)b * n + v] = (uint8_t)(d & 1);
         a.z_hat[(size_t)b * n + v] = (uint8_t)(d >> 1);
     }

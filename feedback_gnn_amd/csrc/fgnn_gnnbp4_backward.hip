@@ -32,6 +32,7 @@
 #include "fgnn_internal.h"
 #include "fgnn_math.h"
 #include "fgnn_mlp.h"
+#include "fgnn_vn.h"
 
 // The node loops are written once for both instantiations: `#pragma unroll` unrolls them where the width is a compile-time
 // constant and is a request the optimizer declines, with a warning per loop, where it is a runtime value.
@@ -425,8 +426,7 @@ __global__ void __launch_bounds__(256) gnn_bp4_tape_kernel(GraphDev g, TrainDev 
                 for (int i = 0; i < D; ++i) tk.hv[(size_t)v * D + i] = nh[i];
                 float Lv[3];
                 llr_of<FX>(w, nh, Lv);
-                lz[v] = fg_softplus(-Lv[0]) - fg_lse2(-Lv[2], -Lv[1]);
-                lx[v] = fg_softplus(-Lv[2]) - fg_lse2(-Lv[0], -Lv[1]);
+                vn_binary_llrs<VnMath>(Lv[0], Lv[1], Lv[2], lx[v], lz[v]);
             }
             __syncthreads();
             // ---- soft syndromes: hx rows on llr_z, hz rows on llr_x, logical rows appended ----
@@ -535,8 +535,7 @@ __global__ void __launch_bounds__(256) gnn_bp4_backward_kernel(GraphDev g, Train
 #pragma unroll
                 for (int i = 0; i < D; ++i) hv[i] = tk.hv[(size_t)v * D + i];
                 llr_of<FX>(w, hv, Lv);
-                lz[v] = fg_softplus(-Lv[0]) - fg_lse2(-Lv[2], -Lv[1]);
-                lx[v] = fg_softplus(-Lv[2]) - fg_lse2(-Lv[0], -Lv[1]);
+                vn_binary_llrs<VnMath>(Lv[0], Lv[1], Lv[2], lx[v], lz[v]);
                 dlx[v] = 0.0f;
                 dlz[v] = 0.0f;
             }

@@ -12,6 +12,7 @@
 // Bit-identical to oracle/fgnn_oracle.c: og_osd0 (stable sort: ties keep qubit order).
 #include "fgnn_internal.h"
 #include "fgnn_math.h"
+#include "fgnn_vn.h"
 
 namespace {
 
@@ -75,7 +76,7 @@ __device__ __forceinline__ void osd_eliminate(const GraphDev& g, const OsdArgs& 
             else {
                 const float* mg = a.marg + (size_t)b * 3 * n;
                 const float X = mg[v], Y = mg[n + v], Z = mg[2 * n + v];
-                r = a.side == 0 ? fg_softplus(-X) - fg_lse2(-Z, -Y) : fg_softplus(-Z) - fg_lse2(-X, -Y);  // bp_osd.py:125-131
+                r = a.side == 0 ? vn_llr_z<VnMath>(X, Y, Z) : vn_llr_x<VnMath>(X, Y, Z);  // bp_osd.py:125-131
             }
             r = r + 0.0f;  // -0 -> +0: the oracle compares with '<', for which the two zeros tie
             unsigned u = fg_f2u(r);
@@ -414,7 +415,7 @@ __global__ void __launch_bounds__(OSDW_T) osd_ws_kernel(GraphDev g, OsdWsArgs a)
                 else {
                     const float* mg = a.marg + (size_t)b * 3 * n;
                     const float X = mg[v], Y = mg[n + v], Z = mg[2 * n + v];
-                    r = a.side == 0 ? fg_softplus(-X) - fg_lse2(-Z, -Y) : fg_softplus(-Z) - fg_lse2(-X, -Y);  // bp_osd.py:125-131
+                    r = a.side == 0 ? vn_llr_z<VnMath>(X, Y, Z) : vn_llr_x<VnMath>(X, Y, Z);  // bp_osd.py:125-131
                 }
                 r = r + 0.0f;  // -0 -> +0
                 k = ((unsigned long long)osd_sortable(r) << 32) | (unsigned)v;

@@ -1,8 +1,8 @@
 // fgnn_relay4.hip — Relay-BP4: a chain of min-sum BP4 runs ("legs") with per-qubit memory strengths on both Tanner graphs, LDS-resident.
 //
 // Relay-BP's memory term (Mueller et al., "Improved belief propagation is sufficient for real-time decoding of quantum memories", 2025)
-// applied to each of a qubit's three LLRs, in the form include/fgnn.h states at fgnn_relay4_decode.  The qubit update is bp4_kernel's
-// literal form (fgnn_bp4.hip: one log-sum-exp per edge, fgnn_math.h) with the memory-weighted LLRs Lam in place of the channel LLRs,
+// applied to each of a qubit's three LLRs, in the form include/fgnn.h states at fgnn_relay4_decode.  The qubit update is the literal
+// form of fgnn_vn.h (one log-sum-exp per edge, fgnn_math.h) with the memory-weighted LLRs Lam in place of the channel LLRs,
 // the check update is the shared min-sum rule of fgnn_cn.h, the leg / stop / weight control is relay_kernel's (fgnn_relay.hip).  No
 // saturation shortcuts, no register-resident channel LLRs, no hardware transcendentals: the channel LLRs are re-read from global
 // memory (L2) by the thread that owns the qubit, every float operation is the one bp4_kernel and cn_update execute, in their order.
@@ -29,6 +29,7 @@
 #include "fgnn_internal.h"
 #include "fgnn_math.h"
 #include "fgnn_cn.h"
+#include "fgnn_vn.h"
 
 #ifndef FGNN_RELAY4_WAVES
 #define FGNN_RELAY4_WAVES 4  // waves per SIMD the register allocation aims at: what the LDS of the benchmark codes admits
@@ -112,11 +113,15 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_
                 const float gv = gam[v];
                 const float om = 1.0f - gv;
                 float MX = M[v], MY = M[n + v], MZ = M[2 * n + v];
+                // the qubit's c->v messages (zeros before the first check update of a leg) and their sums: only this fetch and the
+                // store below differ between the regular rows, which keep the messages in registers, and the runtime degrees
+                const int x0 = REGULAR ? v * DV : g.vptr_x[v], z0 = REGULAR ? g.E_x + v * DV : g.vptr_z[v];
+                const int dx = REGULAR ? DV : g.vptr_x[v + 1] - x0, dz = REGULAR ? DV : g.vptr_z[v + 1] - z0;
+                float* px = msg + x0;
+                float* pz = msg + z0;
+                float mx[REGULAR ? DV : 1], mz[REGULAR ? DV : 1];
+                float Sz = 0.0f, Sx = 0.0f;
                 if constexpr (REGULAR) {
-                    float* px = msg + v * DV;
-                    float* pz = msg + g.E_x + v * DV;
-                    float mx[DV], mz[DV];
-                    float Sz = 0.0f, Sx = 0.0f;
                     if (k > 0) {
 #pragma unroll
                         for (int j = 0; j < DV; ++j) { mz[j] = pz[j]; Sz = Sz + mz[j]; }
@@ -126,75 +131,29 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_
 #pragma unroll
                         for (int j = 0; j < DV; ++j) mz[j] = mx[j] = 0.0f;
                     }
-                    if (k > 0) {
-                        const float LX0 = om * lx + gv * MX, LY0 = om * ly + gv * MY, LZ0 = om * lz + gv * MZ;
-                        MY = (Sz + Sx) + LY0;
-                        MX = Sz + LX0;
-                        MZ = Sx + LZ0;
-                        M[v] = MX;
-                        M[n + v] = MY;
-                        M[2 * n + v] = MZ;
-                        int d = 0;
-                        float best = 0.0f;
-                        if (MX < best) { best = MX; d = 1; }
-                        if (MZ < best) { best = MZ; d = 2; }
-                        if (MY < best) { best = MY; d = 3; }
-                        dec[v] = (uint8_t)d;
-                        if (k == T) continue;
-                    }
-                    const float LX = om * lx + gv * MX, LY = om * ly + gv * MY, LZ = om * lz + gv * MZ;
-                    const float Y = (Sz + Sx) + LY;
-                    const float X = Sz + LX;
-                    const float Z = Sx + LZ;
-                    const float numx = fg_softplus(-X);
-                    const float numz = fg_softplus(-Z);
+                } else if (k > 0) {
+                    vn_sums(msg, z0, z0 + dz, x0, x0 + dx, Sz, Sx);
+                }
+                if (k > 0) {  // posteriors of the memory-weighted LLRs, kept for the next memory term, and their decision (fgnn_vn.h)
+                    vn_totals(Sz, Sx, om * lx + gv * MX, om * ly + gv * MY, om * lz + gv * MZ, MX, MY, MZ);
+                    M[v] = MX;
+                    M[n + v] = MY;
+                    M[2 * n + v] = MZ;
+                    dec[v] = (uint8_t)vn_decide(MX, MY, MZ);
+                    if (k == T) continue;
+                }
+                float X, Y, Z;
+                vn_totals(Sz, Sx, om * lx + gv * MX, om * ly + gv * MY, om * lz + gv * MZ, X, Y, Z);
+                const float numx = VnMath::softplus(-X);
+                const float numz = VnMath::softplus(-Z);
+                if constexpr (REGULAR) {
 #pragma unroll
-                    for (int j = 0; j < DV; ++j) {
-                        const float Ze = Z - mx[j], Ye = Y - mx[j];
-                        px[j] = numx - fg_lse2(-Ze, -Ye);
-                    }
+                    for (int j = 0; j < DV; ++j) px[j] = vn_edge<VnMath>(numx, Z, Y, mx[j]);
 #pragma unroll
-                    for (int j = 0; j < DV; ++j) {
-                        const float Xe = X - mz[j], Ye = Y - mz[j];
-                        pz[j] = numz - fg_lse2(-Xe, -Ye);
-                    }
+                    for (int j = 0; j < DV; ++j) pz[j] = vn_edge<VnMath>(numz, X, Y, mz[j]);
                 } else {
-                    const int x0 = g.vptr_x[v], x1 = g.vptr_x[v + 1], z0 = g.vptr_z[v], z1 = g.vptr_z[v + 1];
-                    float Sz = 0.0f, Sx = 0.0f;
-                    if (k > 0) {
-                        for (int e = z0; e < z1; ++e) Sz = Sz + msg[e];
-                        for (int e = x0; e < x1; ++e) Sx = Sx + msg[e];
-                        const float LX0 = om * lx + gv * MX, LY0 = om * ly + gv * MY, LZ0 = om * lz + gv * MZ;
-                        MY = (Sz + Sx) + LY0;
-                        MX = Sz + LX0;
-                        MZ = Sx + LZ0;
-                        M[v] = MX;
-                        M[n + v] = MY;
-                        M[2 * n + v] = MZ;
-                        int d = 0;
-                        float best = 0.0f;
-                        if (MX < best) { best = MX; d = 1; }
-                        if (MZ < best) { best = MZ; d = 2; }
-                        if (MY < best) { best = MY; d = 3; }
-                        dec[v] = (uint8_t)d;
-                        if (k == T) continue;
-                    }
-                    const float LX = om * lx + gv * MX, LY = om * ly + gv * MY, LZ = om * lz + gv * MZ;
-                    const float Y = (Sz + Sx) + LY;
-                    const float X = Sz + LX;
-                    const float Z = Sx + LZ;
-                    const float numx = fg_softplus(-X);
-                    const float numz = fg_softplus(-Z);
-                    for (int e = x0; e < x1; ++e) {
-                        const float mm = k > 0 ? msg[e] : 0.0f;
-                        const float Ze = Z - mm, Ye = Y - mm;
-                        msg[e] = numx - fg_lse2(-Ze, -Ye);
-                    }
-                    for (int e = z0; e < z1; ++e) {
-                        const float mm = k > 0 ? msg[e] : 0.0f;
-                        const float Xe = X - mm, Ye = Y - mm;
-                        msg[e] = numz - fg_lse2(-Xe, -Ye);
-                    }
+                    for (int j = 0; j < dx; ++j) px[j] = vn_edge<VnMath>(numx, Z, Y, k > 0 ? px[j] : 0.0f);
+                    for (int j = 0; j < dz; ++j) pz[j] = vn_edge<VnMath>(numz, X, Y, k > 0 ? pz[j] : 0.0f);
                 }
             }
         }
