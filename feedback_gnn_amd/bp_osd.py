@@ -200,7 +200,8 @@ class BP4_OSD_Model:
         sx, sz = g.syndrome(ex, ez)
         pf = np.float32(p)
         L = float(np.log(np.float32(3.0) * (np.float32(1.0) - pf) / pf, dtype=np.float32))
-        out = g.bp4_decode(sx, sz, d.num_iter, d.cn_type, d.normalization_factor, llr_const=L, want_logits=False)
+        decode = g.bp4_decode_layered if getattr(d, "schedule", "flooding") == "layered" else g.bp4_decode
+        out = decode(sx, sz, d.num_iter, d.cn_type, d.normalization_factor, llr_const=L, want_logits=False)
         x_hat, z_hat = out["x_hat"], out["z_hat"]
         _, _, flags = g.residual(ex, ez, x_hat, z_hat, want_arrays=False)  # bit 0 = syndrome missed = `err` (:117-120)
         index, nact = g.compact(flags, 1)

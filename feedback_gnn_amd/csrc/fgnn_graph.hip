@@ -248,6 +248,8 @@ extern "C" void fgnn_graph_destroy(fgnn_graph* g)
     for (hipEvent_t e : g->prof_ev) (void)hipEventDestroy(e);
     for (void* p : g->basis_dev)
         if (p) (void)hipFree(p);
+    for (void* p : g->layer_alloc)
+        if (p) (void)hipFree(p);
     for (void* p : g->allocs) (void)hipFree(p);
     for (auto& r : g->row_alloc)
         for (void* p : r)
@@ -384,6 +386,213 @@ extern "C" int fgnn_check_rows(int n, int m_x, int m_z, int nnz_x, const int32_t
     if (cvn16) std::copy(g->h_cvn16.begin(), g->h_cvn16.end(), cvn16);
     fgnn_graph_destroy(g);
     return FGNN_OK;
+}
+
+// ---- layers of the serial schedule (fgnn_bp4_decode_layered) ------------------------------------------------------------------
+namespace {
+
+// the qubits of every check, hx checks 0..m_x-1 then hz checks m_x..m_x+m_z-1, in the order of the edge lists
+int check_qubits(int n, int m_x, int m_z, int nnz_x, const int32_t* chk_x, const int32_t* var_x, int nnz_z, const int32_t* chk_z,
+                 const int32_t* var_z, std::vector<int>& ptr, std::vector<int>& vn)
+{
+    if (n <= 0 || m_x <= 0 || m_z <= 0 || nnz_x < 0 || nnz_z < 0) return fgnn_fail(FGNN_ERR_ARG, "n, m_x and m_z must be positive");
+    if ((nnz_x && (!chk_x || !var_x)) || (nnz_z && (!chk_z || !var_z))) return fgnn_fail(FGNN_ERR_ARG, "edge list is NULL");
+    const int32_t* chk[2] = {chk_x, chk_z};
+    const int32_t* var[2] = {var_x, var_z};
+    const int nnz[2] = {nnz_x, nnz_z}, mm[2] = {m_x, m_z}, base[2] = {0, m_x};
+    const int m = m_x + m_z;
+    ptr.assign(m + 1, 0);
+    for (int s = 0; s < 2; ++s)
+        for (int i = 0; i < nnz[s]; ++i) {
+            if (chk[s][i] < 0 || chk[s][i] >= mm[s] || var[s][i] < 0 || var[s][i] >= n)
+                return fgnn_fail(FGNN_ERR_ARG, "edge index out of range");
+            ptr[base[s] + chk[s][i] + 1]++;
+        }
+    for (int c = 0; c < m; ++c) ptr[c + 1] += ptr[c];
+    vn.resize(ptr[m]);
+    std::vector<int> fill(ptr.begin(), ptr.end() - 1);
+    for (int s = 0; s < 2; ++s)
+        for (int i = 0; i < nnz[s]; ++i) vn[fill[base[s] + chk[s][i]]++] = var[s][i];
+    return FGNN_OK;
+}
+
+std::string check_name(int c, int m_x)
+{
+    return c < m_x ? "hx check " + std::to_string(c) : "hz check " + std::to_string(c - m_x) + " (number " + std::to_string(c) + ")";
+}
+
+void greedy_layers(int n, int m, const std::vector<int>& ptr, const std::vector<int>& vn, int32_t* layer_of, int32_t* num_layers)
+{
+    std::vector<std::vector<int>> at(n);  // the layers that hold a check of qubit v
+    std::vector<int> seen;                // seen[l] == c + 1: layer l holds a check that shares a qubit with check c
+    int L = 0;
+    for (int c = 0; c < m; ++c) {
+        for (int p = ptr[c]; p < ptr[c + 1]; ++p)
+            for (int l : at[vn[p]]) seen[l] = c + 1;
+        int l = 0;
+        while (l < L && seen[l] == c + 1) ++l;
+        if (l == L) {
+            ++L;
+            seen.push_back(0);
+        }
+        layer_of[c] = l;
+        for (int p = ptr[c]; p < ptr[c + 1]; ++p) at[vn[p]].push_back(l);
+    }
+    *num_layers = L;
+}
+
+int validate_layers(int n, int m_x, int m, const std::vector<int>& ptr, const std::vector<int>& vn, int num_layers, const int32_t* layer_of)
+{
+    if (!layer_of) return fgnn_fail(FGNN_ERR_ARG, "layer_of is NULL");
+    if (num_layers < 1) return fgnn_fail(FGNN_ERR_ARG, "num_layers = " + std::to_string(num_layers) + " must be >= 1");
+    std::vector<int> count(num_layers, 0);
+    for (int c = 0; c < m; ++c) {
+        if (layer_of[c] < 0 || layer_of[c] >= num_layers)
+            return fgnn_fail(FGNN_ERR_ARG, check_name(c, m_x) + " has layer " + std::to_string(layer_of[c]) + ", outside [0, " +
+                                               std::to_string(num_layers) + ")");
+        count[layer_of[c]]++;
+    }
+    for (int l = 0; l < num_layers; ++l)
+        if (!count[l]) return fgnn_fail(FGNN_ERR_ARG, "layer " + std::to_string(l) + " is empty");
+    // per qubit: the checks at it; stamp[l] = the last qubit with a check in layer l, owner[l] = that check: two in one layer collide
+    std::vector<int> owner(num_layers, -1), stamp(num_layers, -1);
+    std::vector<std::vector<int>> at(n);
+    for (int c = 0; c < m; ++c)
+        for (int p = ptr[c]; p < ptr[c + 1]; ++p) at[vn[p]].push_back(c);
+    for (int v = 0; v < n; ++v)
+        for (int c : at[v]) {
+            const int l = layer_of[c];
+            if (stamp[l] == v && owner[l] != c)
+                return fgnn_fail(FGNN_ERR_ARG, check_name(owner[l], m_x) + " and " + check_name(c, m_x) + " of layer " + std::to_string(l) +
+                                                   " share qubit " + std::to_string(v));
+            stamp[l] = v;
+            owner[l] = c;
+        }
+    return FGNN_OK;
+}
+
+void free_layers(const fgnn_graph* g)
+{
+    for (void*& p : g->layer_alloc)
+        if (p) {
+            (void)hipFree(p);  // waits for the launches that read it
+            p = nullptr;
+        }
+    g->num_layers = 0;
+    g->h_layer_of.clear();
+}
+
+int install_layers(const fgnn_graph* g, int num_layers, const int32_t* layer_of)
+{
+    const GraphDev& d = g->d;
+    std::vector<int> ptr, vn;
+    int rc = check_qubits(d.n, d.m_x, d.m_z, d.E_x, g->h_chk[0].data(), g->h_var[0].data(), d.E_z, g->h_chk[1].data(),
+                          g->h_var[1].data(), ptr, vn);
+    if (rc) return rc;
+    std::vector<int32_t> lay(d.m);
+    if (!layer_of) {
+        greedy_layers(d.n, d.m, ptr, vn, lay.data(), &num_layers);
+    } else {
+        if ((rc = validate_layers(d.n, d.m_x, d.m, ptr, vn, num_layers, layer_of))) return rc;
+        std::copy(layer_of, layer_of + d.m, lay.begin());
+    }
+    // the device tables, from the graph's own check-major view: a check's edges in ascending qubit order, slot = VN-major message slot
+    std::vector<int> cptr(d.m + 1, 0), cslot(d.E), cvn(d.E);
+    {
+        std::vector<int> vptr[2];
+        for (int s = 0; s < 2; ++s) {
+            vptr[s].assign(d.n + 1, 0);
+            for (int v : g->h_var[s]) vptr[s][v + 1]++;
+            for (int v = 0; v < d.n; ++v) vptr[s][v + 1] += vptr[s][v];
+        }
+        for (int s = 0; s < 2; ++s)
+            for (int c : g->h_chk[s]) cptr[(s ? d.m_x : 0) + c + 1]++;
+        for (int c = 0; c < d.m; ++c) cptr[c + 1] += cptr[c];
+        std::vector<int> fill(cptr.begin(), cptr.end() - 1);
+        for (int s = 0; s < 2; ++s)
+            for (int e = 0; e < (s ? d.E_z : d.E_x); ++e) {  // the canonical lists are sorted by (qubit, check): slot e of the side
+                const int pos = fill[(s ? d.m_x : 0) + g->h_chk[s][e]]++;
+                cslot[pos] = e + (s ? d.E_x : 0);
+                cvn[pos] = g->h_var[s][e];
+            }
+    }
+    std::vector<int> lcptr(num_layers + 1, 0), lchk(d.m), leptr(num_layers + 1, 0), ledge((size_t)2 * d.E);
+    for (int c = 0; c < d.m; ++c) lcptr[lay[c] + 1]++;
+    for (int l = 0; l < num_layers; ++l) lcptr[l + 1] += lcptr[l];
+    {
+        std::vector<int> fill(lcptr.begin(), lcptr.end() - 1);
+        for (int c = 0; c < d.m; ++c) lchk[fill[lay[c]]++] = c;
+    }
+    int ne = 0;
+    for (int l = 0; l < num_layers; ++l) {
+        for (int i = lcptr[l]; i < lcptr[l + 1]; ++i)
+            for (int p = cptr[lchk[i]]; p < cptr[lchk[i] + 1]; ++p, ++ne) {
+                ledge[2 * (size_t)ne] = cslot[p];
+                ledge[2 * (size_t)ne + 1] = cvn[p];
+            }
+        leptr[l + 1] = ne;
+    }
+    fgnn_device_guard dg(g->device);
+    if (dg.err != hipSuccess) return fgnn_fail(FGNN_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(dg.err));
+    free_layers(g);
+    const std::vector<int>* tabs[4] = {&lcptr, &lchk, &leptr, &ledge};
+    for (int i = 0; i < 4; ++i) {
+        const size_t bytes = std::max<size_t>(tabs[i]->size(), 2) * sizeof(int);
+        hipError_t e = hipMalloc(&g->layer_alloc[i], bytes);
+        if (e == hipSuccess && !tabs[i]->empty())
+            e = hipMemcpy(g->layer_alloc[i], tabs[i]->data(), tabs[i]->size() * sizeof(int), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            free_layers(g);
+            return fgnn_fail(FGNN_ERR_HIP, std::string("uploading the layer tables: ") + hipGetErrorString(e));
+        }
+    }
+    g->num_layers = num_layers;
+    g->h_layer_of = lay;
+    return FGNN_OK;
+}
+
+}  // namespace
+
+extern "C" int fgnn_greedy_layers(int n, int m_x, int m_z, int nnz_x, const int32_t* chk_x, const int32_t* var_x, int nnz_z,
+                                  const int32_t* chk_z, const int32_t* var_z, int32_t* layer_of, int32_t* num_layers)
+{
+    if (!layer_of || !num_layers) return fgnn_fail(FGNN_ERR_ARG, "layer_of or num_layers is NULL");
+    std::vector<int> ptr, vn;
+    const int rc = check_qubits(n, m_x, m_z, nnz_x, chk_x, var_x, nnz_z, chk_z, var_z, ptr, vn);
+    if (rc) return rc;
+    greedy_layers(n, m_x + m_z, ptr, vn, layer_of, num_layers);
+    return FGNN_OK;
+}
+
+extern "C" int fgnn_validate_layers(int n, int m_x, int m_z, int nnz_x, const int32_t* chk_x, const int32_t* var_x, int nnz_z,
+                                    const int32_t* chk_z, const int32_t* var_z, int num_layers, const int32_t* layer_of)
+{
+    std::vector<int> ptr, vn;
+    const int rc = check_qubits(n, m_x, m_z, nnz_x, chk_x, var_x, nnz_z, chk_z, var_z, ptr, vn);
+    if (rc) return rc;
+    return validate_layers(n, m_x, m_x + m_z, ptr, vn, num_layers, layer_of);
+}
+
+extern "C" int fgnn_graph_set_layers(fgnn_graph* g, int num_layers, const int32_t* layer_of)
+{
+    if (!g) return fgnn_fail(FGNN_ERR_ARG, "graph is NULL");
+    if (g->host_only) return fgnn_fail(FGNN_ERR_STATE, "a host-only graph carries no device tables");
+    return install_layers(g, num_layers, layer_of);
+}
+
+extern "C" int fgnn_graph_layers(const fgnn_graph* g, int32_t* num_layers, int32_t* layer_of)
+{
+    if (!g || !num_layers) return fgnn_fail(FGNN_ERR_ARG, "NULL argument");
+    *num_layers = g->num_layers;
+    if (layer_of) std::copy(g->h_layer_of.begin(), g->h_layer_of.end(), layer_of);
+    return FGNN_OK;
+}
+
+int fgnn_graph_ensure_layers(const fgnn_graph* g)
+{
+    if (g->num_layers > 0) return FGNN_OK;
+    if (g->host_only) return fgnn_fail(FGNN_ERR_STATE, "a host-only graph carries no device tables");
+    return install_layers(g, 0, nullptr);
 }
 
 // Per-launch timing of the BP4 kernel: HIP events recorded on the launch stream immediately before and

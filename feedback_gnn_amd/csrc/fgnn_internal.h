@@ -58,6 +58,12 @@ struct fgnn_graph {
     void* row_alloc[6][4];
     void* basis_dev[2] = {nullptr, nullptr};  // pivot rows of hx / hz (fgnn_graph_set_basis, OSD)
     int basis_rank[2] = {0, 0};
+    // layering of the serial schedule (fgnn_graph_set_layers; fgnn_bp4_decode_layered installs the greedy one on a graph without):
+    // layer_of per check (hx checks first, then hz) on the host; on the device the checks of layer l = lay_chk[lay_cptr[l] ..
+    // lay_cptr[l+1]) ascending, and their edges in the same order = lay_edge[lay_eptr[l] .. lay_eptr[l+1]) as (slot, qubit) pairs
+    mutable int num_layers = 0;
+    mutable std::vector<int32_t> h_layer_of;
+    mutable void* layer_alloc[4] = {nullptr, nullptr, nullptr, nullptr};  // lay_cptr, lay_chk, lay_eptr, lay_edge
     // optional per-launch timing of the BP4 kernel with HIP events on the launch stream (fgnn_profile_*)
     mutable bool prof_on = false;
     mutable int prof_n = 0;
@@ -221,6 +227,9 @@ struct LaunchGeom {
     int tpc, cpb, threads, blocks;
 };
 LaunchGeom fgnn_geom(const fgnn_graph* g, int B);
+
+// the greedy layering on a graph that has none (fgnn_bp4_decode_layered takes a const handle: the layer tables are mutable members)
+int fgnn_graph_ensure_layers(const fgnn_graph* g);
 
 // internal entry points with an optional slot->sample indirection (compacted sandwich rounds); bp4: flagged[b] (optional) = the
 // decision's syndrome differs from the measured one — the sandwich's flag test fused into the decoder's epilogue

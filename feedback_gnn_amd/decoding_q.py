@@ -19,7 +19,9 @@ class QLDPCBPDecoder:
     Parameters follow decoding_q.py:15-27: ``code`` (css_code), ``trainable``, ``cn_type`` in
     {'boxplus', 'boxplus-phi', 'minsum'}, ``hard_out``/``track_exit``/``loss_type`` (stored, unused —
     as in the reference), ``num_iter``, ``normalization_factor``, ``output_dtype``, ``stage_one``,
-    ``stage_two``.  Extra keywords: ``device``; ``graph`` (share another decoder's TannerGraph); ``reference_dtypes`` (default True) returns
+    ``stage_two``.  Extra keywords: ``schedule`` ('flooding', the reference's; 'layered' updates the checks layer by layer, each seeing
+    the results of the layers before it — plain and ``stage_one`` calls only, NotImplementedError with ``trainable`` / ``stage_two``)
+    and ``layers`` (a layering for `TannerGraph.set_layers`; default: the graph's own, else the greedy one); ``device``; ``graph`` (share another decoder's TannerGraph); ``reference_dtypes`` (default True) returns
     ``x_hat`` as int64 and ``z_hat`` as float64 exactly like decoding_q.py:788-790, False keeps uint8.
 
     Call: ``decoder((llr_ch[bs,3,n] float32, syndrome_x[m_x,bs], syndrome_z[m_z,bs]))`` →
@@ -30,9 +32,16 @@ class QLDPCBPDecoder:
 
     def __init__(self, code, trainable=False, cn_type='boxplus', hard_out=True, track_exit=False, num_iter=32,
                  normalization_factor=0.625, output_dtype=torch.float32, loss_type='boxplus-phi', stage_one=False,
-                 stage_two=False, device=None, reference_dtypes=True, graph=None, **kwargs):
+                 stage_two=False, device=None, reference_dtypes=True, graph=None, schedule="flooding", layers=None, **kwargs):
         if cn_type not in CN_TYPES:
             raise ValueError('Unknown node type.')  # decoding_q.py:107
+        if schedule not in ("flooding", "layered"):
+            raise ValueError(f"schedule must be 'flooding' or 'layered', got {schedule!r}")
+        if schedule == "layered" and (trainable or stage_two):
+            raise NotImplementedError("the layered schedule has no per-iteration trace: trainable / stage_two decoders run flooding only")
+        if layers is not None and schedule != "layered":
+            raise ValueError("layers= belongs to schedule='layered'")
+        self._schedule = schedule
         self._trainable = bool(trainable)
         self._cn_type = cn_type
         self._hard_out = hard_out
@@ -51,6 +60,8 @@ class QLDPCBPDecoder:
             raise ValueError("shared graph was built for a different stage_one/stage_two setting")
         # decoders of one sandwich can share one device graph (``graph=``): the tables are immutable
         self.graph = graph if graph is not None else TannerGraph(code, stage_one=want_stage, device=device)
+        if schedule == "layered" and (layers is not None or self.graph.layers()[0] == 0):
+            self.graph.set_layers(layers)  # None: the greedy layering; a shared graph keeps the layering it already has
         self._num_vns = self.graph.n
         self._num_cns_x = self.graph.m_x
         self._num_cns_z = self.graph.m_z
@@ -65,6 +76,11 @@ class QLDPCBPDecoder:
     @property
     def cn_type(self):
         return self._cn_type
+
+    @property
+    def schedule(self):
+        """'flooding' (all qubits, then all checks: fgnn_bp4_decode) or 'layered' (the checks layer by layer: fgnn_bp4_decode_layered)."""
+        return self._schedule
 
     @property
     def normalization_factor(self):
@@ -126,8 +142,8 @@ class QLDPCBPDecoder:
         g = self.graph
         if self._trainable or self._stage_two:
             return self._call_with_logit_trace(llr_ch, sx, sz)
-        out = g.bp4_decode(sx, sz, self._num_iter, self._cn_type, self._normalization_factor, llr_ch=llr_ch,
-                           want_logits=self._stage_one)
+        decode = g.bp4_decode_layered if self._schedule == "layered" else g.bp4_decode
+        out = decode(sx, sz, self._num_iter, self._cn_type, self._normalization_factor, llr_ch=llr_ch, want_logits=self._stage_one)
         x_hat, z_hat = self._hard_out_dtypes(out["x_hat"], out["z_hat"])
         if self._stage_one:
             llr = out["llr"]

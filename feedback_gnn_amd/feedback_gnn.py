@@ -250,6 +250,9 @@ class Sandwich_BP_GNN_Evaluation_Model:
             raise ValueError("wt=True needs an explicit p0: the second argument of call() is then an error weight, not a rate")
         if len(decoders) < num_layers or len(feedbacks) < num_layers - 1:
             raise ValueError("need num_layers decoders and num_layers-1 feedbacks")
+        if any(getattr(d, "schedule", "flooding") != "flooding" for d in decoders[:num_layers]):
+            raise NotImplementedError("the fused sandwich driver (fgnn_sandwich_decode) runs flooding BP4 only: a decoder with "
+                                      "schedule='layered' cannot be a layer of it")
         self.k, self.n = code.K, code.N
         self.hx, self.hz, self.lx, self.lz = code.hx, code.hz, code.lx, code.lz
         self.hx_perp, self.hz_perp = code.hx_perp, code.hz_perp
@@ -474,7 +477,8 @@ class First_Stage_BP_Model:
         p0 = np.float32(self.p0)
         L = float(np.log(np.float32(3.0) * (np.float32(1.0) - p0) / p0, dtype=np.float32))
         d = self.decoder
-        o = g.bp4_decode(sx, sz, d.num_iter, d.cn_type, d.normalization_factor, llr_const=L)
+        decode = g.bp4_decode_layered if getattr(d, "schedule", "flooding") == "layered" else g.bp4_decode
+        o = decode(sx, sz, d.num_iter, d.cn_type, d.normalization_factor, llr_const=L)
         return o["llr"].permute(0, 2, 1).contiguous(), o["x_logit"].t(), o["z_logit"].t()
 
     call = __call__
@@ -491,6 +495,9 @@ class Second_Stage_GNN_BP_Model:
     ``model.trainable_weights`` — see ``feedback_gnn_amd.training`` for the optimizer and the loop of Feedback_GNN.ipynb."""
 
     def __init__(self, code, feedback, decoder, num_iter=16, trainable=True, loss_from=8):
+        if getattr(decoder, "schedule", "flooding") != "flooding":
+            raise NotImplementedError("the second training stage needs the per-iteration trace and the reverse pass of flooding BP4: "
+                                      "there is no layered trace")
         self.feedback, self.decoder, self.num_iter, self.loss_from, self.trainable = feedback, decoder, int(num_iter), int(loss_from), trainable
 
     @property

@@ -279,6 +279,60 @@ class TannerGraph:
             out["msg_x"], out["msg_z"] = mox, moz
         return out
 
+    # ---- layered (serial) schedule ---------------------------------------------------------------
+    def set_layers(self, layer_of=None):
+        """Install the layering of `bp4_decode_layered` (fgnn_graph_set_layers): ``layer_of`` [m_x + m_z] gives every check (hx checks
+        first, then hz) its layer 0 .. max; None installs the greedy layering.  No layer may be empty and no two checks of a layer may
+        share a qubit, across hx and hz: a ValueError names the offender."""
+        if layer_of is None:
+            check(_lib.lib().fgnn_graph_set_layers(self.handle, 0, None))
+            return
+        lay = np.ascontiguousarray(layer_of, dtype=np.int32)
+        if lay.shape != (self.m_x + self.m_z,):
+            raise ValueError(f"layer_of must have shape ({self.m_x + self.m_z},), got {lay.shape}")
+        check(_lib.lib().fgnn_graph_set_layers(self.handle, int(lay.max()) + 1, _np_ptr(lay)))
+
+    def layers(self):
+        """(num_layers, layer_of [m_x + m_z] int32) of the installed layering; (0, None) when there is none yet."""
+        num = C.c_int32(0)
+        check(_lib.lib().fgnn_graph_layers(self.handle, C.byref(num), None))
+        if num.value == 0:
+            return 0, None
+        lay = np.empty(self.m_x + self.m_z, np.int32)
+        check(_lib.lib().fgnn_graph_layers(self.handle, C.byref(num), _np_ptr(lay)))
+        return int(num.value), lay
+
+    def bp4_decode_layered(self, synd_x, synd_z, num_iter, cn_type="boxplus-phi", factor=1.0, llr_ch=None, llr_const=0.0,
+                           msg_init=None, return_msgs=False, want_logits=True):
+        """`bp4_decode` in the layered (serial) schedule (fgnn_bp4_decode_layered): the checks are updated layer by layer, every update
+        sees the results of the layers before it.  Same keywords and the same result dict; a graph without a layering gets the greedy
+        one (`set_layers`)."""
+        if cn_type not in CN_TYPES:
+            raise ValueError("Unknown node type.")
+        B = int(synd_x.shape[0])
+        synd_x = self._chk(synd_x, (B, self.m_x), torch.uint8, "synd_x")
+        synd_z = self._chk(synd_z, (B, self.m_z), torch.uint8, "synd_z")
+        if llr_ch is not None:
+            llr_ch = self._chk(llr_ch, (B, 3, self.n), torch.float32, "llr_ch")
+        mix = miz = None
+        if msg_init is not None:
+            mix = self._chk(msg_init[0], (B, self.E_x), torch.float32, "msg_init_x")
+            miz = self._chk(msg_init[1], (B, self.E_z), torch.float32, "msg_init_z")
+        llr = self._new((B, 3, self.n), torch.float32)
+        xh = self._new((B, self.n), torch.uint8)
+        zh = self._new((B, self.n), torch.uint8)
+        xl = self._new((B, self.rows_xp), torch.float32) if want_logits else None
+        zl = self._new((B, self.rows_zp), torch.float32) if want_logits else None
+        mox = self._new((B, self.E_x), torch.float32) if return_msgs else None
+        moz = self._new((B, self.E_z), torch.float32) if return_msgs else None
+        check(_lib.lib().fgnn_bp4_decode_layered(self.handle, CN_TYPES[cn_type], int(num_iter), float(factor), _ptr(llr_ch),
+                                                 float(llr_const), _ptr(synd_x), _ptr(synd_z), B, _ptr(mix), _ptr(miz), _ptr(llr),
+                                                 _ptr(xh), _ptr(zh), _ptr(xl), _ptr(zl), _ptr(mox), _ptr(moz), _stream(self.device)))
+        out = dict(llr=llr, x_hat=xh, z_hat=zh, x_logit=xl, z_logit=zl)
+        if return_msgs:
+            out["msg_x"], out["msg_z"] = mox, moz
+        return out
+
     def bp4_decode_trace(self, synd_x, synd_z, num_iter, cn_type="boxplus-phi", factor=1.0, llr_ch=None, llr_const=0.0,
                          msg_init=None, want_tape=False):
         """One launch of `num_iter` iterations that records the soft syndromes after 0, 1, ..., num_iter iterations

@@ -320,6 +320,48 @@ int fgnn_relay_decode(const fgnn_graph* g, float normalization_factor, int pre_i
 int fgnn_relay4_decode(const fgnn_graph* g, int cn_type, float normalization_factor, int pre_iter, int num_legs, int leg_iter,
                        int stop_nconv, const float* gamma, const float* llr_ch, float llr_const, const uint8_t* synd_x,
                        const uint8_t* synd_z, int B, uint8_t* x_hat, uint8_t* z_hat, int32_t* stats, void* stream);
+/* Layers of the serial (layered) check schedule.  Checks are numbered 0..m_x-1 for hx and m_x..m_x+m_z-1 for hz; a layering is
+ * layer_of[m_x+m_z] with values in [0, num_layers) such that every layer is non-empty and no two checks of a layer share a qubit —
+ * across hx and hz too, since a qubit's update reads the messages of both sides.  All pointers are host pointers; fgnn_greedy_layers and
+ * fgnn_validate_layers touch no device.
+ * fgnn_greedy_layers: checks in ascending number, each into the lowest-numbered layer that holds no check sharing a qubit with it.
+ * fgnn_validate_layers: FGNN_OK, or FGNN_ERR_ARG with a message naming the check whose layer is out of range, the empty layer, or
+ * the two checks of one layer and the qubit they share.
+ * fgnn_graph_set_layers: layer_of = NULL installs the greedy layering (num_layers is ignored); a caller's layering is validated as
+ * above and uploaded as a CSR list of checks per layer.  fgnn_graph_layers: the installed layering (*num_layers = 0 and layer_of
+ * untouched when there is none; layer_of may be NULL). */
+int fgnn_greedy_layers(int n, int m_x, int m_z, int nnz_x, const int32_t* chk_x, const int32_t* var_x, int nnz_z, const int32_t* chk_z,
+                       const int32_t* var_z, int32_t* layer_of, int32_t* num_layers);
+int fgnn_validate_layers(int n, int m_x, int m_z, int nnz_x, const int32_t* chk_x, const int32_t* var_x, int nnz_z,
+                         const int32_t* chk_z, const int32_t* var_z, int num_layers, const int32_t* layer_of);
+int fgnn_graph_set_layers(fgnn_graph* g, int num_layers, const int32_t* layer_of);
+int fgnn_graph_layers(const fgnn_graph* g, int32_t* num_layers, int32_t* layer_of);
+/* BP4 in the layered (serial) schedule: the checks are updated one layer at a time and every update sees the results of the layers
+ * before it.  Arguments, buffers and outputs as fgnn_bp4_decode (llr_ch = NULL: llr_const; msg_init_* = NULL: zeros; msg_out_*, x_logit,
+ * z_logit optional; all three cn_types), and a syndrome that is NULL is all-zero.  A graph without a layering gets the greedy one
+ * (fgnn_graph_set_layers(g, 0, NULL)).  All arithmetic is float32 in the order written, on the shared float32 routines of fgnn_math.h:
+ * options 1, 2, 3 and 5 are ignored.  Per codeword, with mu the c->v messages:
+ *     mu = msg_init, or 0
+ *     for it in 0 .. num_iter-1:
+ *         for l in 0 .. num_layers-1:
+ *             for every check c of layer l (any order: they share no qubit):
+ *                 for every edge e = (c, v) of c:
+ *                     Sz_v, Sx_v = sums of the CURRENT mu over v's hz / hx slots, each ascending from 0.0f
+ *                     X = Sz + lam^X_v;  Z = Sx + lam^Z_v;  Y = (Sz + Sx) + lam^Y_v                    (BP4's totals)
+ *                     nu_e = softplus(-X) - lse2(-(Z - mu_e), -(Y - mu_e)) on an hx edge,
+ *                            softplus(-Z) - lse2(-(X - mu_e), -(Y - mu_e)) on an hz edge               (literal form, one per edge)
+ *                 mu on c's edges = check update cn_type of (nu_e)_e with c's syndrome bit, * normalization_factor
+ *     marginals, decisions, soft syndromes and msg_out from the final mu: exactly what fgnn_bp4_decode returns for num_iter = 0 and
+ *     msg_init = mu.
+ * So num_iter = 0 is fgnn_bp4_decode with num_iter = 0, two launches chained through msg_out -> msg_init equal one launch of the
+ * summed iteration count, and a layering of ONE layer (possible only when no two checks share a qubit) is the flooding schedule.
+ * One codeword's messages (fgnn_bp4_decode's slot layout) and 3n floats (the channel LLRs, then the epilogue's binary LLRs) stay in
+ * LDS for the whole launch; a graph they do not fit is refused (FGNN_ERR_ARG), there is no global-memory variant.  Without
+ * fgnn_graph_set_launch a codeword gets at most 256 threads (a layer holds a fraction of the checks).  B = 0: FGNN_OK. */
+int fgnn_bp4_decode_layered(const fgnn_graph* g, int cn_type, int num_iter, float normalization_factor, const float* llr_ch,
+                            float llr_const, const uint8_t* synd_x, const uint8_t* synd_z, int B, const float* msg_init_x,
+                            const float* msg_init_z, float* llr_out, uint8_t* x_hat, uint8_t* z_hat, float* x_logit,
+                            float* z_logit, float* msg_out_x, float* msg_out_z, void* stream);
 /* BinarySymmetricChannel on the all-zero word, BP_BSC_Model.call feedback_gnn.py:213-214: noise = u < p (Philox stream). */
 int fgnn_bsc_noise(uint64_t seed, float p, uint64_t first_sample, int B, int n, uint8_t* noise, void* stream);
 
