@@ -34,6 +34,9 @@ def __getattr__(name):
     if name in ("RelayBPDecoder", "BP2_Relay_Model", "RelayBP4Decoder", "BP4_Relay_Model"):
         from . import relay as _r
         return getattr(_r, name)
+    if name in ("BP4GDDecoder", "BP4_GD_Model"):
+        from . import decimation as _dm
+        return getattr(_dm, name)
     if name in ("GNN_BP4", "MLP"):
         from . import gnn as _gn
         return getattr(_gn, name)

@@ -864,6 +864,34 @@ class TannerGraph:
                                             _ptr(xh), _ptr(zh), _ptr(stats), _stream(self.device)))
         return xh, zh, stats
 
+    def bp4gd_decode(self, synd_x, synd_z, pre_iter, round_iter, max_rounds=None, decim_llr=25.0, cn_type="minsum", factor=1.0,
+                     llr_ch=None, llr_const=0.0, B=None):
+        """BP4 with guided decimation on both graphs (`fgnn_bp4gd_decode`): up to `pre_iter` iterations, then up to `max_rounds` (None:
+        n) rounds that fix the free qubit of largest margin to its decision (LLR magnitude `decim_llr`) and run up to `round_iter`
+        iterations more; `llr_ch` [B, 3, n] or one `llr_const` for all three LLRs of every qubit; a syndrome that is None is all-zero.
+        Returns `(x_hat [B,n] uint8, z_hat [B,n] uint8, stats [B,4] int32 = found, qubits fixed, iterations, k of the last test)`."""
+        if cn_type not in CN_TYPES:
+            raise ValueError("Unknown node type.")
+        for s in (synd_x, synd_z, llr_ch):
+            if s is not None:
+                B = int(s.shape[0])
+        if B is None:
+            raise ValueError("B is needed when neither syndromes nor llr_ch are given")
+        if synd_x is not None:
+            synd_x = self._chk(synd_x, (B, self.m_x), torch.uint8, "synd_x")
+        if synd_z is not None:
+            synd_z = self._chk(synd_z, (B, self.m_z), torch.uint8, "synd_z")
+        if llr_ch is not None:
+            llr_ch = self._chk(llr_ch, (B, 3, self.n), torch.float32, "llr_ch")
+        max_rounds = self.n if max_rounds is None else int(max_rounds)
+        xh = self._new((B, self.n), torch.uint8)
+        zh = self._new((B, self.n), torch.uint8)
+        stats = self._new((B, 4), torch.int32)
+        check(_lib.lib().fgnn_bp4gd_decode(self.handle, CN_TYPES[cn_type], float(factor), int(pre_iter), int(round_iter), max_rounds,
+                                           float(decim_llr), _ptr(llr_ch), float(llr_const), _ptr(synd_x), _ptr(synd_z), B, _ptr(xh),
+                                           _ptr(zh), _ptr(stats), _stream(self.device)))
+        return xh, zh, stats
+
     def bsc_noise(self, seed, p, first_sample, B):
         e = self._new((B, self.n), torch.uint8)
         with torch.cuda.device(self.device):

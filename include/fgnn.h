@@ -320,6 +320,36 @@ int fgnn_relay_decode(const fgnn_graph* g, float normalization_factor, int pre_i
 int fgnn_relay4_decode(const fgnn_graph* g, int cn_type, float normalization_factor, int pre_iter, int num_legs, int leg_iter,
                        int stop_nconv, const float* gamma, const float* llr_ch, float llr_const, const uint8_t* synd_x,
                        const uint8_t* synd_z, int B, uint8_t* x_hat, uint8_t* z_hat, int32_t* stats, void* stream);
+/* BP4 with guided decimation (BP4-GD; Yao, Abu Laban, Haeger, Amat, Pfister, "Belief propagation decoding of quantum LDPC codes with
+ * guided decimation", 2023, quaternary variant): when BP4 has run its iterations without a solution, the most reliable undecided qubit
+ * is fixed to its current decision and BP4 goes on from the messages it has.  llr_ch [B,3,n] (X, Y, Z) or NULL (= llr_const for all
+ * three), synd_x [B,m_x] / synd_z [B,m_z] as fgnn_bp4_decode (NULL = all-zero); all three cn_types.  All arithmetic is float32 in the
+ * order written; sums run over a qubit's slots in ascending order from 0.0f, exactly as fgnn_bp4_decode.  Per codeword, with
+ * D = decim_llr and R = min(max_rounds, n):
+ *     fix_v = free for all v;  mu = 0 on every edge;  its = 0
+ *     lamhat_v = channel LLRs (lam^X, lam^Y, lam^Z) of v while free; once fixed to d:
+ *                d = I: (+D, +D, +D)   d = X: (-D, +0, +0)   d = Z: (+0, +0, -D)   d = Y: (+0, -D, +0)        (order X, Y, Z)
+ *     for r in 0 .. R:                                   (r = number of qubits fixed so far)
+ *         T = pre_iter if r == 0 else round_iter
+ *         for k in 1 .. T:
+ *             BP4 qubit update, literal form (one log-sum-exp per edge; options 1, 2, 3, 5 ignored), with lamhat in place of the channel LLRs
+ *             check update cn_type on both graphs, * normalization_factor;   its += 1
+ *             Sx, Sz = sums of the new hx / hz messages;  M^X = Sz + lamhat^X;  M^Z = Sx + lamhat^Z;  M^Y = (Sz + Sx) + lamhat^Y
+ *             d_v = argmin(0, M^X, M^Z, M^Y), first minimum wins (BP4's rule);  x_v = d_v & 1;  z_v = d_v >> 1
+ *             if hz.x == synd_z and hx.z == synd_x:  found = 1;  stop
+ *         if r == R: stop                                (found = 0; the output is the pair of this last test)
+ *         c = (0, M^X, M^Z, M^Y);  margin_v = min(c_j, j != d_v) - c_{d_v}        (>= +0; one float32 subtraction)
+ *         v* = the free qubit of largest margin, lowest index on ties;  fix v* to d_{v*}.  The messages are kept.
+ * x_hat, z_hat [B,n] = the pair of the last test made; stats [B,4] (int32) = found, qubits fixed, its, the k of the last test.
+ * pre_iter, round_iter >= 1, max_rounds >= 0, decim_llr > 0 (anything else: FGNN_ERR_ARG); B = 0 returns FGNN_OK and needs no
+ * buffers.  With max_rounds = 0 this is fgnn_bp4_decode stopped at its first solution.  The margin stands in for the paper's "largest
+ * posterior probability": it is the log-ratio of the decided Pauli to the runner-up, orders the qubits by how clear their decision is,
+ * needs no transcendental and does not underflow on saturated marginals, where the probabilities themselves all round to 1.  The
+ * messages, decisions and fix marks of a codeword stay in LDS for the whole launch; a graph they do not fit is refused (FGNN_ERR_ARG),
+ * there is no global-memory variant. */
+int fgnn_bp4gd_decode(const fgnn_graph* g, int cn_type, float normalization_factor, int pre_iter, int round_iter, int max_rounds,
+                      float decim_llr, const float* llr_ch, float llr_const, const uint8_t* synd_x, const uint8_t* synd_z, int B,
+                      uint8_t* x_hat, uint8_t* z_hat, int32_t* stats, void* stream);
 /* Layers of the serial (layered) check schedule.  Checks are numbered 0..m_x-1 for hx and m_x..m_x+m_z-1 for hz; a layering is
  * layer_of[m_x+m_z] with values in [0, num_layers) such that every layer is non-empty and no two checks of a layer share a qubit —
  * across hx and hz too, since a qubit's update reads the messages of both sides.  All pointers are host pointers; fgnn_greedy_layers and
