@@ -47,8 +47,96 @@ def _hp_big():
     return cq.hypergraph_product(h, h, "HP_n6480_lds_overflow")
 
 
-# not one of the reference's constructions with a fixture under tests/golden (tests/test_codes.py walks CODE_MAKERS): its own table
-EXTRA_CODE_MAKERS = {"hp_big": _hp_big}
+def _bare_code(hx, hz):
+    """A code object carrying only what TannerGraph / OracleGraph read (the wrapping of `binary_oracle`): dense uint8 hx and hz and one
+    all-zero row each for hx_perp, hz_perp, lx and lz.  No GF(2) rank work: the logical rows are not what these codes test."""
+    import types
+    hx, hz = np.ascontiguousarray(hx, dtype=np.uint8), np.ascontiguousarray(hz, dtype=np.uint8)
+    zero = np.zeros((1, hx.shape[1]), np.uint8)
+    return types.SimpleNamespace(hx=hx, hz=hz, hx_perp=zero, hz_perp=zero, lx=zero, lz=zero)
+
+
+def _shift_sum(l, m, x_pows, y_pows):
+    """The sum of the monomials x^e (e in x_pows) and y^e (e in y_pows) on Z_l x Z_m as a dense uint8 [l m, l m] matrix, in the
+    convention of codes_q.create_bivariate_QC_codes (x = S_l (x) I_m, y = I_l (x) S_m, column i m + j <-> (i, j)): x^e has its ones at
+    (((i - e) mod l) m + j, i m + j), y^e at (i m + (j - e) mod m, i m + j).  m = 1 gives an l x l circulant with the ones of
+    codes_q.create_circulant_matrix(l, [-e, ...])."""
+    i, j = np.divmod(np.arange(l * m), m)
+    h = np.zeros((l * m, l * m), np.uint8)
+    for e in x_pows:
+        h[((i - e) % l) * m + j, i * m + j] ^= 1
+    for e in y_pows:
+        h[i * m + (j - e) % m, i * m + j] ^= 1
+    return h
+
+
+def bb_blocks(l, m):
+    """(A, B) of the bivariate-bicycle construction with ibm72's polynomials, A = x^3 + y + y^2 and B = y^3 + x + x^2, on Z_l x Z_m:
+    [A | B] is (3,6)-regular for l, m >= 4."""
+    return _shift_sum(l, m, [3], [1, 2]), _shift_sum(l, m, [1, 2], [3])
+
+
+def gb_blocks(l):
+    """(A, B) of the generalized-bicycle construction with gb48's exponents [0,2,8,15] and [0,2,12,17] as circulants of size l
+    (ones at (i + c mod l, i), codes_q.create_circulant_matrix): [A | B] is (4,8)-regular."""
+    return _shift_sum(l, 1, [0, -2, -8, -15], []), _shift_sum(l, 1, [0, -2, -12, -17], [])
+
+
+def _bicycle(A, B):
+    """hx = [A | B], hz = [B^T | A^T]."""
+    return _bare_code(np.hstack([A, B]), np.hstack([B.T, A.T]))
+
+
+def _side0(A, B):
+    """A graph for the binary decoders, which read side 0 only: hx = [A | B] and hz = n / dc rows of dc consecutive qubits (dv_z = 1,
+    the same check degree), so every degree is uniform and the packed rows exist while hx's offsets alone pass 2^15.  hz does not
+    commute with hx: this is no CSS code, and nothing here decodes side 1."""
+    hx = np.hstack([A, B])
+    n, dc = hx.shape[1], int(hx[0].sum())
+    assert n % dc == 0
+    hz = np.zeros((n // dc, n), np.uint8)
+    hz[np.arange(n) // dc, np.arange(n)] = 1
+    return _bare_code(hx, hz)
+
+
+def _wide_rows(n):
+    """16 hx and 16 hz checks of 8 distinct qubits each on n qubits (n = 65 535 / 65 536): entry j of a row lies near j n / 8, so
+    entries 4..7 — half of them — lie in [32 768, n), and the last entry of hx row 15 and of hz row 0 is qubit n - 1.  Most qubits
+    have no edge, so the qubit degrees are not uniform: no slot rows, and qubit rows exactly when n < 65 536."""
+    r, j = np.arange(16)[:, None], np.arange(8)[None, :]
+    qx = j * (n // 8) + 257 * r + 31 * j
+    qz = j * (n // 8) + 263 * r + 37 * j + 2000
+    qx[15, 7] = qz[0, 7] = n - 1
+    assert qx.max() == qz.max() == n - 1 and all(len(set(row)) == 8 for q in (qx, qz) for row in q.tolist())
+    hx, hz = np.zeros((16, n), np.uint8), np.zeros((16, n), np.uint8)
+    hx[r, qx] = 1
+    hz[r, qz] = 1
+    return _bare_code(hx, hz)
+
+
+# not one of the reference's constructions with a fixture under tests/golden (tests/test_codes.py walks CODE_MAKERS): its own table.
+# The synthetic regular codes carry the packed 16-bit check rows (fgnn_graph.hip) through the upper half of their range and across
+# both of their limits, 4 E < 65 536 for the slot offsets and n < 65 536 for the qubits; they are built from index arithmetic in
+# milliseconds (tests/test_check_rows_limits_cpu.py states what each one reaches)
+EXTRA_CODE_MAKERS = {
+    "hp_big": _hp_big,
+    # (3,3,6)-regular bivariate bicycle, n = 2 l m, 4 E = 24 n: offsets up to 43 196 / up to 65 516, the last code with slot rows /
+    # 4 E = 65 712, the first without them (the qubit rows stay)
+    "bb1800": lambda: _bicycle(*bb_blocks(30, 30)),
+    "bb2730": lambda: _bicycle(*bb_blocks(35, 39)),
+    "bb2738": lambda: _bicycle(*bb_blocks(37, 37)),
+    # (4,4,8)-regular generalized bicycle, n = 2 l, 4 E = 64 l: offsets up to 63 996 / 4 E = 65 536, the first without slot rows
+    "gb2000": lambda: _bicycle(*gb_blocks(1000)),
+    "gb2048": lambda: _bicycle(*gb_blocks(1024)),
+    # side 0 of the binary decoders: (3,6) with 4 E_x = 42 336 of 4 E = 56 448, (4,8) with 4 E_x = 51 200 of 4 E = 64 000, and (3,6)
+    # past the limit (4 E = 73 728)
+    "side0_36": lambda: _side0(*bb_blocks(42, 42)),
+    "side0_48": lambda: _side0(*gb_blocks(1600)),
+    "side0_36_over": lambda: _side0(*bb_blocks(48, 48)),
+    # qubit rows near 2^16: present at n = 65 535 (qubit 65 534 is read), absent at n = 65 536
+    "wide65535": lambda: _wide_rows(65535),
+    "wide65536": lambda: _wide_rows(65536),
+}
 CODE_MAKERS["gb46_oc"] = lambda: _overcomplete("gb46_oc")
 CODE_MAKERS["gb48_oc"] = lambda: _overcomplete("gb48_oc")
 
