@@ -37,6 +37,9 @@ def __getattr__(name):
     if name in ("BP4GDDecoder", "BP4_GD_Model"):
         from . import decimation as _dm
         return getattr(_dm, name)
+    if name in ("BP4FeedbackDecoder", "BP4_Feedback_Model"):
+        from . import prior_feedback as _pf
+        return getattr(_pf, name)
     if name in ("GNN_BP4", "MLP"):
         from . import gnn as _gn
         return getattr(_gn, name)

@@ -11,6 +11,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libfgnn_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
 
 CN_TYPES = {"boxplus": 0, "boxplus-phi": 1, "minsum": 2}
+FB_RULES = {"perturb": 0, "enhanced": 1}
 ROWS_X_LOGIT, ROWS_Z_LOGIT, ROWS_HX_PERP, ROWS_HZ_PERP, ROWS_LX, ROWS_LZ = 0, 1, 2, 3, 4, 5
 
 
@@ -106,6 +107,9 @@ _SIGNATURES = {
                                      C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "fgnn_bp4gd_decode": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_float,
                                     C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fgnn_bp4fb_decode": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_uint64,
+                                    C.c_uint64, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p]),
     "fgnn_greedy_layers": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.POINTER(C.c_int32)]),
     "fgnn_validate_layers": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,

@@ -892,6 +892,40 @@ class TannerGraph:
                                            _ptr(zh), _ptr(stats), _stream(self.device)))
         return xh, zh, stats
 
+    def bp4fb_decode(self, synd_x, synd_z, rule, pre_iter, attempt_iter, max_attempts, strength, cn_type="minsum", factor=1.0,
+                     restart=False, seed=0x5EED, first_sample=0, llr_ch=None, llr_const=0.0, B=None):
+        """BP4 with prior feedback on both graphs (`fgnn_bp4fb_decode`): up to `pre_iter` iterations, then up to `max_attempts` times
+        the rule `"perturb"` or `"enhanced"` changes the channel LLRs (by `strength`) at qubits of the unsatisfied checks and BP4 runs
+        up to `attempt_iter` iterations more, from the messages it has or, with `restart`, from zero messages.  The rules draw from the
+        Philox stream of `seed` at the global sample indices `first_sample` .. `first_sample + B - 1`; `llr_ch` [B, 3, n] or one
+        `llr_const` for all three LLRs of every qubit; a syndrome that is None is all-zero.  Returns `(x_hat [B,n] uint8, z_hat [B,n]
+        uint8, stats [B,4] int32 = found, feedback steps made, iterations, k of the last test)`."""
+        if cn_type not in CN_TYPES:
+            raise ValueError("Unknown node type.")
+        if rule not in _lib.FB_RULES:
+            raise ValueError('rule must be "perturb" or "enhanced"')
+        for s in (synd_x, synd_z, llr_ch):
+            if s is not None:
+                B = int(s.shape[0])
+        if B is None:
+            raise ValueError("B is needed when neither syndromes nor llr_ch are given")
+        if synd_x is not None:
+            synd_x = self._chk(synd_x, (B, self.m_x), torch.uint8, "synd_x")
+        if synd_z is not None:
+            synd_z = self._chk(synd_z, (B, self.m_z), torch.uint8, "synd_z")
+        if llr_ch is not None:
+            llr_ch = self._chk(llr_ch, (B, 3, self.n), torch.float32, "llr_ch")
+        if not 0 <= int(seed) < 1 << 64 or not 0 <= int(first_sample) < 1 << 64:
+            raise ValueError("seed and first_sample must fit 64 unsigned bits")
+        xh = self._new((B, self.n), torch.uint8)
+        zh = self._new((B, self.n), torch.uint8)
+        stats = self._new((B, 4), torch.int32)
+        check(_lib.lib().fgnn_bp4fb_decode(self.handle, _lib.FB_RULES[rule], CN_TYPES[cn_type], float(factor), int(pre_iter),
+                                           int(attempt_iter), int(max_attempts), float(strength), int(restart), int(seed),
+                                           int(first_sample), _ptr(llr_ch), float(llr_const), _ptr(synd_x), _ptr(synd_z), B, _ptr(xh),
+                                           _ptr(zh), _ptr(stats), _stream(self.device)))
+        return xh, zh, stats
+
     def bsc_noise(self, seed, p, first_sample, B):
         e = self._new((B, self.n), torch.uint8)
         with torch.cuda.device(self.device):

@@ -350,6 +350,53 @@ int fgnn_relay4_decode(const fgnn_graph* g, int cn_type, float normalization_fac
 int fgnn_bp4gd_decode(const fgnn_graph* g, int cn_type, float normalization_factor, int pre_iter, int round_iter, int max_rounds,
                       float decim_llr, const float* llr_ch, float llr_const, const uint8_t* synd_x, const uint8_t* synd_z, int B,
                       uint8_t* x_hat, uint8_t* z_hat, int32_t* stats, void* stream);
+/* BP4 with prior feedback: when BP4 has run its iterations without a solution, the unsatisfied checks of its last estimate choose
+ * qubits whose channel LLRs are changed, and BP4 runs again: the hand-written rules the learned feedback of the GNN replaces.
+ *   FGNN_FB_PERTURB    random perturbation (Poulin, Chung, "On the iterative decoding of sparse quantum codes", 2008)
+ *   FGNN_FB_ENHANCED   enhanced feedback (Wang, Sanders, Poulin, "Enhanced feedback iterative decoding of sparse quantum codes", 2012)
+ * llr_ch [B,3,n] (X, Y, Z) or NULL (= llr_const for all three), synd_x [B,m_x] / synd_z [B,m_z] (NULL = all-zero) and all three
+ * cn_types as fgnn_bp4gd_decode.  All arithmetic is float32 in the order written; sums run over a qubit's slots in ascending order from
+ * 0.0f, exactly as fgnn_bp4_decode.  Checks are numbered 0..m_x-1 (hx) and m_x..m_x+m_z-1 (hz), as for the layers.  Per codeword b, with
+ * i = first_sample + b, lam the channel LLRs (never changed), F = strength and A = max_attempts:
+ *     lamhat = lam;  mu = 0 on every edge;  its = 0
+ *     for a in 0 .. A:                                   (a = number of feedback steps made so far)
+ *         T = pre_iter if a == 0 else attempt_iter
+ *         if restart and a > 0: mu = 0 on every edge
+ *         for k in 1 .. T:
+ *             BP4 qubit update, literal form (one log-sum-exp per edge; options 1, 2, 3, 5 ignored), with lamhat in place of the channel LLRs
+ *             check update cn_type on both graphs, * normalization_factor;   its += 1
+ *             Sx, Sz = sums of the new hx / hz messages;  M^X = Sz + lamhat^X;  M^Z = Sx + lamhat^Z;  M^Y = (Sz + Sx) + lamhat^Y
+ *             d_v = argmin(0, M^X, M^Z, M^Y), first minimum wins (BP4's rule);  x_v = d_v & 1;  z_v = d_v >> 1
+ *             if hz.x == synd_z and hx.z == synd_x:  found = 1;  stop
+ *         if a == A: stop                                (found = 0; the output is the pair of this last test)
+ *         U = the checks (both sides) whose parity in this last test (k = T) differs from their syndrome bit
+ *         lamhat = lam, then the rule below with attempt number a + 1        (feedback never accumulates: always from lam)
+ * Random draws: w(idx, att, s) = fg_philox4x32_10(lo32(i), hi32(i), idx, (att << 8) | s, lo32(seed), hi32(seed)) (fgnn_rng.h), floats
+ * unit(x) = fg_u32_to_unit(x).  Streams 0-2 of fgnn_rng.h keep the fourth counter word below 256, so the channel noise of the same
+ * seed is never reused.
+ *   FGNN_FB_PERTURB: for every qubit v on at least one check of U, with w = w(v, a+1, 3):
+ *         lamhat^X_v = lam^X_v - F * unit(w[0]);  lamhat^Y_v = lam^Y_v - F * unit(w[1]);  lamhat^Z_v = lam^Z_v - F * unit(w[2])
+ *     each one product, then one subtraction, not contracted.  This is Poulin-Chung's p_W -> (1 + delta) p_W on the qubits of the
+ *     frustrated checks, written in the LLR domain (lam^W = log(p_I / p_W): raising p_W by a random factor lowers lam^W by a random
+ *     amount), so that no transcendental enters the definition.
+ *   FGNN_FB_ENHANCED: every c in U has the key (uint64) w(c, a+1, 4)[0] << 32 | (0xFFFFFFFF - c); c* is the check of largest key;
+ *     v* is the j-th qubit of c* in ascending qubit order, j = fg_fy_pick(unit(w(c*, a+1, 4)[1]), deg(c*)).  With s the syndrome bit of
+ *     c* and t = s ? -F : +F, an hx check changes lamhat^Z_{v*} = lam^Z + t and lamhat^Y_{v*} = lam^Y + t, an hz check lamhat^X_{v*}
+ *     and lamhat^Y_{v*} the same way.  The measured bit says that the error anticommutes with the check on an odd (s = 1) or even (s = 0)
+ *     number of its qubits and the estimate says the opposite: the two Paulis that anticommute with the check are made likelier, or
+ *     less likely, at one of its qubits.  A check without qubits changes nothing.
+ *   All other qubits keep lam.
+ * x_hat, z_hat [B,n] = the pair of the last test made; stats [B,4] (int32) = found, the a of that test, its, the k of that test.
+ * rule 0 or 1, pre_iter and attempt_iter >= 1, 0 <= max_attempts <= 65535, strength finite and >= 0, restart 0 or 1 (anything else:
+ * FGNN_ERR_ARG); B = 0 returns FGNN_OK and needs no buffers.  With max_attempts = 0 the result is that of fgnn_bp4gd_decode with
+ * max_rounds = 0, bit for bit (stats column 1 is 0).  The original enhanced-feedback paper restarts BP from zero messages
+ * (restart = 1); restart = 0 keeps them.  The messages, decisions and marks of a codeword stay in LDS for the whole launch, in the byte
+ * count of fgnn_bp4gd_decode; a graph they do not fit is refused (FGNN_ERR_ARG), there is no global-memory variant. */
+enum { FGNN_FB_PERTURB = 0, FGNN_FB_ENHANCED = 1 };
+int fgnn_bp4fb_decode(const fgnn_graph* g, int rule, int cn_type, float normalization_factor, int pre_iter, int attempt_iter,
+                      int max_attempts, float strength, int restart, uint64_t seed, uint64_t first_sample, const float* llr_ch,
+                      float llr_const, const uint8_t* synd_x, const uint8_t* synd_z, int B, uint8_t* x_hat, uint8_t* z_hat,
+                      int32_t* stats, void* stream);
 /* Layers of the serial (layered) check schedule.  Checks are numbered 0..m_x-1 for hx and m_x..m_x+m_z-1 for hz; a layering is
  * layer_of[m_x+m_z] with values in [0, num_layers) such that every layer is non-empty and no two checks of a layer share a qubit —
  * across hx and hz too, since a qubit's update reads the messages of both sides.  All pointers are host pointers; fgnn_greedy_layers and
