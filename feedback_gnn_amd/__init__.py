@@ -40,6 +40,9 @@ def __getattr__(name):
     if name in ("BP4FeedbackDecoder", "BP4_Feedback_Model"):
         from . import prior_feedback as _pf
         return getattr(_pf, name)
+    if name in ("AMBP4Decoder", "BP4_AMBP_Model"):
+        from . import mbp as _mb
+        return getattr(_mb, name)
     if name in ("GNN_BP4", "MLP"):
         from . import gnn as _gn
         return getattr(_gn, name)

@@ -43,6 +43,17 @@ FG_FN float vn_edge(float num, float A, float Y, float mu)
     return num - MX::lse2(-Ae, -Ye);
 }
 
+// the same edge with its own c->v message taken out at strength w (MBP4's inhibition term, fgnn_mbp4.hip): own = w * mu is one
+// product, then the two subtractions (never an fma: the library is built with -ffp-contract=off).  w = 1.0f: own = mu bit for bit, so
+// this is vn_edge
+template <typename MX>
+FG_FN float vn_edge_own(float num, float A, float Y, float mu, float w)
+{
+    const float own = w * mu;
+    const float Ae = A - own, Ye = Y - own;
+    return num - MX::lse2(-Ae, -Ye);
+}
+
 // the same edge in the shared form (FGNN_OPT_BP4_SHARED_LSE): (A - mu) - (Y - mu) = A - Y for every edge of a side, so the part of the
 // log-sum-exp that depends on the difference alone, c = lse2_corr(-A, -Y), comes once per qubit and side
 FG_FN float vn_edge_shared(float num, float c, float A, float Y, float mu)

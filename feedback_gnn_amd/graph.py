@@ -926,6 +926,40 @@ class TannerGraph:
                                            _ptr(zh), _ptr(stats), _stream(self.device)))
         return xh, zh, stats
 
+    def mbp4_decode(self, synd_x, synd_z, factors, owns, pre_iter, attempt_iter, cn_type="minsum", restart=True, llr_ch=None,
+                    llr_const=0.0, B=None):
+        """BP4 with message-strength control on both graphs (`fgnn_mbp4_decode`): attempt a (up to `pre_iter` iterations for a = 0,
+        `attempt_iter` for the later ones) multiplies every check output by `factors[a]` and takes an edge's own message out of the
+        qubit totals multiplied by `owns[a]`; the first estimate that reproduces both syndromes ends the codeword.  `factors` and
+        `owns` are host sequences of the same length, 1 .. 64, rounded to float32 (Kuo-Lai's MBP4: owns[a] = alpha_a, factors[a] =
+        base / alpha_a); with `restart` every attempt after the first starts from zero messages; `llr_ch` [B, 3, n] or one
+        `llr_const` for all three LLRs of every qubit; a syndrome that is None is all-zero.  Returns `(x_hat [B,n] uint8, z_hat [B,n]
+        uint8, stats [B,4] int32 = found, the attempt of the last test, iterations, k of the last test)`."""
+        if cn_type not in CN_TYPES:
+            raise ValueError("Unknown node type.")
+        factors = np.ascontiguousarray(np.asarray(factors, dtype=np.float32).reshape(-1))
+        owns = np.ascontiguousarray(np.asarray(owns, dtype=np.float32).reshape(-1))
+        if len(factors) != len(owns):
+            raise ValueError("factors and owns must have the same length")
+        for s in (synd_x, synd_z, llr_ch):
+            if s is not None:
+                B = int(s.shape[0])
+        if B is None:
+            raise ValueError("B is needed when neither syndromes nor llr_ch are given")
+        if synd_x is not None:
+            synd_x = self._chk(synd_x, (B, self.m_x), torch.uint8, "synd_x")
+        if synd_z is not None:
+            synd_z = self._chk(synd_z, (B, self.m_z), torch.uint8, "synd_z")
+        if llr_ch is not None:
+            llr_ch = self._chk(llr_ch, (B, 3, self.n), torch.float32, "llr_ch")
+        xh = self._new((B, self.n), torch.uint8)
+        zh = self._new((B, self.n), torch.uint8)
+        stats = self._new((B, 4), torch.int32)
+        check(_lib.lib().fgnn_mbp4_decode(self.handle, CN_TYPES[cn_type], len(factors), factors.ctypes.data, owns.ctypes.data,
+                                          int(pre_iter), int(attempt_iter), int(restart), _ptr(llr_ch), float(llr_const), _ptr(synd_x),
+                                          _ptr(synd_z), B, _ptr(xh), _ptr(zh), _ptr(stats), _stream(self.device)))
+        return xh, zh, stats
+
     def bsc_noise(self, seed, p, first_sample, B):
         e = self._new((B, self.n), torch.uint8)
         with torch.cuda.device(self.device):

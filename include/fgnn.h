@@ -397,6 +397,39 @@ int fgnn_bp4fb_decode(const fgnn_graph* g, int rule, int cn_type, float normaliz
                       int max_attempts, float strength, int restart, uint64_t seed, uint64_t first_sample, const float* llr_ch,
                       float llr_const, const uint8_t* synd_x, const uint8_t* synd_z, int B, uint8_t* x_hat, uint8_t* z_hat,
                       int32_t* stats, void* stream);
+/* BP4 with message-strength control (MBP4 / AMBP4; Kuo, Lai, "Exploiting degeneracy in belief propagation decoding of quantum codes",
+ * npj Quantum Information, 2022), flooding schedule: a qubit's belief is formed from its incoming check messages scaled by 1 / alpha,
+ * while the message it sends back to a check has that check's own contribution removed at full strength (the inhibition term); the
+ * adaptive form tries a list of alphas and keeps the first whose estimate reproduces both syndromes.  This entry point holds no
+ * formula for alpha: every check output of attempt a is multiplied by factor[a], and a qubit takes the edge's own message out of the
+ * totals multiplied by own[a].  Kuo-Lai's MBP4 with strength alpha_a on a check rule normalised by `base` is own[a] = alpha_a,
+ * factor[a] = base / alpha_a.  factor and own are HOST arrays of num_attempts floats, shared by the batch.  llr_ch [B,3,n] (X, Y, Z)
+ * or NULL (= llr_const for all three), synd_x [B,m_x] / synd_z [B,m_z] (NULL = all-zero) and all three cn_types as fgnn_bp4fb_decode.
+ * All arithmetic is float32 in the order written; sums run over a qubit's slots in ascending order from 0.0f, exactly as
+ * fgnn_bp4_decode.  Per codeword, with lam the channel LLRs (never changed):
+ *     mu = 0 on every edge;  its = 0
+ *     for a in 0 .. num_attempts-1:
+ *         T = pre_iter if a == 0 else attempt_iter
+ *         if restart and a > 0: mu = 0 on every edge
+ *         for k in 1 .. T:
+ *             Sz, Sx = sums of the hz / hx messages at qubit v;  X = Sz + lam^X;  Z = Sx + lam^Z;  Y = (Sz + Sx) + lam^Y      (BP4's totals)
+ *             own_e = own[a] * mu_e                                                   (one product, not contracted into what follows)
+ *             nu_e = softplus(-X) - lse2(-(Z - own_e), -(Y - own_e)) on an hx edge,
+ *                    softplus(-Z) - lse2(-(X - own_e), -(Y - own_e)) on an hz edge    (literal form, one log-sum-exp per edge; options
+ *                                                                                      1, 2, 3, 5 ignored)
+ *             mu = check update cn_type of nu on both graphs, * factor[a];   its += 1
+ *             Sx, Sz = sums of the new hx / hz messages;  M^X = Sz + lam^X;  M^Z = Sx + lam^Z;  M^Y = (Sz + Sx) + lam^Y
+ *             d_v = argmin(0, M^X, M^Z, M^Y), first minimum wins (BP4's rule);  x_v = d_v & 1;  z_v = d_v >> 1
+ *             if hz.x == synd_z and hx.z == synd_x:  found = 1;  stop
+ * x_hat, z_hat [B,n] = the pair of the last test made; stats [B,4] (int32) = found, the a of that test, its, the k of that test.
+ * 1 <= num_attempts <= 64, pre_iter and attempt_iter >= 1, restart 0 or 1, every factor[a] finite and > 0, every own[a] finite and
+ * >= 0 (anything else: FGNN_ERR_ARG); B = 0 returns FGNN_OK and needs no buffers.  With own[a] = 1.0f the product is mu_e bit for bit:
+ * num_attempts = 1 and own[0] = 1.0f give the result of fgnn_bp4fb_decode with max_attempts = 0 and normalization_factor = factor[0],
+ * bit for bit (stats column 1 is 0).  The messages and decisions of a codeword stay in LDS for the whole launch, next to the two
+ * 64-float tables of factor and own; a graph they do not fit is refused (FGNN_ERR_ARG), there is no global-memory variant. */
+int fgnn_mbp4_decode(const fgnn_graph* g, int cn_type, int num_attempts, const float* factor, const float* own, int pre_iter,
+                     int attempt_iter, int restart, const float* llr_ch, float llr_const, const uint8_t* synd_x, const uint8_t* synd_z,
+                     int B, uint8_t* x_hat, uint8_t* z_hat, int32_t* stats, void* stream);
 /* Layers of the serial (layered) check schedule.  Checks are numbered 0..m_x-1 for hx and m_x..m_x+m_z-1 for hz; a layering is
  * layer_of[m_x+m_z] with values in [0, num_layers) such that every layer is non-empty and no two checks of a layer share a qubit —
  * across hx and hz too, since a qubit's update reads the messages of both sides.  All pointers are host pointers; fgnn_greedy_layers and
