@@ -88,12 +88,14 @@ struct BpArgs {
 // bit-exactness as a number.  What a TensorFlow-ROCm build of the reference would execute is of this kind.
 template <bool HWT>
 struct Mx {
-    static __device__ __forceinline__ float softplus(float t) { return fg_softplus(t); }
+    // fg_softplus / fg_phi with the last select as one v_max_f32 / v_med3_f32 instead of v_cmp + v_cndmask: the same bits on every
+    // input (fgnn_math_ranged.h; tests/test_math_selects.py, exhaustive)
+    static __device__ __forceinline__ float softplus(float t) { return fg_softplus_max(t); }
     // the log of a log-sum-exp sees 1 + exp(-min(d, 20)) in [1, 2]: fgnn_math_ranged.h forms its exponent term without the half-rate
     // int -> float conversion of fg_log — the same bits (tests/test_math_ranged.py, exhaustive)
     static __device__ __forceinline__ float lse2(float a, float b) { return fg_lse2_ranged(a, b); }
     static __device__ __forceinline__ float lse2_corr(float a, float b) { return fg_lse2_corr_ranged(a, b); }
-    static __device__ __forceinline__ float phi(float x) { return fg_phi(x); }
+    static __device__ __forceinline__ float phi(float x) { return fg_phi_med(x); }
 };
 template <>
 struct Mx<true> {
@@ -211,7 +213,7 @@ __device__ __forceinline__ void phi_n(const float (&x)[N], float (&out)[N])
         const float a = fg_u2f(fg_f2u(rc1[k]) - eb1[k]);
         const float r1 = FG_FMA(y[k], a, a - 1.0f);
         float sp = FG_FMA((float)(int32_t)eb1[k], FG_LN2_S23, lc1[k] + fg_log1p_small(r1));
-        sp = (xc[k] > FG_SOFTPLUS_THRESH) ? xc[k] : sp;
+        sp = fg_phi_select_med(sp, xc[k]);  // the select of fg_phi as a median (fgnn_math_ranged.h)
         const float mm = fg_u2f(fg_f2u(y[k] - 1.0f) - eb2[k]);
         const float r2 = FG_FMA(mm, rc2[k], -1.0f);
         const float lg = FG_FMA((float)(int32_t)eb2[k], FG_LN2_S23, lc2[k] + fg_log1p_small(r2));

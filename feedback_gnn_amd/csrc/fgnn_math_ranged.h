@@ -43,4 +43,51 @@ FG_FN float fg_lse2_ranged(float a, float b)
     return fg_lse2_corr_ranged(a, b) + m;
 }
 
+/* ---- the selects of fg_phi / fg_softplus as one ordered-value instruction ------------------------------------------------------
+ * Both routines end in "x above the softplus threshold ? x : computed value", a v_cmp + v_cndmask pair (and a VCC dependency) on
+ * the device.  The computed value is ordered against x and against one constant in a way that lets a median / a maximum pick the
+ * same float (tests/test_math_selects.py: exhaustive on the CPU; tests/math_selects_gpu.hip on the device):
+ *   phi      : S = fg_log1p(fg_exp(FG_SOFTPLUS_THRESH)) is the float after the threshold.  For xc <= threshold the computed
+ *              sp = log1p(exp(xc)) lies in [xc, S]; for xc > threshold (xc >= S) it is never in [S, xc).  med3(sp, xc, S) is therefore
+ *              sp below and xc above.  max(sp, xc) alone is NOT enough: on 753 561 floats between 13.9423857 and 14.7666502 the
+ *              computed log1p exceeds xc.
+ *   softplus : r = exp(t) below -threshold (0 under -87), log1p(exp(min(t, threshold))) otherwise; r >= t wherever the result is r,
+ *              and r = S <= t wherever it is t: max(t, r), written as (t < -threshold) ? exp : max(t, log1p).  The two LOW selects
+ *              cannot go the same way: log1p(exp t) != exp t on 2 309 063 floats of [-16.2889576, -13.9423857].
+ * No NaNs reach either routine and neither ordered value is a zero whose sign could matter. */
+#define FG_SOFTPLUS_AT_THRESH 13.9423857f /* fg_log1p(fg_exp(FG_SOFTPLUS_THRESH)), bits 0x415f1403 = FG_SOFTPLUS_THRESH + 1 ulp */
+
+/* median of three: one v_med3_f32 on the device (as FG_CLAMP), the min / max composition on the host */
+#if defined(__HIP_DEVICE_COMPILE__)
+#define FG_MED3(a, b, c) __builtin_amdgcn_fmed3f((a), (b), (c))
+#else
+#define FG_MED3(a, b, c) FG_MAX(FG_MIN((a), (b)), FG_MIN(FG_MAX((a), (b)), (c)))
+#endif
+
+/* the select of fg_phi on sp = fg_log1p(fg_exp(xc)), xc in [FG_PHI_MIN, FG_PHI_MAX] */
+FG_FN float fg_phi_select_med(float sp, float xc) { return FG_MED3(sp, xc, FG_SOFTPLUS_AT_THRESH); }
+
+/* fg_phi(x) for every x: the operations of fg_phi in the same order, the select as a median. */
+FG_FN float fg_phi_med(float x)
+{
+    float xc = FG_CLAMP(x, FG_PHI_MIN, FG_PHI_MAX);
+    float y = fg_exp(xc);
+    float sp = fg_phi_select_med(fg_log1p(y), xc);
+    return sp - fg_log(y - 1.0f);
+}
+
+/* fg_softplus(t) for every finite t: the operations of fg_softplus in the same order, the last select as a maximum. */
+FG_FN float fg_softplus_max(float t)
+{
+    float tc = FG_CLAMP(t, -87.0f, FG_SOFTPLUS_THRESH);
+    float y = fg_exp(tc);
+    float l = fg_log1p(y);
+    float small = (t < -87.0f) ? 0.0f : y;
+    /* max(t, r) with r = (t < -thr) ? small : l, the maximum taken inside the select: below -thr it is small itself (small >= 0 > t).
+     * This way both operands of the maximum are results of float arithmetic; with r as an operand the compiler puts a canonicalising
+     * v_max_f32 r, r in front (small carries fg_exp's integer-built bits), which costs what the maximum saves. */
+    float m = FG_MAX(t, l);
+    return (t < -FG_SOFTPLUS_THRESH) ? small : m;
+}
+
 #endif /* FGNN_MATH_RANGED_H */
