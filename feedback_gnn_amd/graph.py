@@ -386,8 +386,8 @@ class TannerGraph:
         if not chained:  # one launch: the kernel records the soft syndromes and the tape itself (fgnn_bp4_decode_trace)
             return self.bp4_decode_trace(synd_x, synd_z, num_iter, "boxplus-phi", factor, llr_ch=llr_ch, want_tape=True)
         B, T = int(llr_ch.shape[0]), int(num_iter)
-        tx = torch.zeros((T + 1, B, self.E_x), dtype=torch.float32, device=self.device)
-        tz = torch.zeros((T + 1, B, self.E_z), dtype=torch.float32, device=self.device)
+        tx = self._new((T + 1, B, self.E_x), torch.float32).zero_()
+        tz = self._new((T + 1, B, self.E_z), torch.float32).zero_()
         xl = self._new((T + 1, B, self.rows_xp), torch.float32)
         zl = self._new((T + 1, B, self.rows_zp), torch.float32)
         out = self.bp4_decode(synd_x, synd_z, 0, "boxplus-phi", factor, llr_ch=llr_ch)
@@ -589,7 +589,7 @@ class TannerGraph:
     # ---- Sandwich body -----------------------------------------------------------------------------------
     def sandwich_workspace(self, B):
         nbytes = _lib.lib().fgnn_sandwich_workspace_bytes(self.handle, int(B))
-        return torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        return self._new((nbytes,), torch.uint8)
 
     def sandwich_decode(self, synd_x, synd_z, iters, weights_list, llr_const, factors=None, cn_types=None, compact=False,
                         workspace=None, return_llr=False, return_rounds=False):
@@ -645,13 +645,12 @@ class TannerGraph:
         try:
             for s in range(0, B, chunk):
                 sx, sz = synd_x[s:s + chunk].contiguous(), synd_z[s:s + chunk].contiguous()
-                ones = torch.ones(sx.shape[0], dtype=torch.uint8, device=self.device)
                 outs = []
                 for reassociated in (True, False):
                     self.set_gnn_factored(reassociated)
                     self.set_bp4_shared_lse(reassociated)
                     o = self.sandwich_decode(sx, sz, iters, weights_list, llr_const, factors=factors, cn_types=cn_types, return_llr=True)
-                    o["flag"] = self.flag_update(o["x_hat"], o["z_hat"], sx, sz, ones.clone()) != 0
+                    o["flag"] = self.flag_update(o["x_hat"], o["z_hat"], sx, sz, self._new((sx.shape[0],), torch.uint8).fill_(1)) != 0
                     o["first"] = self.bp4_decode(sx, sz, iters[0], cn_types[0], factors[0], llr_const=llr_const, want_logits=False)
                     outs.append(o)
                 a, b = outs
@@ -687,7 +686,7 @@ class TannerGraph:
         B = int(mask.shape[0])
         mask = self._chk(mask, (B,), torch.uint8, "mask")
         index = self._new((max(B, 1),), torch.int32)
-        count = torch.zeros(1, dtype=torch.int32, device=self.device)
+        count = self._new((1,), torch.int32).zero_()
         with torch.cuda.device(self.device):
             check(_lib.lib().fgnn_compact(_ptr(mask), int(bit), B, _ptr(index), _ptr(count), _stream(self.device)))
         return index, int(count.item())
@@ -758,7 +757,7 @@ class TannerGraph:
         check(_lib.lib().fgnn_osd_workspace_bytes(self.handle, int(side), osd_method_id(method), int(order), int(slots), C.byref(nbytes)))
         if out is not None and out.numel() >= nbytes.value:
             return out
-        return torch.empty(int(nbytes.value), dtype=torch.uint8, device=self.device)
+        return self._new((int(nbytes.value),), torch.uint8)
 
     def osd_ws(self, side, synd, e_hat, method, order, marg=None, llr_bin=None, index=None, nact=0, chosen=None, workspace=None):
         """`osd` (method "osd0": `osd0`) on a device workspace (`fgnn_osd_ws`): any basis with n <= 16384, the same outputs bit for
@@ -974,7 +973,7 @@ class TannerGraph:
         synd_z = self._chk(synd_z, (B, self.m_z), torch.uint8, "synd_z")
         nbytes = _lib.lib().fgnn_gnnbp4_weights_workspace_bytes(self.handle, weights.handle, B)
         if workspace is None:
-            workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            workspace = self._new((nbytes,), torch.uint8)
         xh = self._new((B, self.n), torch.uint8)
         zh = self._new((B, self.n), torch.uint8)
         llr = self._new((B, 3, self.n), torch.float32)
