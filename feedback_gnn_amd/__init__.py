@@ -43,6 +43,9 @@ def __getattr__(name):
     if name in ("AMBP4Decoder", "BP4_AMBP_Model"):
         from . import mbp as _mb
         return getattr(_mb, name)
+    if name in ("SoftSyndromeBP4Decoder", "BP4_SoftSyndrome_Model"):
+        from . import soft_syndrome as _ss
+        return getattr(_ss, name)
     if name in ("GNN_BP4", "MLP"):
         from . import gnn as _gn
         return getattr(_gn, name)

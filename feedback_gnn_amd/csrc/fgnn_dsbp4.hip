@@ -1,0 +1,353 @@
+// fgnn_dsbp4.hip — soft-syndrome BP4 (Kuo, Chern, Lai, "Decoding of quantum data-syndrome codes via belief propagation", 2021;
+// Raveendran et al., "Soft syndrome decoding of quantum LDPC codes for joint correction of data and syndrome errors", 2022), flooding
+// schedule, LDS-resident, with the attempt list of AMBP4 kept.  Check c carries a syndrome LLR gamma_c: the error u_c of its measured
+// bit is a degree-one variable on the check, so it is one more constant input of the check rule (fgnn_cn_soft.h), held in a register,
+// and the decoder returns u_hat next to the data error.  A sample is solved when H e_hat == s ^ u_hat on both graphs.  The algorithm is
+// stated to the float operation at fgnn_dsbp4_decode in include/fgnn.h.  The kernel is a sibling of mbp4_kernel (fgnn_mbp4.hip): the
+// same message layout, literal qubit update with own[a], factor[a], step / stop control, parity-by-stamp test and ndone exit.
+//
+// LDS of one codeword, in floats, each area rounded up to 4 floats:
+//   msg  [E_x + E_z]  c->v / v->c messages, bp4_kernel's layout
+//   dec  [n] bytes    decisions d_v = x_v | z_v << 1 of the last test
+//   uh   [m] bytes    bit 0: u_hat of the last check update, bit 1: the u_hat the last test used
+// and per workgroup tab[128], stamp[cpb] and ndone as in mbp4_kernel.
+//
+// u_hat.  A check's byte is written by the lane that updates the check, read by that same lane in the next step's parity test, and
+// read by the output loop, which walks the checks with the same lane assignment; no other thread touches it.  A step that tests and
+// then updates (0 < k < T) would overwrite the tested bit before the control phase can write it out, so the test moves it to bit 1.
+//
+// gamma_c is loop-invariant and the same lane owns check c in every step, so it stays out of LDS: the lane reads it again from global
+// memory in every check update, next to the check's row, which it also reads again.  Keeping a lane's values in registers instead
+// was measured on MI355X and gained nothing ("Soft syndromes"), and its registers cost a wave per SIMD.
+//
+// A step of an attempt with T check updates, k = 0 .. T counting the finished ones:
+//   qubits   as mbp4_kernel
+//   barrier
+//   checks   k > 0: parity of the decisions against s ^ u_hat (stamp);  k < T: soft check update * factor[r], u_hat = gamma + w < 0
+//   barrier
+//   control  solved / out of attempts: outputs, done;  k = T: the next attempt
+// No float atomics; no result depends on the order in which threads arrive.
+//
+// Registers.  Compiled for FGNN_DSBP4_WAVES waves per SIMD, the most at which no instantiation needs scratch (DESIGN.md section 4,
+// "Soft syndromes", lists what each instantiation takes).
+#include <climits>
+#include <cmath>
+
+#include "fgnn_internal.h"
+#include "fgnn_math.h"
+#include "fgnn_cn_soft.h"
+#include "fgnn_vn.h"
+
+#ifndef FGNN_DSBP4_WAVES
+#define FGNN_DSBP4_WAVES 7  // waves per SIMD the register allocation aims at
+#endif
+
+static_assert(FGNN_SOFT_BOXPLUS == FGNN_CN_BOXPLUS && FGNN_SOFT_BOXPLUS_PHI == FGNN_CN_BOXPLUS_PHI && FGNN_SOFT_MINSUM == FGNN_CN_MINSUM,
+              "fgnn_cn_soft.h restates the FGNN_CN_* values of include/fgnn.h");
+
+namespace {
+
+constexpr int DSBP4_MAX_ATTEMPTS = 64;
+
+struct DsArgs {
+    int B, pre_iter, attempt_iter, attempts, restart, max_steps, tpc, cpb, lds_per_cw, d_off, u_off;
+    float llr_const, gamma_x, gamma_z;
+    const float* llr_ch;      // [B,3,n] or null
+    const uint8_t* synd_x;    // [B,m_x] or null (all-zero syndrome)
+    const uint8_t* synd_z;    // [B,m_z] or null
+    const float* synd_llr_x;  // [B,m_x] or null (gamma_x for every hx check)
+    const float* synd_llr_z;  // [B,m_z] or null
+    uint8_t* x_hat;           // [B,n]
+    uint8_t* z_hat;           // [B,n]
+    uint8_t* u_x_hat;         // [B,m_x]
+    uint8_t* u_z_hat;         // [B,m_z]
+    int32_t* stats;           // [B,4]
+    float tab[2 * DSBP4_MAX_ATTEMPTS];  // factor[0..63], own[0..63]; entries from `attempts` on are 0 and never read
+};
+
+// gamma of check c of the workgroup's codeword cwl: the side's array, or its scalar.  gx0 / gz0 are the rows of the workgroup's first
+// codeword, the same for every lane, and the lane adds a 32-bit offset: no per-lane pointer lives through the qubit phase.
+__device__ __forceinline__ float gamma_at(const float* gx0, const float* gz0, float gamma_x, float gamma_z, int cwl, int m_x, int m_z, int c)
+{
+    const bool is_x = c < m_x;
+    const float* gl = is_x ? gx0 : gz0;
+    const unsigned o = is_x ? (unsigned)(cwl * m_x + c) : (unsigned)(cwl * m_z + (c - m_x));
+    return gl ? gl[o] : (is_x ? gamma_x : gamma_z);
+}
+
+// DV/DC > 0: (DV,DV,DC)-regular graphs with the packed slot rows of g.cslot16 (min-sum); DV = DC = 0: runtime degrees, the loop.
+template <int CN_TYPE, int DV, int DC>
+__global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_DSBP4_WAVES))) dsbp4_kernel(GraphDev g, DsArgs a)
+{
+    FG_LOG_TAB_SETUP();
+    constexpr bool REGULAR = DV > 0;
+    static_assert(!REGULAR || CN_TYPE == FGNN_CN_MINSUM, "the regular rows are compiled for min-sum");
+    extern __shared__ float lds[];
+    const int cwl = threadIdx.x / a.tpc;
+    const int lane = threadIdx.x - cwl * a.tpc;
+    const int b = blockIdx.x * a.cpb + cwl;
+    const bool active = b < a.B;
+    float* msg = lds + (size_t)cwl * a.lds_per_cw;
+    uint8_t* dec = reinterpret_cast<uint8_t*>(msg + a.d_off);
+    uint8_t* uh = reinterpret_cast<uint8_t*>(msg + a.u_off);
+    float* tab = lds + (size_t)a.cpb * a.lds_per_cw;
+    int* stamp = reinterpret_cast<int*>(tab + 2 * DSBP4_MAX_ATTEMPTS);
+    int* ndone = stamp + a.cpb;
+    const int n = g.n, m = g.m, tpc = a.tpc;
+    // inputs are addressed as the rows of the workgroup's first codeword, the same for every lane, plus a 32-bit offset per lane
+    // (a workgroup's codewords fit the LDS, so cpb * 3 n is small): no per-lane pointer lives through the kernel
+    const size_t b0 = (size_t)blockIdx.x * a.cpb;
+    const float* lch0 = a.llr_ch ? a.llr_ch + b0 * 3 * n : nullptr;
+    const uint8_t* sx0 = a.synd_x ? a.synd_x + b0 * g.m_x : nullptr;
+    const uint8_t* sz0 = a.synd_z ? a.synd_z + b0 * g.m_z : nullptr;
+    const float* gx0 = a.synd_llr_x ? a.synd_llr_x + b0 * g.m_x : nullptr;
+    const float* gz0 = a.synd_llr_z ? a.synd_llr_z + b0 * g.m_z : nullptr;
+    const unsigned lo = (unsigned)(cwl * 3 * n);
+    const int nact = min(a.cpb, a.B - (int)blockIdx.x * a.cpb);
+
+    auto synd_of = [&](const int c) __attribute__((always_inline)) -> unsigned {
+        const bool is_x = c < g.m_x;
+        const uint8_t* s = is_x ? sx0 : sz0;
+        const unsigned o = is_x ? (unsigned)(cwl * g.m_x + c) : (unsigned)(cwl * g.m_z + (c - g.m_x));
+        return s ? (s[o] & 1u) : 0u;
+    };
+    const float gamma_x = a.gamma_x, gamma_z = a.gamma_z;
+#define GAMMA_OF(c) gamma_at(gx0, gz0, gamma_x, gamma_z, cwl, g.m_x, g.m_z, (c))
+
+    for (int i = threadIdx.x; i < 2 * DSBP4_MAX_ATTEMPTS; i += blockDim.x) tab[i] = a.tab[i];
+    for (int i = threadIdx.x; i < a.cpb + 1; i += blockDim.x) stamp[i] = 0;  // stamp, ndone
+    if (active) {
+        for (int e = lane; e < g.E; e += a.tpc) msg[e] = 0.0f;
+        for (int v = lane; v < n; v += a.tpc) dec[v] = 0;
+        for (int c = lane; c < m; c += a.tpc) uh[c] = 0;
+    }
+    const int per_lane = (m + a.tpc - 1) / a.tpc;
+    const bool synd_in_reg = per_lane <= 32;
+    unsigned synd_bits = 0;
+    if (active && synd_in_reg) {
+        int i = 0;
+        for (int c = lane; c < m; c += a.tpc, ++i) synd_bits |= synd_of(c) << i;
+    }
+    __syncthreads();
+
+    int r = 0, k = 0, its = 0;  // r < a.attempts <= 64 throughout: the last attempt ends the codeword
+    bool done = !active;
+    for (int step = 1; step <= a.max_steps; ++step) {
+        const int T = (r == 0) ? a.pre_iter : a.attempt_iter;
+        // ---- qubits: marginals after k check updates and their decision, messages to the checks ----
+        if (!done) {
+            const bool zero = a.restart && k == 0 && r > 0;  // a restarting attempt starts from zero messages
+            const float ow = tab[DSBP4_MAX_ATTEMPTS + r];
+            for (int v = lane; v < n; v += a.tpc) {
+                const float lx = lch0 ? lch0[lo + (unsigned)v] : a.llr_const;
+                const float ly = lch0 ? lch0[lo + (unsigned)(n + v)] : a.llr_const;
+                const float lz = lch0 ? lch0[lo + (unsigned)(2 * n + v)] : a.llr_const;
+                const int x0 = REGULAR ? v * DV : g.vptr_x[v], z0 = REGULAR ? g.E_x + v * DV : g.vptr_z[v];
+                const int dx = REGULAR ? DV : g.vptr_x[v + 1] - x0, dz = REGULAR ? DV : g.vptr_z[v + 1] - z0;
+                float* px = msg + x0;
+                float* pz = msg + z0;
+                if (zero) {  // the slots of a qubit are its owner's in this phase
+                    for (int j = 0; j < dx; ++j) px[j] = 0.0f;
+                    for (int j = 0; j < dz; ++j) pz[j] = 0.0f;
+                }
+                float mx[REGULAR ? DV : 1], mz[REGULAR ? DV : 1];
+                float Sz = 0.0f, Sx = 0.0f;
+                if constexpr (REGULAR) {
+#pragma unroll
+                    for (int j = 0; j < DV; ++j) { mz[j] = pz[j]; Sz = Sz + mz[j]; }
+#pragma unroll
+                    for (int j = 0; j < DV; ++j) { mx[j] = px[j]; Sx = Sx + mx[j]; }
+                } else {
+                    vn_sums(msg, z0, z0 + dz, x0, x0 + dx, Sz, Sx);
+                }
+                float X, Y, Z;
+                vn_totals(Sz, Sx, lx, ly, lz, X, Y, Z);
+                if (k > 0) {  // the test's decision; an attempt's last test sends no messages
+                    dec[v] = (uint8_t)vn_decide(X, Y, Z);
+                    if (k == T) continue;
+                }
+                const float numx = VnMath::softplus(-X);
+                const float numz = VnMath::softplus(-Z);
+                if constexpr (REGULAR) {
+#pragma unroll
+                    for (int j = 0; j < DV; ++j) px[j] = vn_edge_own<VnMath>(numx, Z, Y, mx[j], ow);
+#pragma unroll
+                    for (int j = 0; j < DV; ++j) pz[j] = vn_edge_own<VnMath>(numz, X, Y, mz[j], ow);
+                } else {
+                    for (int j = 0; j < dx; ++j) px[j] = vn_edge_own<VnMath>(numx, Z, Y, px[j], ow);
+                    for (int j = 0; j < dz; ++j) pz[j] = vn_edge_own<VnMath>(numz, X, Y, pz[j], ow);
+                }
+            }
+        }
+        __syncthreads();
+        if (*ndone == nact) break;  // the same word for every thread, last written before the barrier above
+        // ---- checks of both graphs: parity of the decisions against s ^ u_hat (k > 0), then the soft check update (k < T) ----
+        if (!done) {
+            const float fac = tab[r];
+            // one check: c, its index i among the lane's checks, its syndrome LLR
+            auto one_check = [&](const int c, const int i, const float gm) __attribute__((always_inline)) {
+                const unsigned sy = synd_in_reg ? ((synd_bits >> i) & 1u) : synd_of(c);
+                const bool is_x = c < g.m_x;
+                const int sh = is_x ? 1 : 0;  // hx rows test z_hat (bit 1 of the decision), hz rows x_hat (bit 0)
+                const unsigned ut = (unsigned)uh[c] & 1u;  // u_hat of the check update before this step: this lane wrote it
+                unsigned un = ut;
+                bool odd = false;
+                if constexpr (REGULAR) {
+                    const uint4 pk = reinterpret_cast<const uint4*>(g.cslot16)[c];
+                    const unsigned w[4] = {pk.x, pk.y, pk.z, pk.w};
+                    unsigned off[DC];
+#pragma unroll
+                    for (int j = 0; j < DC; ++j) off[j] = (w[j >> 1] >> ((j & 1) * 16)) & 0xffffu;
+                    if (k > 0) {
+                        const unsigned base = is_x ? 0u : (unsigned)g.E_x;  // slot base + v * DV + j belongs to qubit v
+                        unsigned par = sy ^ ut;
+#pragma unroll
+                        for (int j = 0; j < DC; ++j) par ^= ((unsigned)dec[((off[j] >> 2) - base) / DV] >> sh) & 1u;
+                        odd = par != 0u;
+                    }
+                    if (k < T) un = soft_u_hat(gm, cn_soft_minsum_regular<DC>(msg, off, DC, sy, gm, fac));
+                } else {
+                    const int c0 = g.cptr[c], deg = g.cptr[c + 1] - c0;
+                    if (k > 0) {
+                        unsigned par = sy ^ ut;
+                        for (int j = 0; j < deg; ++j) par ^= ((unsigned)dec[g.cvn[c0 + j]] >> sh) & 1u;
+                        odd = par != 0u;
+                    }
+                    if (k < T) un = soft_u_hat(gm, cn_soft_update<CN_TYPE, PhiSoft>(msg, g.cslot + c0, deg, sy, gm, fac));
+                }
+                uh[c] = (uint8_t)(un | (ut << 1));
+                if (odd) stamp[cwl] = step;
+            };
+            int i = 0;
+            for (int c = lane; c < m; c += tpc, ++i) one_check(c, i, k < T ? GAMMA_OF(c) : 0.0f);
+        }
+        __syncthreads();
+        // ---- per codeword: solution found, attempt over, decoder finished ----
+        if (!done) {
+            if (k == 0) {
+                k = 1;
+                ++its;
+            } else {
+                const bool sat = stamp[cwl] != step;
+                if (sat || (k == T && r == a.attempts - 1)) {
+                    // the output rows are addressed from a laundered copy of b: formed here, once per codeword, instead of living in
+                    // per-lane 64-bit registers through every step
+                    int bo = b;
+                    asm volatile("" : "+v"(bo));
+                    const size_t ob = (size_t)bo;
+                    for (int v = lane; v < n; v += a.tpc) {
+                        const unsigned d = dec[v];
+                        a.x_hat[ob * n + v] = (uint8_t)(d & 1u);
+                        a.z_hat[ob * n + v] = (uint8_t)(d >> 1);
+                    }
+                    for (int c = lane; c < m; c += a.tpc) {  // the lane that wrote the byte
+                        const uint8_t u = (uint8_t)((uh[c] >> 1) & 1u);
+                        if (c < g.m_x) a.u_x_hat[ob * g.m_x + c] = u;
+                        else a.u_z_hat[ob * g.m_z + (c - g.m_x)] = u;
+                    }
+                    if (lane == 0) {
+                        int32_t* st = a.stats + ob * 4;
+                        st[0] = sat ? 1 : 0;
+                        st[1] = r;
+                        st[2] = its;
+                        st[3] = k;
+                        atomicAdd(ndone, 1);
+                    }
+                    done = true;
+                } else if (k == T) {
+                    ++r;
+                    k = 0;
+                } else {
+                    ++k;
+                    ++its;
+                }
+            }
+        }
+    }
+}
+
+#undef GAMMA_OF
+
+template <int CN_TYPE, int DV, int DC>
+int launch(const fgnn_graph* g, const DsArgs& a, const LaunchGeom& L, size_t lds_bytes, hipStream_t st)
+{
+    return fgnn_launch(dsbp4_kernel<CN_TYPE, DV, DC>, dim3(L.blocks), dim3(L.threads), lds_bytes, st, g->d, a);
+}
+
+}  // namespace
+
+extern "C" int fgnn_dsbp4_decode(const fgnn_graph* g, int cn_type, int num_attempts, const float* factor, const float* own, int pre_iter,
+                                 int attempt_iter, int restart, const float* llr_ch, float llr_const, const uint8_t* synd_x,
+                                 const uint8_t* synd_z, const float* synd_llr_x, float gamma_x, const float* synd_llr_z, float gamma_z,
+                                 int B, uint8_t* x_hat, uint8_t* z_hat, uint8_t* u_x_hat, uint8_t* u_z_hat, int32_t* stats, void* stream)
+{
+    if (!g) return fgnn_fail(FGNN_ERR_ARG, "graph is NULL");
+    if (g->host_only) return fgnn_fail(FGNN_ERR_ARG, "a host-only graph cannot decode");
+    if (cn_type < 0 || cn_type > 2) return fgnn_fail(FGNN_ERR_ARG, "Unknown node type.");  // decoding_q.py:107
+    if (B < 0) return fgnn_fail(FGNN_ERR_ARG, "B must be >= 0");
+    if (num_attempts < 1 || num_attempts > DSBP4_MAX_ATTEMPTS) return fgnn_fail(FGNN_ERR_ARG, "num_attempts must be in 1 .. 64");
+    if (pre_iter < 1 || attempt_iter < 1) return fgnn_fail(FGNN_ERR_ARG, "pre_iter and attempt_iter must be >= 1");
+    if (restart != 0 && restart != 1) return fgnn_fail(FGNN_ERR_ARG, "restart must be 0 or 1");
+    if (!factor || !own) return fgnn_fail(FGNN_ERR_ARG, "factor and own must hold num_attempts floats each");
+    for (int i = 0; i < num_attempts; ++i) {
+        if (!std::isfinite(factor[i]) || !(factor[i] > 0.0f)) return fgnn_fail(FGNN_ERR_ARG, "every factor must be finite and > 0");
+        if (!std::isfinite(own[i]) || own[i] < 0.0f) return fgnn_fail(FGNN_ERR_ARG, "every own weight must be finite and >= 0");
+    }
+    if (std::isnan(gamma_x) || std::isnan(gamma_z)) return fgnn_fail(FGNN_ERR_ARG, "gamma_x and gamma_z must not be NaN");
+    if (B == 0) return FGNN_OK;  // an empty batch needs no buffers
+    if (!x_hat || !z_hat || !u_x_hat || !u_z_hat || !stats) return fgnn_fail(FGNN_ERR_ARG, "no output buffer");
+    FGNN_DEVICE_GUARD(g->device);
+    LaunchGeom L = fgnn_geom(g, B);
+    DsArgs a;
+    a.B = B;
+    a.pre_iter = pre_iter;
+    a.attempt_iter = attempt_iter;
+    a.attempts = num_attempts;
+    a.restart = restart;
+    // a codeword takes T + 1 steps per attempt; one more step lets the workgroup see its last codeword finished
+    const long long steps = (long long)pre_iter + 1 + (long long)(num_attempts - 1) * ((long long)attempt_iter + 1) + 1;
+    a.max_steps = (int)std::min<long long>(steps, INT_MAX - 1);
+    a.tpc = L.tpc;
+    a.cpb = L.cpb;
+    a.llr_const = llr_const;
+    a.gamma_x = gamma_x;
+    a.gamma_z = gamma_z;
+    a.llr_ch = llr_ch;
+    a.synd_x = synd_x;
+    a.synd_z = synd_z;
+    a.synd_llr_x = synd_llr_x;
+    a.synd_llr_z = synd_llr_z;
+    a.x_hat = x_hat;
+    a.z_hat = z_hat;
+    a.u_x_hat = u_x_hat;
+    a.u_z_hat = u_z_hat;
+    a.stats = stats;
+    for (int i = 0; i < DSBP4_MAX_ATTEMPTS; ++i) {
+        a.tab[i] = i < num_attempts ? factor[i] : 0.0f;
+        a.tab[DSBP4_MAX_ATTEMPTS + i] = i < num_attempts ? own[i] : 0.0f;
+    }
+    // per codeword: E messages, n decision bytes and m u_hat bytes, each rounded up to 4 floats; per workgroup: the two 64-float tables,
+    // a stamp per codeword and ndone
+    const size_t dec_area = (((size_t)g->d.n + 3) / 4 + 3) & ~(size_t)3;
+    const size_t uh_area = (((size_t)g->d.m + 3) / 4 + 3) & ~(size_t)3;
+    const size_t d_off = ((size_t)g->d.E + 3) & ~(size_t)3;
+    const size_t u_off = d_off + dec_area;
+    const size_t per_cw = u_off + uh_area;
+    const size_t lds_bytes = per_cw * sizeof(float) * (size_t)L.cpb + (size_t)2 * DSBP4_MAX_ATTEMPTS * sizeof(float) +
+                             (((size_t)L.cpb + 1 + 3) & ~(size_t)3) * sizeof(int);
+    if (lds_bytes > FGNN_LDS_BUDGET)
+        return fgnn_fail(FGNN_ERR_ARG, "code too large for the LDS-resident soft-syndrome BP4 kernel: " + std::to_string(lds_bytes) +
+                                           " bytes of LDS per workgroup, the limit is " + std::to_string(FGNN_LDS_BUDGET));
+    a.d_off = (int)d_off;
+    a.u_off = (int)u_off;
+    a.lds_per_cw = (int)per_cw;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    switch (cn_type) {
+    case FGNN_CN_BOXPLUS: return launch<FGNN_CN_BOXPLUS, 0, 0>(g, a, L, lds_bytes, st);
+    case FGNN_CN_BOXPLUS_PHI: return launch<FGNN_CN_BOXPLUS_PHI, 0, 0>(g, a, L, lds_bytes, st);
+    default: break;
+    }
+    if (g->d.cslot16 && !g->force_generic && g->d.dvx == 3 && g->d.dvz == 3 && g->d.dc == 6)
+        return launch<FGNN_CN_MINSUM, 3, 6>(g, a, L, lds_bytes, st);
+    return launch<FGNN_CN_MINSUM, 0, 0>(g, a, L, lds_bytes, st);
+}

@@ -959,6 +959,67 @@ class TannerGraph:
                                           _ptr(synd_z), B, _ptr(xh), _ptr(zh), _ptr(stats), _stream(self.device)))
         return xh, zh, stats
 
+    def dsbp4_decode(self, synd_x, synd_z, factors, owns, pre_iter, attempt_iter, cn_type="minsum", restart=True, llr_ch=None,
+                     llr_const=0.0, synd_llr_x=None, synd_llr_z=None, gamma_x=float("inf"), gamma_z=float("inf"), B=None):
+        """Soft-syndrome BP4 on both graphs (`fgnn_dsbp4_decode`): `mbp4_decode` with a syndrome LLR per check and a joint stop test.
+        `synd_llr_x` [B, m_x] / `synd_llr_z` [B, m_z] (float32) say how far each measured bit can be trusted; None means the scalar
+        `gamma_x` / `gamma_z` for every check of that side (+inf, the default: a perfect measurement; NaN is refused).  The check rule
+        takes the LLR as one more input, the decoder estimates which syndrome bits were wrong, and a sample is solved when the data
+        estimate reproduces `synd ^ u_hat` on both graphs.  Every other argument is `mbp4_decode`'s.  Returns `(x_hat [B,n], z_hat
+        [B,n], u_x_hat [B,m_x], u_z_hat [B,m_z]` uint8, `stats [B,4]` int32 = found, the attempt of the last test, iterations, k of the
+        last test)`."""
+        if cn_type not in CN_TYPES:
+            raise ValueError("Unknown node type.")
+        factors = np.ascontiguousarray(np.asarray(factors, dtype=np.float32).reshape(-1))
+        owns = np.ascontiguousarray(np.asarray(owns, dtype=np.float32).reshape(-1))
+        if len(factors) != len(owns):
+            raise ValueError("factors and owns must have the same length")
+        for s in (synd_x, synd_z, llr_ch, synd_llr_x, synd_llr_z):
+            if s is not None:
+                B = int(s.shape[0])
+        if B is None:
+            raise ValueError("B is needed when neither syndromes nor llr_ch nor syndrome LLRs are given")
+        if synd_x is not None:
+            synd_x = self._chk(synd_x, (B, self.m_x), torch.uint8, "synd_x")
+        if synd_z is not None:
+            synd_z = self._chk(synd_z, (B, self.m_z), torch.uint8, "synd_z")
+        if llr_ch is not None:
+            llr_ch = self._chk(llr_ch, (B, 3, self.n), torch.float32, "llr_ch")
+        if synd_llr_x is not None:
+            synd_llr_x = self._chk(synd_llr_x, (B, self.m_x), torch.float32, "synd_llr_x")
+        if synd_llr_z is not None:
+            synd_llr_z = self._chk(synd_llr_z, (B, self.m_z), torch.float32, "synd_llr_z")
+        xh = self._new((B, self.n), torch.uint8)
+        zh = self._new((B, self.n), torch.uint8)
+        uxh = self._new((B, self.m_x), torch.uint8)
+        uzh = self._new((B, self.m_z), torch.uint8)
+        stats = self._new((B, 4), torch.int32)
+        check(_lib.lib().fgnn_dsbp4_decode(self.handle, CN_TYPES[cn_type], len(factors), factors.ctypes.data, owns.ctypes.data,
+                                           int(pre_iter), int(attempt_iter), int(restart), _ptr(llr_ch), float(llr_const), _ptr(synd_x),
+                                           _ptr(synd_z), _ptr(synd_llr_x), float(gamma_x), _ptr(synd_llr_z), float(gamma_z), B, _ptr(xh),
+                                           _ptr(zh), _ptr(uxh), _ptr(uzh), _ptr(stats), _stream(self.device)))
+        return xh, zh, uxh, uzh, stats
+
+    @staticmethod
+    def syndrome_noise_seeds(seed):
+        """The two stream seeds of `syndrome_noise`: ``(seed + 0x9E3779B97F4A7C15) mod 2^64`` for the hx checks and ``(seed + 2 *
+        0x9E3779B97F4A7C15) mod 2^64`` for the hz checks."""
+        step, mask = 0x9E3779B97F4A7C15, (1 << 64) - 1
+        return (int(seed) + step) & mask, (int(seed) + 2 * step) & mask
+
+    def syndrome_noise(self, seed, q, first_sample, B):
+        """Measurement flips `(u_x [B, m_x], u_z [B, m_z])` uint8, each bit 1 with probability `q`: two calls of `fgnn_bsc_noise`, of
+        width m_x on the seed ``(seed + 0x9E3779B97F4A7C15) mod 2^64`` and of width m_z on ``(seed + 2 * 0x9E3779B97F4A7C15) mod 2^64``
+        (`syndrome_noise_seeds`), so that neither stream is the one `pauli_noise` or `bsc_noise` draws from `seed` itself.  The streams
+        are indexed by global sample: rows `first_sample .. first_sample + B - 1` are what one process drawing all samples would get."""
+        out = []
+        with torch.cuda.device(self.device):
+            for s, width in zip(self.syndrome_noise_seeds(seed), (self.m_x, self.m_z)):
+                u = self._new((B, width), torch.uint8)
+                check(_lib.lib().fgnn_bsc_noise(s, float(np.float32(q)), int(first_sample), B, width, _ptr(u), _stream(self.device)))
+                out.append(u)
+        return out[0], out[1]
+
     def bsc_noise(self, seed, p, first_sample, B):
         e = self._new((B, self.n), torch.uint8)
         with torch.cuda.device(self.device):

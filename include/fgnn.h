@@ -430,6 +430,44 @@ int fgnn_bp4fb_decode(const fgnn_graph* g, int rule, int cn_type, float normaliz
 int fgnn_mbp4_decode(const fgnn_graph* g, int cn_type, int num_attempts, const float* factor, const float* own, int pre_iter,
                      int attempt_iter, int restart, const float* llr_ch, float llr_const, const uint8_t* synd_x, const uint8_t* synd_z,
                      int B, uint8_t* x_hat, uint8_t* z_hat, int32_t* stats, void* stream);
+/* Soft-syndrome BP4: data and syndrome errors decoded together (Kuo, Chern, Lai, "Decoding of quantum data-syndrome codes via belief
+ * propagation", 2021; Raveendran et al., "Soft syndrome decoding of quantum LDPC codes for joint correction of data and syndrome
+ * errors", 2022; Berent et al., "Analog information decoding of bosonic quantum LDPC codes", 2023), flooding schedule, with the attempt
+ * list of fgnn_mbp4_decode kept.  Check c carries a log-likelihood ratio gamma_c that says how far its measured bit s_c can be trusted:
+ * the bit's error u_c is a degree-one variable on that check, and the decoder returns u_hat, its estimate of which syndrome bits were
+ * wrong, next to the data error.  In real numbers this is hard-syndrome BP4 on the data-syndrome code [H | I]; here the extra
+ * variable is one more constant input of the check rule.  One attempt with own = 1 is plain soft-syndrome flooding BP4; a descending
+ * alpha list (own[a] = alpha_a, factor[a] = base / alpha_a) is Kuo, Chern and Lai's MBP4 on the data-syndrome code.
+ * synd_llr_x [B,m_x] / synd_llr_z [B,m_z] hold gamma per check; NULL means the scalar gamma_x / gamma_z for every check of that side.
+ * Everything not mentioned here is fgnn_mbp4_decode to the float operation: message layout, the literal qubit update with own[a],
+ * factor[a], pre_iter / attempt_iter / restart, iteration counting, the four stats columns and B = 0.  Two things differ.
+ * 1. Soft check rule.  A check has d edges with inputs nu_1 .. nu_d in ascending qubit order, syndrome bit s and syndrome LLR gamma.
+ *    The rule of that cn_type is evaluated on the d + 1 inputs (nu_1, .., nu_d, gamma), in that order, with the same float operations.
+ *    Outputs 1 .. d, times factor[a], are the new c->v messages.  Output d + 1, times factor[a], is w_c; it is stored nowhere in the
+ *    message array.  Per rule, including the orders that matter for bits:
+ *      boxplus-phi: a_gamma = phi(|gamma|);  T = ((a_1 + ..) + a_d) + a_gamma;  the sign of gamma enters neg like any input's sign;
+ *                   w_c = with_sign(phi(T - a_gamma), neg ^ (gamma < 0)) * factor.
+ *      minsum:      gamma is clipped to +-20 like the rest;  minv, min2 and nsum run over all d + 1 values in order;  w_c takes min_e
+ *                   or minv by the same d == 0 test.
+ *      boxplus:     t_gamma = tanh(gamma / 2), with 0 -> 1e-12;  P = (..(t_1 * t_2) .. * t_d) * t_gamma, then the syndrome sign;
+ *                   w_c = (2 * atanh(clip(rcp(t_gamma) * P))) * factor, with the same small-magnitude flush and clip.
+ *    Then, for every check and rule:  Gamma_c = gamma_c + w_c (one add);  u_hat_c = Gamma_c < 0.
+ *    gamma = +inf is a legal value and means a perfect measurement: no rule forms a NaN from it, and u_hat_c is then 0.  Negative values
+ *    are legal and mean what the rule makes of them.  NaN is unspecified.
+ * 2. Joint test.  It runs after check update k, on the decisions BP4's rule forms from the new messages.  A sample is solved iff, for
+ *    every hx row c, parity(z_hat over c) ^ s_c ^ u_hat_c == 0, and for every hz row c, parity(x_hat over c) ^ s_c ^ u_hat_c == 0, with
+ *    u_hat that of check update k.
+ * x_hat, z_hat [B,n] and u_x_hat [B,m_x], u_z_hat [B,m_z] = those of the last test made; stats [B,4] as fgnn_mbp4_decode.  A scalar
+ * gamma_x or gamma_z that is NaN is FGNN_ERR_ARG; argument checks otherwise as fgnn_mbp4_decode.  With min-sum and gamma = +inf on every
+ * check of degree >= 2 the clipped extra input is 20, which no clipped edge exceeds, and Gamma = +inf: x_hat, z_hat and stats are those
+ * of fgnn_mbp4_decode bit for bit, and u_hat is zero.  The messages, decisions and one u_hat byte per check of a codeword stay in LDS for
+ * the whole launch, next to the two 64-float tables; a graph they do not fit is refused (FGNN_ERR_ARG), there is no global-memory
+ * variant. */
+int fgnn_dsbp4_decode(const fgnn_graph* g, int cn_type, int num_attempts, const float* factor, const float* own, int pre_iter,
+                      int attempt_iter, int restart, const float* llr_ch, float llr_const, const uint8_t* synd_x, const uint8_t* synd_z,
+                      const float* synd_llr_x /* [B,m_x] or NULL */, float gamma_x, const float* synd_llr_z /* [B,m_z] or NULL */,
+                      float gamma_z, int B, uint8_t* x_hat, uint8_t* z_hat, uint8_t* u_x_hat /* [B,m_x] */, uint8_t* u_z_hat /* [B,m_z] */,
+                      int32_t* stats /* [B,4] */, void* stream);
 /* Layers of the serial (layered) check schedule.  Checks are numbered 0..m_x-1 for hx and m_x..m_x+m_z-1 for hz; a layering is
  * layer_of[m_x+m_z] with values in [0, num_layers) such that every layer is non-empty and no two checks of a layer share a qubit —
  * across hx and hz too, since a qubit's update reads the messages of both sides.  All pointers are host pointers; fgnn_greedy_layers and
