@@ -62,11 +62,6 @@ struct LayArgs {
     float* msg_out_z;
 };
 
-// the phi of BP4's check rule and soft syndromes (decoding_q.py:365-373): what bp4_kernel's exact policy evaluates
-struct PhiBp4 {
-    static __device__ __forceinline__ float phi(float x) { return fg_phi(x); }
-};
-
 template <int CN_TYPE>
 __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_LAYERED_WAVES))) bp4_layered_kernel(GraphDev g, LayArgs a)
 {

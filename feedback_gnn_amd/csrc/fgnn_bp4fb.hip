@@ -4,9 +4,10 @@
 //                     unsatisfied check gets three seeded random reductions of its LLRs;
 //   FGNN_FB_ENHANCED  enhanced feedback (Wang, Sanders, Poulin, "Enhanced feedback iterative decoding of sparse quantum codes", 2012):
 //                     one qubit of one unsatisfied check gets the two Paulis that anticommute with the check made likelier or less likely.
-// The algorithm is stated to the float operation at fgnn_bp4fb_decode in include/fgnn.h.  The kernel is bp4gd_kernel (fgnn_bp4gd.hip)
-// with its `fix` bytes turned into `mark` bytes: the same message layout, literal qubit update (fgnn_vn.h), shared check rule
-// (fgnn_cn.h), step / stop control, parity-by-stamp test and ndone exit.  lamhat is never stored: the thread that owns a qubit re-reads
+// The algorithm is stated to the float operation at fgnn_bp4fb_decode in include/fgnn.h.  The kernel stands on the frame of the
+// step-loop decoders (fgnn_step.h): codeword rows, staged syndrome bits, a qubit's slots with the literal edge rule (fgnn_vn.h), a
+// check's row and parity, the output write; the check rule is the shared one (fgnn_cn.h).  Its own are the attempt walk below, the
+// `mark` bytes, the keys and the Philox draws.  lamhat is never stored: the thread that owns a qubit re-reads
 // the channel LLRs from global memory (L2) and, for a marked qubit only, re-derives the change, for PERTURB from one Philox block
 // (fgnn_rng.h, integer instructions only).  Feedback never accumulates: every attempt's lamhat is the channel LLRs plus one change.
 //
@@ -38,14 +39,11 @@
 //
 // Registers.  Compiled for FGNN_BP4FB_WAVES waves per SIMD, the most at which no instantiation needs scratch (DESIGN.md section 4,
 // "Prior feedback", lists what each instantiation takes).
-#include <climits>
 #include <cmath>
 
-#include "fgnn_internal.h"
-#include "fgnn_math.h"
+#include "fgnn_step.h"
 #include "fgnn_rng.h"
 #include "fgnn_cn.h"
-#include "fgnn_vn.h"
 
 #ifndef FGNN_BP4FB_WAVES
 #define FGNN_BP4FB_WAVES 6  // waves per SIMD the register allocation aims at
@@ -56,22 +54,11 @@ namespace {
 constexpr int FB_MARK_PERTURB = 5;
 constexpr uint32_t FB_STREAM_PERTURB = 3, FB_STREAM_ENHANCED = 4;  // streams 0-2 of fgnn_rng.h keep the fourth counter word below 256
 
-struct FbArgs {
-    int B, rule, pre_iter, attempt_iter, attempts, restart, max_steps, tpc, cpb, lds_per_cw, d_off, m_off;
-    float factor, llr_const, strength;
+struct FbArgs : StepArgs {
+    int rule, pre_iter, attempt_iter, attempts, restart, m_off;
+    float factor, strength;
     uint32_t seed_lo, seed_hi;
     uint64_t first_sample;
-    const float* llr_ch;     // [B,3,n] or null
-    const uint8_t* synd_x;   // [B,m_x] or null (all-zero syndrome)
-    const uint8_t* synd_z;   // [B,m_z] or null
-    uint8_t* x_hat;          // [B,n]
-    uint8_t* z_hat;          // [B,n]
-    int32_t* stats;          // [B,4]
-};
-
-// the phi of BP4's check rule (decoding_q.py:365-373): what bp4_kernel's exact policy evaluates
-struct PhiBp4 {
-    static __device__ __forceinline__ float phi(float x) { return fg_phi(x); }
 };
 
 // lamhat of a marked qubit from its channel LLRs (order X, Y, Z).  f = 5: lam - F * u, one product, then one subtraction, per LLR;
@@ -100,10 +87,9 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_
     constexpr bool REGULAR = DV > 0;
     static_assert(!REGULAR || CN_TYPE == FGNN_CN_MINSUM, "the regular rows are compiled for min-sum");
     extern __shared__ float lds[];
-    const int cwl = threadIdx.x / a.tpc;
-    const int lane = threadIdx.x - cwl * a.tpc;
-    const int b = blockIdx.x * a.cpb + cwl;
-    const bool active = b < a.B;
+    const StepCw cw(a);
+    const int cwl = cw.cwl, lane = cw.lane;
+    const StepRows rows(g, a, cw);
     float* msg = lds + (size_t)cwl * a.lds_per_cw;
     uint8_t* dec = reinterpret_cast<uint8_t*>(msg + a.d_off);
     uint8_t* mark = reinterpret_cast<uint8_t*>(msg + a.m_off);
@@ -111,41 +97,27 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_
     int* stamp = reinterpret_cast<int*>(key + 2 * a.cpb);
     int* ndone = stamp + a.cpb;
     const int n = g.n, m = g.m;
-    const size_t bb = active ? (size_t)b : 0;
-    const float* lch = a.llr_ch ? a.llr_ch + bb * 3 * n : nullptr;
-    const uint8_t* sx = a.synd_x ? a.synd_x + bb * g.m_x : nullptr;
-    const uint8_t* sz = a.synd_z ? a.synd_z + bb * g.m_z : nullptr;
-    const int nact = min(a.cpb, a.B - (int)blockIdx.x * a.cpb);
-    const uint64_t sample = a.first_sample + (uint64_t)bb;
+    const uint64_t sample = a.first_sample + (uint64_t)rows.bb;
     const uint32_t s_lo = (uint32_t)sample, s_hi = (uint32_t)(sample >> 32);
 
-    auto synd_of = [&](const int c) __attribute__((always_inline)) -> unsigned {
-        const uint8_t* s = c < g.m_x ? sx : sz;
-        return s ? (s[c < g.m_x ? c : c - g.m_x] & 1u) : 0u;
-    };
     // w(idx, att, s) of include/fgnn.h
     auto draw = [&](const uint32_t idx, const int att, const uint32_t stream, uint32_t w[4]) __attribute__((always_inline)) {
         fg_philox4x32_10(s_lo, s_hi, idx, ((uint32_t)att << 8) | stream, a.seed_lo, a.seed_hi, w);
     };
 
     for (int i = threadIdx.x; i < 5 * a.cpb + 1; i += blockDim.x) stamp[i - 4 * a.cpb] = 0;  // key words, stamp, ndone
-    if (active) {
+    if (cw.active) {
         for (int e = lane; e < g.E; e += a.tpc) msg[e] = 0.0f;
         for (int v = lane; v < n; v += a.tpc) {
             dec[v] = 0;
             mark[v] = 0;
         }
     }
-    const bool synd_in_reg = (m + a.tpc - 1) / a.tpc <= 32;
-    unsigned synd_bits = 0;
-    if (active && synd_in_reg) {
-        int i = 0;
-        for (int c = lane; c < m; c += a.tpc, ++i) synd_bits |= synd_of(c) << i;
-    }
+    const StepSynd synd(g, rows, cw, a.tpc);
     __syncthreads();
 
     int r = 0, k = 0, its = 0;
-    bool done = !active;
+    bool done = !cw.active;
     for (int step = 1; step <= a.max_steps; ++step) {
         const int T = (r == 0) ? a.pre_iter : a.attempt_iter;
         const bool post = k == T && r < a.attempts;  // this step's test may be followed by a feedback step
@@ -154,34 +126,17 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_
             const bool zero = a.restart && k == 0 && r > 0;  // a restarting attempt starts from zero messages
             for (int v = lane; v < n; v += a.tpc) {
                 const int f = mark[v];
-                float lx = lch ? lch[v] : a.llr_const;
-                float ly = lch ? lch[n + v] : a.llr_const;
-                float lz = lch ? lch[2 * n + v] : a.llr_const;
+                float lx, ly, lz;
+                rows.llrs(n, v, a.llr_const, lx, ly, lz);
                 if (f) {
                     uint32_t w[4] = {0u, 0u, 0u, 0u};
                     if (f == FB_MARK_PERTURB) draw((uint32_t)v, r, FB_STREAM_PERTURB, w);
                     fb_lamhat(f, a.strength, w, lx, ly, lz);
                 }
-                // the qubit's c->v messages (zeros before the first check update) and their sums: only this fetch and the store
-                // below differ between the regular rows, which keep the messages in registers, and the runtime degrees
-                const int x0 = REGULAR ? v * DV : g.vptr_x[v], z0 = REGULAR ? g.E_x + v * DV : g.vptr_z[v];
-                const int dx = REGULAR ? DV : g.vptr_x[v + 1] - x0, dz = REGULAR ? DV : g.vptr_z[v + 1] - z0;
-                float* px = msg + x0;
-                float* pz = msg + z0;
-                if (zero) {  // the slots of a qubit are its owner's in this phase
-                    for (int j = 0; j < dx; ++j) px[j] = 0.0f;
-                    for (int j = 0; j < dz; ++j) pz[j] = 0.0f;
-                }
-                float mx[REGULAR ? DV : 1], mz[REGULAR ? DV : 1];
-                float Sz = 0.0f, Sx = 0.0f;
-                if constexpr (REGULAR) {
-#pragma unroll
-                    for (int j = 0; j < DV; ++j) { mz[j] = pz[j]; Sz = Sz + mz[j]; }
-#pragma unroll
-                    for (int j = 0; j < DV; ++j) { mx[j] = px[j]; Sx = Sx + mx[j]; }
-                } else {
-                    vn_sums(msg, z0, z0 + dz, x0, x0 + dx, Sz, Sx);
-                }
+                QubitSlots<DV> q(g, msg, v);
+                if (zero) q.clear();
+                float Sz, Sx;
+                q.fetch(Sz, Sx);
                 float X, Y, Z;
                 vn_totals(Sz, Sx, lx, ly, lz, X, Y, Z);
                 if (k > 0) {  // the test's decision; after an attempt's last test the mark has served
@@ -191,53 +146,33 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_
                         continue;
                     }
                 }
-                const float numx = VnMath::softplus(-X);
-                const float numz = VnMath::softplus(-Z);
-                if constexpr (REGULAR) {
-#pragma unroll
-                    for (int j = 0; j < DV; ++j) px[j] = vn_edge<VnMath>(numx, Z, Y, mx[j]);
-#pragma unroll
-                    for (int j = 0; j < DV; ++j) pz[j] = vn_edge<VnMath>(numz, X, Y, mz[j]);
-                } else {
-                    for (int j = 0; j < dx; ++j) px[j] = vn_edge<VnMath>(numx, Z, Y, px[j]);
-                    for (int j = 0; j < dz; ++j) pz[j] = vn_edge<VnMath>(numz, X, Y, pz[j]);
-                }
+                q.store(X, Y, Z, vn_edge<VnMath>);
             }
         }
         __syncthreads();
-        if (*ndone == nact) break;  // the same word for every thread, last written before the barrier above
+        if (*ndone == cw.nact) break;  // the same word for every thread, last written before the barrier above
         // ---- checks of both graphs: parity of the decisions (k > 0) and what an unsatisfied check feeds back, then the check update (k < T) ----
         if (!done) {
             int i = 0;
             for (int c = lane; c < m; c += a.tpc, ++i) {
-                const unsigned sy = synd_in_reg ? ((synd_bits >> i) & 1u) : synd_of(c);
+                const unsigned sy = synd.at(g, rows, i, c);
                 const bool is_x = c < g.m_x;
-                const int sh = is_x ? 1 : 0;  // hx rows test z_hat (bit 1 of the decision), hz rows x_hat (bit 0)
                 bool odd = false;
                 if constexpr (REGULAR) {
-                    const uint4 pk = reinterpret_cast<const uint4*>(g.cslot16)[c];
-                    const unsigned w[4] = {pk.x, pk.y, pk.z, pk.w};
                     unsigned off[DC];
-#pragma unroll
-                    for (int j = 0; j < DC; ++j) off[j] = (w[j >> 1] >> ((j & 1) * 16)) & 0xffffu;
+                    row_unpack(g, c, off);
                     if (k > 0) {
-                        const unsigned base = is_x ? 0u : (unsigned)g.E_x;  // slot base + v * DV + j belongs to qubit v
-                        unsigned par = sy;
-#pragma unroll
-                        for (int j = 0; j < DC; ++j) par ^= ((unsigned)dec[((off[j] >> 2) - base) / DV] >> sh) & 1u;
-                        odd = par != 0u;
+                        odd = parity_regular<DV>(g, dec, off, is_x, sy) != 0u;
                         if (odd && post && a.rule == FGNN_FB_PERTURB) {
 #pragma unroll
-                            for (int j = 0; j < DC; ++j) mark[((off[j] >> 2) - base) / DV] = (uint8_t)FB_MARK_PERTURB;
+                            for (int j = 0; j < DC; ++j) mark[row_qubit<DV>(off[j], row_base(g, is_x))] = (uint8_t)FB_MARK_PERTURB;
                         }
                     }
                     if (k < T) cn_minsum_regular<DC>(msg, off, DC, sy, a.factor);
                 } else {
                     const int c0 = g.cptr[c], deg = g.cptr[c + 1] - c0;
                     if (k > 0) {
-                        unsigned par = sy;
-                        for (int j = 0; j < deg; ++j) par ^= ((unsigned)dec[g.cvn[c0 + j]] >> sh) & 1u;
-                        odd = par != 0u;
+                        odd = parity_csr(g, dec, c0, deg, is_x, sy) != 0u;
                         if (odd && post && a.rule == FGNN_FB_PERTURB)
                             for (int j = 0; j < deg; ++j) mark[g.cvn[c0 + j]] = (uint8_t)FB_MARK_PERTURB;
                     }
@@ -262,19 +197,8 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_
             } else {
                 const bool sat = stamp[cwl] != step;
                 if (sat || (k == T && r == a.attempts)) {
-                    for (int v = lane; v < n; v += a.tpc) {
-                        const unsigned d = dec[v];
-                        a.x_hat[bb * n + v] = (uint8_t)(d & 1u);
-                        a.z_hat[bb * n + v] = (uint8_t)(d >> 1);
-                    }
-                    if (lane == 0) {
-                        int32_t* st = a.stats + (size_t)b * 4;
-                        st[0] = sat ? 1 : 0;
-                        st[1] = r;
-                        st[2] = its;
-                        st[3] = k;
-                        atomicAdd(ndone, 1);
-                    }
+                    step_write_decisions(a, dec, rows.bb, n, lane);
+                    if (lane == 0) step_finish(a, (size_t)cw.b, sat, r, its, k, ndone);
                     done = true;
                 } else if (k == T) {
                     if (a.rule == FGNN_FB_ENHANCED) {
@@ -285,7 +209,7 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_
                             uint32_t w[4];
                             draw(cs, r + 1, FB_STREAM_ENHANCED, w);
                             const int vs = g.cvn[c0 + fg_fy_pick(fg_u32_to_unit(w[1]), deg)];  // a check's qubits ascend
-                            if (vs % a.tpc == lane) mark[vs] = (uint8_t)(1u + ((int)cs < g.m_x ? 0u : 2u) + synd_of((int)cs));
+                            if (vs % a.tpc == lane) mark[vs] = (uint8_t)(1u + ((int)cs < g.m_x ? 0u : 2u) + rows.synd_of(g, (int)cs));
                         }
                         if (lane == 0) key[2 * cwl + ((r + 1) & 1)] = 0ull;  // read an attempt ago, posted to an attempt from now
                     }
@@ -298,12 +222,6 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_
             }
         }
     }
-}
-
-template <int CN_TYPE, int DV, int DC>
-int launch(const fgnn_graph* g, const FbArgs& a, const LaunchGeom& L, size_t lds_bytes, hipStream_t st)
-{
-    return fgnn_launch(bp4fb_kernel<CN_TYPE, DV, DC>, dim3(L.blocks), dim3(L.threads), lds_bytes, st, g->d, a);
 }
 
 }  // namespace
@@ -325,51 +243,28 @@ extern "C" int fgnn_bp4fb_decode(const fgnn_graph* g, int rule, int cn_type, flo
     if (B == 0) return FGNN_OK;  // an empty batch needs no buffers
     if (!x_hat || !z_hat || !stats) return fgnn_fail(FGNN_ERR_ARG, "no output buffer");
     FGNN_DEVICE_GUARD(g->device);
-    LaunchGeom L = fgnn_geom(g, B);
+    const LaunchGeom L = fgnn_geom(g, B);
     FbArgs a;
-    a.B = B;
+    step_args_fill(a, L, B, pre_iter, max_attempts, attempt_iter, llr_ch, llr_const, synd_x, synd_z, x_hat, z_hat, stats);
     a.rule = rule;
     a.pre_iter = pre_iter;
     a.attempt_iter = attempt_iter;
     a.attempts = max_attempts;
     a.restart = restart;
-    // a codeword takes T + 1 steps per attempt; one more step lets the workgroup see its last codeword finished
-    const long long steps = (long long)pre_iter + 1 + (long long)max_attempts * ((long long)attempt_iter + 1) + 1;
-    a.max_steps = (int)std::min<long long>(steps, INT_MAX - 1);
-    a.tpc = L.tpc;
-    a.cpb = L.cpb;
     a.factor = normalization_factor;
-    a.llr_const = llr_const;
     a.strength = strength;
     a.seed_lo = (uint32_t)seed;
     a.seed_hi = (uint32_t)(seed >> 32);
     a.first_sample = first_sample;
-    a.llr_ch = llr_ch;
-    a.synd_x = synd_x;
-    a.synd_z = synd_z;
-    a.x_hat = x_hat;
-    a.z_hat = z_hat;
-    a.stats = stats;
-    // per codeword: E messages, n decision bytes and n mark bytes, each rounded up to 4 floats; per workgroup: two 64-bit keys and a
-    // stamp per codeword, ndone: the byte count of fgnn_bp4gd_decode
-    const size_t bytes_area = (((size_t)g->d.n + 3) / 4 + 3) & ~(size_t)3;
-    const size_t d_off = ((size_t)g->d.E + 3) & ~(size_t)3;
-    const size_t m_off = d_off + bytes_area;
-    const size_t per_cw = m_off + bytes_area;
-    const size_t lds_bytes = per_cw * sizeof(float) * (size_t)L.cpb + (((size_t)5 * L.cpb + 1 + 3) & ~(size_t)3) * sizeof(int);
-    if (lds_bytes > FGNN_LDS_BUDGET)
-        return fgnn_fail(FGNN_ERR_ARG, "code too large for the LDS-resident BP4 feedback kernel: " + std::to_string(lds_bytes) +
-                                           " bytes of LDS per workgroup, the limit is " + std::to_string(FGNN_LDS_BUDGET));
+    // per codeword: E messages, n decision bytes and n mark bytes; per workgroup: two 64-bit keys and a stamp per codeword, ndone:
+    // the byte count of fgnn_bp4gd_decode
+    const size_t d_off = lds_round4(g->d.E), m_off = d_off + lds_bytes_as_floats(g->d.n);
+    size_t lds_bytes;
+    if (int err = step_lds_bytes(a, "BP4 feedback", m_off + lds_bytes_as_floats(g->d.n), 0, 5 * L.cpb + 1, &lds_bytes)) return err;
     a.d_off = (int)d_off;
     a.m_off = (int)m_off;
-    a.lds_per_cw = (int)per_cw;
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    switch (cn_type) {
-    case FGNN_CN_BOXPLUS: return launch<FGNN_CN_BOXPLUS, 0, 0>(g, a, L, lds_bytes, st);
-    case FGNN_CN_BOXPLUS_PHI: return launch<FGNN_CN_BOXPLUS_PHI, 0, 0>(g, a, L, lds_bytes, st);
-    default: break;
-    }
-    if (g->d.cslot16 && !g->force_generic && g->d.dvx == 3 && g->d.dvz == 3 && g->d.dc == 6)
-        return launch<FGNN_CN_MINSUM, 3, 6>(g, a, L, lds_bytes, st);
-    return launch<FGNN_CN_MINSUM, 0, 0>(g, a, L, lds_bytes, st);
+    return step_dispatch(g, cn_type, [&](auto cn, auto dv, auto dc) {
+        return fgnn_launch(bp4fb_kernel<decltype(cn)::value, decltype(dv)::value, decltype(dc)::value>, dim3(L.blocks), dim3(L.threads),
+                           lds_bytes, static_cast<hipStream_t>(stream), g->d, a);
+    });
 }

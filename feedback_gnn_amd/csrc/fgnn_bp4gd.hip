@@ -3,10 +3,12 @@
 //
 // Yao, Abu Laban, Haeger, Amat, Pfister, "Belief propagation decoding of quantum LDPC codes with guided decimation" (2023), quaternary
 // variant, in the form include/fgnn.h states at fgnn_bp4gd_decode.  The qubit update is the literal form of fgnn_vn.h (one log-sum-exp
-// per edge, fgnn_math.h) with the decimated LLRs lamhat in place of the channel LLRs, the check update is the shared rule of fgnn_cn.h,
-// the step / stop control is relay4_kernel's (fgnn_relay4.hip).  No saturation shortcuts, no register-resident channel LLRs, no
-// hardware transcendentals: the channel LLRs are re-read from global memory (L2) by the thread that owns the qubit and overridden
-// where the qubit is fixed; every float operation is the one bp4_kernel and cn_update execute, in their order.
+// per edge, fgnn_math.h) with the decimated LLRs lamhat in place of the channel LLRs, the check update is the shared rule of fgnn_cn.h.
+// The kernel stands on the frame of the step-loop decoders (fgnn_step.h): codeword rows, staged syndrome bits, a qubit's slots, a
+// check's row and parity, the output write; its own are the round walk below, the `fix` bytes and the bids.  No saturation shortcuts,
+// no register-resident channel LLRs, no hardware transcendentals: the channel LLRs are re-read from global memory (L2) by the thread
+// that owns the qubit and overridden where the qubit is fixed; every float operation is the one bp4_kernel and cn_update execute, in
+// their order.
 //
 // LDS of one codeword, in floats, each area rounded up to 4 floats (bp4gd_lds_bytes in tests/test_gpu_bp4gd.py mirrors it):
 //   msg [E_x + E_z]  c->v / v->c messages, slot e in [0,E_x) = hx edges, [E_x,E) = hz edges, sorted by (qubit, check): bp4_kernel's layout
@@ -39,12 +41,8 @@
 // of 72 VGPRs, at which three of the four instantiations spill to scratch; at six (a budget of 80 VGPRs) none does.  The kernels are
 // therefore compiled for 6 waves per SIMD: the registers, not the LDS, hold [[882,24]] to six workgroups per CU.  DESIGN.md section 4
 // lists what each instantiation takes.
-#include <climits>
-
-#include "fgnn_internal.h"
-#include "fgnn_math.h"
+#include "fgnn_step.h"
 #include "fgnn_cn.h"
-#include "fgnn_vn.h"
 
 #ifndef FGNN_BP4GD_WAVES
 #define FGNN_BP4GD_WAVES 6  // waves per SIMD the register allocation aims at: the most at which no instantiation needs scratch
@@ -52,20 +50,9 @@
 
 namespace {
 
-struct GdArgs {
-    int B, pre_iter, round_iter, rounds, max_steps, tpc, cpb, lds_per_cw, d_off, f_off;
-    float factor, llr_const, decim;
-    const float* llr_ch;     // [B,3,n] or null
-    const uint8_t* synd_x;   // [B,m_x] or null (all-zero syndrome)
-    const uint8_t* synd_z;   // [B,m_z] or null
-    uint8_t* x_hat;          // [B,n]
-    uint8_t* z_hat;          // [B,n]
-    int32_t* stats;          // [B,4]
-};
-
-// the phi of BP4's check rule (decoding_q.py:365-373): what bp4_kernel's exact policy evaluates
-struct PhiBp4 {
-    static __device__ __forceinline__ float phi(float x) { return fg_phi(x); }
+struct GdArgs : StepArgs {
+    int pre_iter, round_iter, rounds, f_off;
+    float factor, decim;
 };
 
 // lamhat of a qubit fixed to d (f = 1 + d), order X, Y, Z: the fixed Pauli's LLR is -D and the others +0; the identity holds all three at +D
@@ -94,10 +81,9 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_
     constexpr bool REGULAR = DV > 0;
     static_assert(!REGULAR || CN_TYPE == FGNN_CN_MINSUM, "the regular rows are compiled for min-sum");
     extern __shared__ float lds[];
-    const int cwl = threadIdx.x / a.tpc;
-    const int lane = threadIdx.x - cwl * a.tpc;
-    const int b = blockIdx.x * a.cpb + cwl;
-    const bool active = b < a.B;
+    const StepCw cw(a);
+    const int cwl = cw.cwl, lane = cw.lane;
+    const StepRows rows(g, a, cw);
     float* msg = lds + (size_t)cwl * a.lds_per_cw;
     uint8_t* dec = reinterpret_cast<uint8_t*>(msg + a.d_off);
     uint8_t* fix = reinterpret_cast<uint8_t*>(msg + a.f_off);
@@ -105,35 +91,20 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_
     int* stamp = reinterpret_cast<int*>(key + 2 * a.cpb);
     int* ndone = stamp + a.cpb;
     const int n = g.n, m = g.m;
-    const size_t bb = active ? (size_t)b : 0;
-    const float* lch = a.llr_ch ? a.llr_ch + bb * 3 * n : nullptr;
-    const uint8_t* sx = a.synd_x ? a.synd_x + bb * g.m_x : nullptr;
-    const uint8_t* sz = a.synd_z ? a.synd_z + bb * g.m_z : nullptr;
-    const int nact = min(a.cpb, a.B - (int)blockIdx.x * a.cpb);
-
-    auto synd_of = [&](const int c) __attribute__((always_inline)) -> unsigned {
-        const uint8_t* s = c < g.m_x ? sx : sz;
-        return s ? (s[c < g.m_x ? c : c - g.m_x] & 1u) : 0u;
-    };
 
     for (int i = threadIdx.x; i < 5 * a.cpb + 1; i += blockDim.x) stamp[i - 4 * a.cpb] = 0;  // key words, stamp, ndone
-    if (active) {
+    if (cw.active) {
         for (int e = lane; e < g.E; e += a.tpc) msg[e] = 0.0f;
         for (int v = lane; v < n; v += a.tpc) {
             dec[v] = 0;
             fix[v] = 0;
         }
     }
-    const bool synd_in_reg = (m + a.tpc - 1) / a.tpc <= 32;
-    unsigned synd_bits = 0;
-    if (active && synd_in_reg) {
-        int i = 0;
-        for (int c = lane; c < m; c += a.tpc, ++i) synd_bits |= synd_of(c) << i;
-    }
+    const StepSynd synd(g, rows, cw, a.tpc);
     __syncthreads();
 
     int r = 0, k = 0, its = 0;
-    bool done = !active;
+    bool done = !cw.active;
     for (int step = 1; step <= a.max_steps; ++step) {
         const int T = (r == 0) ? a.pre_iter : a.round_iter;
         // ---- qubits: marginals after k check updates and their decision, selection key, messages to the checks ----
@@ -145,26 +116,11 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_
                 if (f) {
                     gd_fixed_llrs(f, a.decim, lx, ly, lz);
                 } else {
-                    lx = lch ? lch[v] : a.llr_const;
-                    ly = lch ? lch[n + v] : a.llr_const;
-                    lz = lch ? lch[2 * n + v] : a.llr_const;
+                    rows.llrs(n, v, a.llr_const, lx, ly, lz);
                 }
-                // the qubit's c->v messages (zeros before the first check update) and their sums: only this fetch and the store
-                // below differ between the regular rows, which keep the messages in registers, and the runtime degrees
-                const int x0 = REGULAR ? v * DV : g.vptr_x[v], z0 = REGULAR ? g.E_x + v * DV : g.vptr_z[v];
-                const int dx = REGULAR ? DV : g.vptr_x[v + 1] - x0, dz = REGULAR ? DV : g.vptr_z[v + 1] - z0;
-                float* px = msg + x0;
-                float* pz = msg + z0;
-                float mx[REGULAR ? DV : 1], mz[REGULAR ? DV : 1];
-                float Sz = 0.0f, Sx = 0.0f;
-                if constexpr (REGULAR) {
-#pragma unroll
-                    for (int j = 0; j < DV; ++j) { mz[j] = pz[j]; Sz = Sz + mz[j]; }
-#pragma unroll
-                    for (int j = 0; j < DV; ++j) { mx[j] = px[j]; Sx = Sx + mx[j]; }
-                } else {
-                    vn_sums(msg, z0, z0 + dz, x0, x0 + dx, Sz, Sx);
-                }
+                QubitSlots<DV> q(g, msg, v);
+                float Sz, Sx;
+                q.fetch(Sz, Sx);
                 float X, Y, Z;
                 vn_totals(Sz, Sx, lx, ly, lz, X, Y, Z);
                 if (k > 0) {  // the test's decision; at the end of a round the free qubits bid for the next fix
@@ -177,49 +133,25 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_
                         continue;
                     }
                 }
-                const float numx = VnMath::softplus(-X);
-                const float numz = VnMath::softplus(-Z);
-                if constexpr (REGULAR) {
-#pragma unroll
-                    for (int j = 0; j < DV; ++j) px[j] = vn_edge<VnMath>(numx, Z, Y, mx[j]);
-#pragma unroll
-                    for (int j = 0; j < DV; ++j) pz[j] = vn_edge<VnMath>(numz, X, Y, mz[j]);
-                } else {
-                    for (int j = 0; j < dx; ++j) px[j] = vn_edge<VnMath>(numx, Z, Y, px[j]);
-                    for (int j = 0; j < dz; ++j) pz[j] = vn_edge<VnMath>(numz, X, Y, pz[j]);
-                }
+                q.store(X, Y, Z, vn_edge<VnMath>);
             }
         }
         __syncthreads();
-        if (*ndone == nact) break;  // the same word for every thread, last written before the barrier above
+        if (*ndone == cw.nact) break;  // the same word for every thread, last written before the barrier above
         // ---- checks of both graphs: parity of the decisions (k > 0), then the check update (k < T) ----
         if (!done) {
             int i = 0;
             for (int c = lane; c < m; c += a.tpc, ++i) {
-                const unsigned sy = synd_in_reg ? ((synd_bits >> i) & 1u) : synd_of(c);
+                const unsigned sy = synd.at(g, rows, i, c);
                 const bool is_x = c < g.m_x;
-                const int sh = is_x ? 1 : 0;  // hx rows test z_hat (bit 1 of the decision), hz rows x_hat (bit 0)
                 if constexpr (REGULAR) {
-                    const uint4 pk = reinterpret_cast<const uint4*>(g.cslot16)[c];
-                    const unsigned w[4] = {pk.x, pk.y, pk.z, pk.w};
                     unsigned off[DC];
-#pragma unroll
-                    for (int j = 0; j < DC; ++j) off[j] = (w[j >> 1] >> ((j & 1) * 16)) & 0xffffu;
-                    if (k > 0) {
-                        const unsigned base = is_x ? 0u : (unsigned)g.E_x;  // slot base + v * DV + j belongs to qubit v
-                        unsigned par = sy;
-#pragma unroll
-                        for (int j = 0; j < DC; ++j) par ^= ((unsigned)dec[((off[j] >> 2) - base) / DV] >> sh) & 1u;
-                        if (par) stamp[cwl] = step;
-                    }
+                    row_unpack(g, c, off);
+                    if (k > 0 && parity_regular<DV>(g, dec, off, is_x, sy)) stamp[cwl] = step;
                     if (k < T) cn_minsum_regular<DC>(msg, off, DC, sy, a.factor);
                 } else {
                     const int c0 = g.cptr[c], deg = g.cptr[c + 1] - c0;
-                    if (k > 0) {
-                        unsigned par = sy;
-                        for (int j = 0; j < deg; ++j) par ^= ((unsigned)dec[g.cvn[c0 + j]] >> sh) & 1u;
-                        if (par) stamp[cwl] = step;
-                    }
+                    if (k > 0 && parity_csr(g, dec, c0, deg, is_x, sy)) stamp[cwl] = step;
                     if (k < T) cn_update<CN_TYPE, PhiBp4>(msg, g.cslot + c0, deg, sy, a.factor);
                 }
             }
@@ -233,19 +165,8 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_
             } else {
                 const bool sat = stamp[cwl] != step;
                 if (sat || (k == T && r == a.rounds)) {
-                    for (int v = lane; v < n; v += a.tpc) {
-                        const unsigned d = dec[v];
-                        a.x_hat[bb * n + v] = (uint8_t)(d & 1u);
-                        a.z_hat[bb * n + v] = (uint8_t)(d >> 1);
-                    }
-                    if (lane == 0) {
-                        int32_t* st = a.stats + (size_t)b * 4;
-                        st[0] = sat ? 1 : 0;
-                        st[1] = r;
-                        st[2] = its;
-                        st[3] = k;
-                        atomicAdd(ndone, 1);
-                    }
+                    step_write_decisions(a, dec, rows.bb, n, lane);
+                    if (lane == 0) step_finish(a, (size_t)cw.b, sat, r, its, k, ndone);
                     done = true;
                 } else if (k == T) {
                     // the winner of this round's bids: every thread of the codeword reads it, the qubit's owner fixes it to its decision
@@ -263,68 +184,35 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_
     }
 }
 
-template <int CN_TYPE, int DV, int DC>
-int launch(const fgnn_graph* g, const GdArgs& a, const LaunchGeom& L, size_t lds_bytes, hipStream_t st)
-{
-    return fgnn_launch(bp4gd_kernel<CN_TYPE, DV, DC>, dim3(L.blocks), dim3(L.threads), lds_bytes, st, g->d, a);
-}
-
 }  // namespace
 
 extern "C" int fgnn_bp4gd_decode(const fgnn_graph* g, int cn_type, float normalization_factor, int pre_iter, int round_iter, int max_rounds,
                                  float decim_llr, const float* llr_ch, float llr_const, const uint8_t* synd_x, const uint8_t* synd_z, int B,
                                  uint8_t* x_hat, uint8_t* z_hat, int32_t* stats, void* stream)
 {
-    if (!g) return fgnn_fail(FGNN_ERR_ARG, "graph is NULL");
-    if (g->host_only) return fgnn_fail(FGNN_ERR_ARG, "a host-only graph cannot decode");
-    if (cn_type < 0 || cn_type > 2) return fgnn_fail(FGNN_ERR_ARG, "Unknown node type.");  // decoding_q.py:107
-    if (B < 0) return fgnn_fail(FGNN_ERR_ARG, "B must be >= 0");
+    if (int err = step_check_args(g, cn_type, B)) return err;
     if (pre_iter < 1 || round_iter < 1) return fgnn_fail(FGNN_ERR_ARG, "pre_iter and round_iter must be >= 1");
     if (max_rounds < 0) return fgnn_fail(FGNN_ERR_ARG, "max_rounds must be >= 0");
     if (!(decim_llr > 0.0f)) return fgnn_fail(FGNN_ERR_ARG, "decim_llr must be > 0");
     if (B == 0) return FGNN_OK;  // an empty batch needs no buffers
     if (!x_hat || !z_hat || !stats) return fgnn_fail(FGNN_ERR_ARG, "no output buffer");
     FGNN_DEVICE_GUARD(g->device);
-    LaunchGeom L = fgnn_geom(g, B);
+    const LaunchGeom L = fgnn_geom(g, B);
     GdArgs a;
-    a.B = B;
+    a.rounds = std::min(max_rounds, g->d.n);
+    step_args_fill(a, L, B, pre_iter, a.rounds, round_iter, llr_ch, llr_const, synd_x, synd_z, x_hat, z_hat, stats);
     a.pre_iter = pre_iter;
     a.round_iter = round_iter;
-    a.rounds = std::min(max_rounds, g->d.n);
-    // a codeword takes T + 1 steps per round; one more step lets the workgroup see its last codeword finished
-    const long long steps = (long long)pre_iter + 1 + (long long)a.rounds * ((long long)round_iter + 1) + 1;
-    a.max_steps = (int)std::min<long long>(steps, INT_MAX - 1);
-    a.tpc = L.tpc;
-    a.cpb = L.cpb;
     a.factor = normalization_factor;
-    a.llr_const = llr_const;
     a.decim = decim_llr;
-    a.llr_ch = llr_ch;
-    a.synd_x = synd_x;
-    a.synd_z = synd_z;
-    a.x_hat = x_hat;
-    a.z_hat = z_hat;
-    a.stats = stats;
-    // per codeword: E messages, n decision bytes and n fix bytes, each rounded up to 4 floats; per workgroup: two 64-bit keys and a
-    // stamp per codeword, ndone
-    const size_t bytes_area = (((size_t)g->d.n + 3) / 4 + 3) & ~(size_t)3;
-    const size_t d_off = ((size_t)g->d.E + 3) & ~(size_t)3;
-    const size_t f_off = d_off + bytes_area;
-    const size_t per_cw = f_off + bytes_area;
-    const size_t lds_bytes = per_cw * sizeof(float) * (size_t)L.cpb + (((size_t)5 * L.cpb + 1 + 3) & ~(size_t)3) * sizeof(int);
-    if (lds_bytes > FGNN_LDS_BUDGET)
-        return fgnn_fail(FGNN_ERR_ARG, "code too large for the LDS-resident BP4-GD kernel: " + std::to_string(lds_bytes) +
-                                           " bytes of LDS per workgroup, the limit is " + std::to_string(FGNN_LDS_BUDGET));
+    // per codeword: E messages, n decision bytes and n fix bytes; per workgroup: two 64-bit keys and a stamp per codeword, ndone
+    const size_t d_off = lds_round4(g->d.E), f_off = d_off + lds_bytes_as_floats(g->d.n);
+    size_t lds_bytes;
+    if (int err = step_lds_bytes(a, "BP4-GD", f_off + lds_bytes_as_floats(g->d.n), 0, 5 * L.cpb + 1, &lds_bytes)) return err;
     a.d_off = (int)d_off;
     a.f_off = (int)f_off;
-    a.lds_per_cw = (int)per_cw;
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    switch (cn_type) {
-    case FGNN_CN_BOXPLUS: return launch<FGNN_CN_BOXPLUS, 0, 0>(g, a, L, lds_bytes, st);
-    case FGNN_CN_BOXPLUS_PHI: return launch<FGNN_CN_BOXPLUS_PHI, 0, 0>(g, a, L, lds_bytes, st);
-    default: break;
-    }
-    if (g->d.cslot16 && !g->force_generic && g->d.dvx == 3 && g->d.dvz == 3 && g->d.dc == 6)
-        return launch<FGNN_CN_MINSUM, 3, 6>(g, a, L, lds_bytes, st);
-    return launch<FGNN_CN_MINSUM, 0, 0>(g, a, L, lds_bytes, st);
+    return step_dispatch(g, cn_type, [&](auto cn, auto dv, auto dc) {
+        return fgnn_launch(bp4gd_kernel<decltype(cn)::value, decltype(dv)::value, decltype(dc)::value>, dim3(L.blocks), dim3(L.threads),
+                           lds_bytes, static_cast<hipStream_t>(stream), g->d, a);
+    });
 }

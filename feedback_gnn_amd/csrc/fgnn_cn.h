@@ -26,6 +26,11 @@ __device__ __forceinline__ float& slot_ref(float* msg, IDX byte_off)
 struct PhiGnn {
     static __device__ __forceinline__ float phi(float x) { return fg_phi_gnn(x); }
 };
+// the phi of BP4's check rule and soft syndromes (decoding_q.py:365-373): what bp4_kernel's exact policy evaluates; the step-loop decoders
+// (fgnn_step.h) and the layered schedule pass it
+struct PhiBp4 {
+    static __device__ __forceinline__ float phi(float x) { return fg_phi(x); }
+};
 
 // ---------------------------------------------------------------------------------------------
 // Check-node rules on runtime-degree rows.  `msg` = this codeword's LDS message array, `slot` =

@@ -3,8 +3,10 @@
 // schedule, LDS-resident, with the attempt list of AMBP4 kept.  Check c carries a syndrome LLR gamma_c: the error u_c of its measured
 // bit is a degree-one variable on the check, so it is one more constant input of the check rule (fgnn_cn_soft.h), held in a register,
 // and the decoder returns u_hat next to the data error.  A sample is solved when H e_hat == s ^ u_hat on both graphs.  The algorithm is
-// stated to the float operation at fgnn_dsbp4_decode in include/fgnn.h.  The kernel is a sibling of mbp4_kernel (fgnn_mbp4.hip): the
-// same message layout, literal qubit update with own[a], factor[a], step / stop control, parity-by-stamp test and ndone exit.
+// stated to the float operation at fgnn_dsbp4_decode in include/fgnn.h.  The kernel stands on the frame of the step-loop decoders
+// (fgnn_step.h): staged syndrome bits, a qubit's slots, a check's row and parity (started from s ^ u_hat), the output write; its
+// attempt walk, `tab` table and own-weight edge rule are mbp4_kernel's (fgnn_mbp4.hip).  Its own are the `uh` bytes, the soft check
+// rule and the addressing of its inputs (DsRows below, where the other four kernels use StepRows).
 //
 // LDS of one codeword, in floats, each area rounded up to 4 floats:
 //   msg  [E_x + E_z]  c->v / v->c messages, bp4_kernel's layout
@@ -30,13 +32,10 @@
 //
 // Registers.  Compiled for FGNN_DSBP4_WAVES waves per SIMD, the most at which no instantiation needs scratch (DESIGN.md section 4,
 // "Soft syndromes", lists what each instantiation takes).
-#include <climits>
 #include <cmath>
 
-#include "fgnn_internal.h"
-#include "fgnn_math.h"
+#include "fgnn_step.h"
 #include "fgnn_cn_soft.h"
-#include "fgnn_vn.h"
 
 #ifndef FGNN_DSBP4_WAVES
 #define FGNN_DSBP4_WAVES 7  // waves per SIMD the register allocation aims at
@@ -49,20 +48,47 @@ namespace {
 
 constexpr int DSBP4_MAX_ATTEMPTS = 64;
 
-struct DsArgs {
-    int B, pre_iter, attempt_iter, attempts, restart, max_steps, tpc, cpb, lds_per_cw, d_off, u_off;
-    float llr_const, gamma_x, gamma_z;
-    const float* llr_ch;      // [B,3,n] or null
-    const uint8_t* synd_x;    // [B,m_x] or null (all-zero syndrome)
-    const uint8_t* synd_z;    // [B,m_z] or null
+struct DsArgs : StepArgs {
+    int pre_iter, attempt_iter, attempts, restart, u_off;
+    float gamma_x, gamma_z;
     const float* synd_llr_x;  // [B,m_x] or null (gamma_x for every hx check)
     const float* synd_llr_z;  // [B,m_z] or null
-    uint8_t* x_hat;           // [B,n]
-    uint8_t* z_hat;           // [B,n]
     uint8_t* u_x_hat;         // [B,m_x]
     uint8_t* u_z_hat;         // [B,m_z]
-    int32_t* stats;           // [B,4]
     float tab[2 * DSBP4_MAX_ATTEMPTS];  // factor[0..63], own[0..63]; entries from `attempts` on are 0 and never read
+};
+
+// This kernel's form of StepRows (fgnn_step.h): the inputs are addressed as the rows of the workgroup's first codeword, the same for
+// every lane, plus a 32-bit offset per lane (a workgroup's codewords fit the LDS, so cpb * 3 n is small): no per-lane pointer lives
+// through the kernel, which takes 71 of the 72 VGPRs of seven waves
+struct DsRows {
+    const float* lch0;
+    const uint8_t* sx0;
+    const uint8_t* sz0;
+    unsigned lo;
+    int cwl;
+    __device__ __forceinline__ DsRows(const GraphDev& g, const StepArgs& a, const StepCw& cw)
+    {
+        const size_t b0 = (size_t)blockIdx.x * a.cpb;
+        lch0 = a.llr_ch ? a.llr_ch + b0 * 3 * g.n : nullptr;
+        sx0 = a.synd_x ? a.synd_x + b0 * g.m_x : nullptr;
+        sz0 = a.synd_z ? a.synd_z + b0 * g.m_z : nullptr;
+        lo = (unsigned)(cw.cwl * 3 * g.n);
+        cwl = cw.cwl;
+    }
+    __device__ __forceinline__ unsigned synd_of(const GraphDev& g, const int c) const
+    {
+        const bool is_x = c < g.m_x;
+        const uint8_t* s = is_x ? sx0 : sz0;
+        const unsigned o = is_x ? (unsigned)(cwl * g.m_x + c) : (unsigned)(cwl * g.m_z + (c - g.m_x));
+        return s ? (s[o] & 1u) : 0u;
+    }
+    __device__ __forceinline__ void llrs(const int n, const int v, const float llr_const, float& lx, float& ly, float& lz) const
+    {
+        lx = lch0 ? lch0[lo + (unsigned)v] : llr_const;
+        ly = lch0 ? lch0[lo + (unsigned)(n + v)] : llr_const;
+        lz = lch0 ? lch0[lo + (unsigned)(2 * n + v)] : llr_const;
+    }
 };
 
 // gamma of check c of the workgroup's codeword cwl: the side's array, or its scalar.  gx0 / gz0 are the rows of the workgroup's first
@@ -83,55 +109,34 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_
     constexpr bool REGULAR = DV > 0;
     static_assert(!REGULAR || CN_TYPE == FGNN_CN_MINSUM, "the regular rows are compiled for min-sum");
     extern __shared__ float lds[];
-    const int cwl = threadIdx.x / a.tpc;
-    const int lane = threadIdx.x - cwl * a.tpc;
-    const int b = blockIdx.x * a.cpb + cwl;
-    const bool active = b < a.B;
+    const StepCw cw(a);
+    const int cwl = cw.cwl, lane = cw.lane;
+    const DsRows rows(g, a, cw);
     float* msg = lds + (size_t)cwl * a.lds_per_cw;
     uint8_t* dec = reinterpret_cast<uint8_t*>(msg + a.d_off);
     uint8_t* uh = reinterpret_cast<uint8_t*>(msg + a.u_off);
     float* tab = lds + (size_t)a.cpb * a.lds_per_cw;
     int* stamp = reinterpret_cast<int*>(tab + 2 * DSBP4_MAX_ATTEMPTS);
     int* ndone = stamp + a.cpb;
-    const int n = g.n, m = g.m, tpc = a.tpc;
-    // inputs are addressed as the rows of the workgroup's first codeword, the same for every lane, plus a 32-bit offset per lane
-    // (a workgroup's codewords fit the LDS, so cpb * 3 n is small): no per-lane pointer lives through the kernel
+    const int n = g.n, m = g.m;
     const size_t b0 = (size_t)blockIdx.x * a.cpb;
-    const float* lch0 = a.llr_ch ? a.llr_ch + b0 * 3 * n : nullptr;
-    const uint8_t* sx0 = a.synd_x ? a.synd_x + b0 * g.m_x : nullptr;
-    const uint8_t* sz0 = a.synd_z ? a.synd_z + b0 * g.m_z : nullptr;
     const float* gx0 = a.synd_llr_x ? a.synd_llr_x + b0 * g.m_x : nullptr;
     const float* gz0 = a.synd_llr_z ? a.synd_llr_z + b0 * g.m_z : nullptr;
-    const unsigned lo = (unsigned)(cwl * 3 * n);
-    const int nact = min(a.cpb, a.B - (int)blockIdx.x * a.cpb);
-
-    auto synd_of = [&](const int c) __attribute__((always_inline)) -> unsigned {
-        const bool is_x = c < g.m_x;
-        const uint8_t* s = is_x ? sx0 : sz0;
-        const unsigned o = is_x ? (unsigned)(cwl * g.m_x + c) : (unsigned)(cwl * g.m_z + (c - g.m_x));
-        return s ? (s[o] & 1u) : 0u;
-    };
     const float gamma_x = a.gamma_x, gamma_z = a.gamma_z;
 #define GAMMA_OF(c) gamma_at(gx0, gz0, gamma_x, gamma_z, cwl, g.m_x, g.m_z, (c))
 
     for (int i = threadIdx.x; i < 2 * DSBP4_MAX_ATTEMPTS; i += blockDim.x) tab[i] = a.tab[i];
     for (int i = threadIdx.x; i < a.cpb + 1; i += blockDim.x) stamp[i] = 0;  // stamp, ndone
-    if (active) {
+    if (cw.active) {
         for (int e = lane; e < g.E; e += a.tpc) msg[e] = 0.0f;
         for (int v = lane; v < n; v += a.tpc) dec[v] = 0;
         for (int c = lane; c < m; c += a.tpc) uh[c] = 0;
     }
-    const int per_lane = (m + a.tpc - 1) / a.tpc;
-    const bool synd_in_reg = per_lane <= 32;
-    unsigned synd_bits = 0;
-    if (active && synd_in_reg) {
-        int i = 0;
-        for (int c = lane; c < m; c += a.tpc, ++i) synd_bits |= synd_of(c) << i;
-    }
+    const StepSynd synd(g, rows, cw, a.tpc);
     __syncthreads();
 
     int r = 0, k = 0, its = 0;  // r < a.attempts <= 64 throughout: the last attempt ends the codeword
-    bool done = !active;
+    bool done = !cw.active;
     for (int step = 1; step <= a.max_steps; ++step) {
         const int T = (r == 0) ? a.pre_iter : a.attempt_iter;
         // ---- qubits: marginals after k check updates and their decision, messages to the checks ----
@@ -139,87 +144,48 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_
             const bool zero = a.restart && k == 0 && r > 0;  // a restarting attempt starts from zero messages
             const float ow = tab[DSBP4_MAX_ATTEMPTS + r];
             for (int v = lane; v < n; v += a.tpc) {
-                const float lx = lch0 ? lch0[lo + (unsigned)v] : a.llr_const;
-                const float ly = lch0 ? lch0[lo + (unsigned)(n + v)] : a.llr_const;
-                const float lz = lch0 ? lch0[lo + (unsigned)(2 * n + v)] : a.llr_const;
-                const int x0 = REGULAR ? v * DV : g.vptr_x[v], z0 = REGULAR ? g.E_x + v * DV : g.vptr_z[v];
-                const int dx = REGULAR ? DV : g.vptr_x[v + 1] - x0, dz = REGULAR ? DV : g.vptr_z[v + 1] - z0;
-                float* px = msg + x0;
-                float* pz = msg + z0;
-                if (zero) {  // the slots of a qubit are its owner's in this phase
-                    for (int j = 0; j < dx; ++j) px[j] = 0.0f;
-                    for (int j = 0; j < dz; ++j) pz[j] = 0.0f;
-                }
-                float mx[REGULAR ? DV : 1], mz[REGULAR ? DV : 1];
-                float Sz = 0.0f, Sx = 0.0f;
-                if constexpr (REGULAR) {
-#pragma unroll
-                    for (int j = 0; j < DV; ++j) { mz[j] = pz[j]; Sz = Sz + mz[j]; }
-#pragma unroll
-                    for (int j = 0; j < DV; ++j) { mx[j] = px[j]; Sx = Sx + mx[j]; }
-                } else {
-                    vn_sums(msg, z0, z0 + dz, x0, x0 + dx, Sz, Sx);
-                }
+                float lx, ly, lz;
+                rows.llrs(n, v, a.llr_const, lx, ly, lz);
+                QubitSlots<DV> q(g, msg, v);
+                if (zero) q.clear();
+                float Sz, Sx;
+                q.fetch(Sz, Sx);
                 float X, Y, Z;
                 vn_totals(Sz, Sx, lx, ly, lz, X, Y, Z);
                 if (k > 0) {  // the test's decision; an attempt's last test sends no messages
                     dec[v] = (uint8_t)vn_decide(X, Y, Z);
                     if (k == T) continue;
                 }
-                const float numx = VnMath::softplus(-X);
-                const float numz = VnMath::softplus(-Z);
-                if constexpr (REGULAR) {
-#pragma unroll
-                    for (int j = 0; j < DV; ++j) px[j] = vn_edge_own<VnMath>(numx, Z, Y, mx[j], ow);
-#pragma unroll
-                    for (int j = 0; j < DV; ++j) pz[j] = vn_edge_own<VnMath>(numz, X, Y, mz[j], ow);
-                } else {
-                    for (int j = 0; j < dx; ++j) px[j] = vn_edge_own<VnMath>(numx, Z, Y, px[j], ow);
-                    for (int j = 0; j < dz; ++j) pz[j] = vn_edge_own<VnMath>(numz, X, Y, pz[j], ow);
-                }
+                q.store(X, Y, Z, [&](float num, float A, float Ye, float mu) { return vn_edge_own<VnMath>(num, A, Ye, mu, ow); });
             }
         }
         __syncthreads();
-        if (*ndone == nact) break;  // the same word for every thread, last written before the barrier above
+        if (*ndone == cw.nact) break;  // the same word for every thread, last written before the barrier above
         // ---- checks of both graphs: parity of the decisions against s ^ u_hat (k > 0), then the soft check update (k < T) ----
         if (!done) {
             const float fac = tab[r];
             // one check: c, its index i among the lane's checks, its syndrome LLR
             auto one_check = [&](const int c, const int i, const float gm) __attribute__((always_inline)) {
-                const unsigned sy = synd_in_reg ? ((synd_bits >> i) & 1u) : synd_of(c);
+                const unsigned sy = synd.at(g, rows, i, c);
                 const bool is_x = c < g.m_x;
-                const int sh = is_x ? 1 : 0;  // hx rows test z_hat (bit 1 of the decision), hz rows x_hat (bit 0)
                 const unsigned ut = (unsigned)uh[c] & 1u;  // u_hat of the check update before this step: this lane wrote it
                 unsigned un = ut;
                 bool odd = false;
                 if constexpr (REGULAR) {
-                    const uint4 pk = reinterpret_cast<const uint4*>(g.cslot16)[c];
-                    const unsigned w[4] = {pk.x, pk.y, pk.z, pk.w};
                     unsigned off[DC];
-#pragma unroll
-                    for (int j = 0; j < DC; ++j) off[j] = (w[j >> 1] >> ((j & 1) * 16)) & 0xffffu;
-                    if (k > 0) {
-                        const unsigned base = is_x ? 0u : (unsigned)g.E_x;  // slot base + v * DV + j belongs to qubit v
-                        unsigned par = sy ^ ut;
-#pragma unroll
-                        for (int j = 0; j < DC; ++j) par ^= ((unsigned)dec[((off[j] >> 2) - base) / DV] >> sh) & 1u;
-                        odd = par != 0u;
-                    }
+                    row_unpack(g, c, off);
+                    if (k > 0) odd = parity_regular<DV>(g, dec, off, is_x, sy ^ ut) != 0u;
                     if (k < T) un = soft_u_hat(gm, cn_soft_minsum_regular<DC>(msg, off, DC, sy, gm, fac));
                 } else {
                     const int c0 = g.cptr[c], deg = g.cptr[c + 1] - c0;
-                    if (k > 0) {
-                        unsigned par = sy ^ ut;
-                        for (int j = 0; j < deg; ++j) par ^= ((unsigned)dec[g.cvn[c0 + j]] >> sh) & 1u;
-                        odd = par != 0u;
-                    }
+                    if (k > 0) odd = parity_csr(g, dec, c0, deg, is_x, sy ^ ut) != 0u;
                     if (k < T) un = soft_u_hat(gm, cn_soft_update<CN_TYPE, PhiSoft>(msg, g.cslot + c0, deg, sy, gm, fac));
                 }
                 uh[c] = (uint8_t)(un | (ut << 1));
                 if (odd) stamp[cwl] = step;
             };
             int i = 0;
-            for (int c = lane; c < m; c += tpc, ++i) one_check(c, i, k < T ? GAMMA_OF(c) : 0.0f);
+            for (int c = lane; c < m; c += a.tpc, ++i) one_check(c, i, k < T ? GAMMA_OF(c) : 0.0f);
         }
         __syncthreads();
         // ---- per codeword: solution found, attempt over, decoder finished ----
@@ -232,27 +198,16 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_
                 if (sat || (k == T && r == a.attempts - 1)) {
                     // the output rows are addressed from a laundered copy of b: formed here, once per codeword, instead of living in
                     // per-lane 64-bit registers through every step
-                    int bo = b;
+                    int bo = cw.b;
                     asm volatile("" : "+v"(bo));
                     const size_t ob = (size_t)bo;
-                    for (int v = lane; v < n; v += a.tpc) {
-                        const unsigned d = dec[v];
-                        a.x_hat[ob * n + v] = (uint8_t)(d & 1u);
-                        a.z_hat[ob * n + v] = (uint8_t)(d >> 1);
-                    }
+                    step_write_decisions(a, dec, ob, n, lane);
                     for (int c = lane; c < m; c += a.tpc) {  // the lane that wrote the byte
                         const uint8_t u = (uint8_t)((uh[c] >> 1) & 1u);
                         if (c < g.m_x) a.u_x_hat[ob * g.m_x + c] = u;
                         else a.u_z_hat[ob * g.m_z + (c - g.m_x)] = u;
                     }
-                    if (lane == 0) {
-                        int32_t* st = a.stats + ob * 4;
-                        st[0] = sat ? 1 : 0;
-                        st[1] = r;
-                        st[2] = its;
-                        st[3] = k;
-                        atomicAdd(ndone, 1);
-                    }
+                    if (lane == 0) step_finish(a, ob, sat, r, its, k, ndone);
                     done = true;
                 } else if (k == T) {
                     ++r;
@@ -268,12 +223,6 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_
 
 #undef GAMMA_OF
 
-template <int CN_TYPE, int DV, int DC>
-int launch(const fgnn_graph* g, const DsArgs& a, const LaunchGeom& L, size_t lds_bytes, hipStream_t st)
-{
-    return fgnn_launch(dsbp4_kernel<CN_TYPE, DV, DC>, dim3(L.blocks), dim3(L.threads), lds_bytes, st, g->d, a);
-}
-
 }  // namespace
 
 extern "C" int fgnn_dsbp4_decode(const fgnn_graph* g, int cn_type, int num_attempts, const float* factor, const float* own, int pre_iter,
@@ -281,10 +230,7 @@ extern "C" int fgnn_dsbp4_decode(const fgnn_graph* g, int cn_type, int num_attem
                                  const uint8_t* synd_z, const float* synd_llr_x, float gamma_x, const float* synd_llr_z, float gamma_z,
                                  int B, uint8_t* x_hat, uint8_t* z_hat, uint8_t* u_x_hat, uint8_t* u_z_hat, int32_t* stats, void* stream)
 {
-    if (!g) return fgnn_fail(FGNN_ERR_ARG, "graph is NULL");
-    if (g->host_only) return fgnn_fail(FGNN_ERR_ARG, "a host-only graph cannot decode");
-    if (cn_type < 0 || cn_type > 2) return fgnn_fail(FGNN_ERR_ARG, "Unknown node type.");  // decoding_q.py:107
-    if (B < 0) return fgnn_fail(FGNN_ERR_ARG, "B must be >= 0");
+    if (int err = step_check_args(g, cn_type, B)) return err;
     if (num_attempts < 1 || num_attempts > DSBP4_MAX_ATTEMPTS) return fgnn_fail(FGNN_ERR_ARG, "num_attempts must be in 1 .. 64");
     if (pre_iter < 1 || attempt_iter < 1) return fgnn_fail(FGNN_ERR_ARG, "pre_iter and attempt_iter must be >= 1");
     if (restart != 0 && restart != 1) return fgnn_fail(FGNN_ERR_ARG, "restart must be 0 or 1");
@@ -297,57 +243,33 @@ extern "C" int fgnn_dsbp4_decode(const fgnn_graph* g, int cn_type, int num_attem
     if (B == 0) return FGNN_OK;  // an empty batch needs no buffers
     if (!x_hat || !z_hat || !u_x_hat || !u_z_hat || !stats) return fgnn_fail(FGNN_ERR_ARG, "no output buffer");
     FGNN_DEVICE_GUARD(g->device);
-    LaunchGeom L = fgnn_geom(g, B);
+    const LaunchGeom L = fgnn_geom(g, B);
     DsArgs a;
-    a.B = B;
+    step_args_fill(a, L, B, pre_iter, num_attempts - 1, attempt_iter, llr_ch, llr_const, synd_x, synd_z, x_hat, z_hat, stats);
     a.pre_iter = pre_iter;
     a.attempt_iter = attempt_iter;
     a.attempts = num_attempts;
     a.restart = restart;
-    // a codeword takes T + 1 steps per attempt; one more step lets the workgroup see its last codeword finished
-    const long long steps = (long long)pre_iter + 1 + (long long)(num_attempts - 1) * ((long long)attempt_iter + 1) + 1;
-    a.max_steps = (int)std::min<long long>(steps, INT_MAX - 1);
-    a.tpc = L.tpc;
-    a.cpb = L.cpb;
-    a.llr_const = llr_const;
     a.gamma_x = gamma_x;
     a.gamma_z = gamma_z;
-    a.llr_ch = llr_ch;
-    a.synd_x = synd_x;
-    a.synd_z = synd_z;
     a.synd_llr_x = synd_llr_x;
     a.synd_llr_z = synd_llr_z;
-    a.x_hat = x_hat;
-    a.z_hat = z_hat;
     a.u_x_hat = u_x_hat;
     a.u_z_hat = u_z_hat;
-    a.stats = stats;
     for (int i = 0; i < DSBP4_MAX_ATTEMPTS; ++i) {
         a.tab[i] = i < num_attempts ? factor[i] : 0.0f;
         a.tab[DSBP4_MAX_ATTEMPTS + i] = i < num_attempts ? own[i] : 0.0f;
     }
-    // per codeword: E messages, n decision bytes and m u_hat bytes, each rounded up to 4 floats; per workgroup: the two 64-float tables,
-    // a stamp per codeword and ndone
-    const size_t dec_area = (((size_t)g->d.n + 3) / 4 + 3) & ~(size_t)3;
-    const size_t uh_area = (((size_t)g->d.m + 3) / 4 + 3) & ~(size_t)3;
-    const size_t d_off = ((size_t)g->d.E + 3) & ~(size_t)3;
-    const size_t u_off = d_off + dec_area;
-    const size_t per_cw = u_off + uh_area;
-    const size_t lds_bytes = per_cw * sizeof(float) * (size_t)L.cpb + (size_t)2 * DSBP4_MAX_ATTEMPTS * sizeof(float) +
-                             (((size_t)L.cpb + 1 + 3) & ~(size_t)3) * sizeof(int);
-    if (lds_bytes > FGNN_LDS_BUDGET)
-        return fgnn_fail(FGNN_ERR_ARG, "code too large for the LDS-resident soft-syndrome BP4 kernel: " + std::to_string(lds_bytes) +
-                                           " bytes of LDS per workgroup, the limit is " + std::to_string(FGNN_LDS_BUDGET));
+    // per codeword: E messages, n decision bytes and m u_hat bytes; per workgroup: the two 64-float tables, a stamp per codeword and
+    // ndone
+    const size_t d_off = lds_round4(g->d.E), u_off = d_off + lds_bytes_as_floats(g->d.n);
+    size_t lds_bytes;
+    if (int err = step_lds_bytes(a, "soft-syndrome BP4", u_off + lds_bytes_as_floats(g->d.m), 2 * DSBP4_MAX_ATTEMPTS, L.cpb + 1, &lds_bytes))
+        return err;
     a.d_off = (int)d_off;
     a.u_off = (int)u_off;
-    a.lds_per_cw = (int)per_cw;
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    switch (cn_type) {
-    case FGNN_CN_BOXPLUS: return launch<FGNN_CN_BOXPLUS, 0, 0>(g, a, L, lds_bytes, st);
-    case FGNN_CN_BOXPLUS_PHI: return launch<FGNN_CN_BOXPLUS_PHI, 0, 0>(g, a, L, lds_bytes, st);
-    default: break;
-    }
-    if (g->d.cslot16 && !g->force_generic && g->d.dvx == 3 && g->d.dvz == 3 && g->d.dc == 6)
-        return launch<FGNN_CN_MINSUM, 3, 6>(g, a, L, lds_bytes, st);
-    return launch<FGNN_CN_MINSUM, 0, 0>(g, a, L, lds_bytes, st);
+    return step_dispatch(g, cn_type, [&](auto cn, auto dv, auto dc) {
+        return fgnn_launch(dsbp4_kernel<decltype(cn)::value, decltype(dv)::value, decltype(dc)::value>, dim3(L.blocks), dim3(L.threads),
+                           lds_bytes, static_cast<hipStream_t>(stream), g->d, a);
+    });
 }

@@ -3,7 +3,10 @@
 // Relay-BP's memory term (Mueller et al., "Improved belief propagation is sufficient for real-time decoding of quantum memories", 2025)
 // applied to each of a qubit's three LLRs, in the form include/fgnn.h states at fgnn_relay4_decode.  The qubit update is the literal
 // form of fgnn_vn.h (one log-sum-exp per edge, fgnn_math.h) with the memory-weighted LLRs Lam in place of the channel LLRs,
-// the check update is the shared min-sum rule of fgnn_cn.h, the leg / stop / weight control is relay_kernel's (fgnn_relay.hip).  No
+// the check update is the shared min-sum rule of fgnn_cn.h, the leg / stop / weight control is relay_kernel's (fgnn_relay.hip).  The
+// kernel stands on the frame of the step-loop decoders (fgnn_step.h): codeword rows, staged syndrome bits, a qubit's slots (counted as
+// zeros before a leg's first check update), a check's row and parity, the write of the decisions; its own are the leg walk below, the
+// posteriors M, the weights and the late stats write.  No
 // saturation shortcuts, no register-resident channel LLRs, no hardware transcendentals: the channel LLRs are re-read from global
 // memory (L2) by the thread that owns the qubit, every float operation is the one bp4_kernel and cn_update execute, in their order.
 //
@@ -22,14 +25,10 @@
 //
 // Occupancy.  With 256 threads (4 waves) per codeword the LDS above admits 4 workgroups of [[882,24]] on a CU (5 x (32 672 + the 256
 // bytes of the log table) exceed 160 KiB) and 3 of [[1270,28]]: 4 waves per SIMD at the most, whatever the registers allow.  The kernels
-// are therefore compiled for 4 waves per SIMD (a budget of 128 VGPRs): the (3,3,6) instantiation takes 88 VGPRs and the loop 67, no
+// are therefore compiled for 4 waves per SIMD (a budget of 128 VGPRs): the (3,3,6) instantiation takes 88 VGPRs and the loop 68, no
 // spills, no scratch.  Asking for more waves would only squeeze the allocation of a kernel whose residency LDS decides.
-#include <climits>
-
-#include "fgnn_internal.h"
-#include "fgnn_math.h"
+#include "fgnn_step.h"
 #include "fgnn_cn.h"
-#include "fgnn_vn.h"
 
 #ifndef FGNN_RELAY4_WAVES
 #define FGNN_RELAY4_WAVES 4  // waves per SIMD the register allocation aims at: what the LDS of the benchmark codes admits
@@ -37,16 +36,10 @@
 
 namespace {
 
-struct Relay4Args {
-    int B, pre_iter, num_legs, leg_iter, stop_nconv, max_steps, tpc, cpb, lds_per_cw, m_off, d_off;
-    float factor, llr_const;
+struct Relay4Args : StepArgs {
+    int pre_iter, num_legs, leg_iter, stop_nconv, m_off;
+    float factor;
     const float* gamma;      // [num_legs,n]
-    const float* llr_ch;     // [B,3,n] or null
-    const uint8_t* synd_x;   // [B,m_x] or null (all-zero syndrome)
-    const uint8_t* synd_z;   // [B,m_z] or null
-    uint8_t* x_hat;          // [B,n]
-    uint8_t* z_hat;          // [B,n]
-    int32_t* stats;          // [B,4]
 };
 
 // the weight of deciding Pauli d (1 = X, 2 = Z, 3 = Y) at a qubit with channel LLRs (lx, ly, lz)
@@ -63,10 +56,9 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_
     FG_LOG_TAB_SETUP();
     constexpr bool REGULAR = DV > 0;
     extern __shared__ float lds[];
-    const int cwl = threadIdx.x / a.tpc;
-    const int lane = threadIdx.x - cwl * a.tpc;
-    const int b = blockIdx.x * a.cpb + cwl;
-    const bool active = b < a.B;
+    const StepCw cw(a);
+    const int cwl = cw.cwl, lane = cw.lane;
+    const StepRows rows(g, a, cw);
     float* msg = lds + (size_t)cwl * a.lds_per_cw;
     float* M = msg + a.m_off;
     uint8_t* dec = reinterpret_cast<uint8_t*>(msg + a.d_off);
@@ -74,66 +66,33 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_
     int* wacc = stamp + a.cpb;
     int* ndone = wacc + a.cpb;
     const int n = g.n, m = g.m;
-    const size_t bb = active ? (size_t)b : 0;
-    const float* lch = a.llr_ch ? a.llr_ch + bb * 3 * n : nullptr;
-    const uint8_t* sx = a.synd_x ? a.synd_x + bb * g.m_x : nullptr;
-    const uint8_t* sz = a.synd_z ? a.synd_z + bb * g.m_z : nullptr;
-    const int nact = min(a.cpb, a.B - (int)blockIdx.x * a.cpb);
-
-    auto synd_of = [&](const int c) __attribute__((always_inline)) -> unsigned {
-        const uint8_t* s = c < g.m_x ? sx : sz;
-        return s ? (s[c < g.m_x ? c : c - g.m_x] & 1u) : 0u;
-    };
 
     for (int i = threadIdx.x; i < 2 * a.cpb + 1; i += blockDim.x) stamp[i] = 0;
-    if (active)
+    if (cw.active)
         for (int v = lane; v < n; v += a.tpc) {
-            M[v] = lch ? lch[v] : a.llr_const;
-            M[n + v] = lch ? lch[n + v] : a.llr_const;
-            M[2 * n + v] = lch ? lch[2 * n + v] : a.llr_const;
+            rows.llrs(n, v, a.llr_const, M[v], M[n + v], M[2 * n + v]);
             dec[v] = 0;
         }
-    const bool synd_in_reg = (m + a.tpc - 1) / a.tpc <= 32;
-    unsigned synd_bits = 0;
-    if (active && synd_in_reg) {
-        int i = 0;
-        for (int c = lane; c < m; c += a.tpc, ++i) synd_bits |= synd_of(c) << i;
-    }
+    const StepSynd synd(g, rows, cw, a.tpc);
     __syncthreads();
 
     int r = 0, k = 0, found = 0, best_w = 0, best_r = 0, best_k = 0, wprev = 0, pend_r = 0, pend_k = 0;
-    bool done = !active, written = !active, pending = false;
+    bool done = !cw.active, written = !cw.active, pending = false;
     for (int step = 1; step <= a.max_steps; ++step) {
         const int T = (r == 0) ? a.pre_iter : a.leg_iter;
         // ---- qubits: marginals after k check updates and their decision, memory term, messages to the checks ----
         if (!done) {
             const float* gam = a.gamma + (size_t)r * n;
             for (int v = lane; v < n; v += a.tpc) {
-                const float lx = lch ? lch[v] : a.llr_const, ly = lch ? lch[n + v] : a.llr_const, lz = lch ? lch[2 * n + v] : a.llr_const;
+                float lx, ly, lz;
+                rows.llrs(n, v, a.llr_const, lx, ly, lz);
                 const float gv = gam[v];
                 const float om = 1.0f - gv;
                 float MX = M[v], MY = M[n + v], MZ = M[2 * n + v];
-                // the qubit's c->v messages (zeros before the first check update of a leg) and their sums: only this fetch and the
-                // store below differ between the regular rows, which keep the messages in registers, and the runtime degrees
-                const int x0 = REGULAR ? v * DV : g.vptr_x[v], z0 = REGULAR ? g.E_x + v * DV : g.vptr_z[v];
-                const int dx = REGULAR ? DV : g.vptr_x[v + 1] - x0, dz = REGULAR ? DV : g.vptr_z[v + 1] - z0;
-                float* px = msg + x0;
-                float* pz = msg + z0;
-                float mx[REGULAR ? DV : 1], mz[REGULAR ? DV : 1];
-                float Sz = 0.0f, Sx = 0.0f;
-                if constexpr (REGULAR) {
-                    if (k > 0) {
-#pragma unroll
-                        for (int j = 0; j < DV; ++j) { mz[j] = pz[j]; Sz = Sz + mz[j]; }
-#pragma unroll
-                        for (int j = 0; j < DV; ++j) { mx[j] = px[j]; Sx = Sx + mx[j]; }
-                    } else {
-#pragma unroll
-                        for (int j = 0; j < DV; ++j) mz[j] = mx[j] = 0.0f;
-                    }
-                } else if (k > 0) {
-                    vn_sums(msg, z0, z0 + dz, x0, x0 + dx, Sz, Sx);
-                }
+                // the qubit's c->v messages: zeros before the first check update of a leg, whatever the last leg left in the slots
+                QubitSlots<DV> q(g, msg, v);
+                float Sz, Sx;
+                q.fetch(Sz, Sx, k > 0);
                 if (k > 0) {  // posteriors of the memory-weighted LLRs, kept for the next memory term, and their decision (fgnn_vn.h)
                     vn_totals(Sz, Sx, om * lx + gv * MX, om * ly + gv * MY, om * lz + gv * MZ, MX, MY, MZ);
                     M[v] = MX;
@@ -144,17 +103,7 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_
                 }
                 float X, Y, Z;
                 vn_totals(Sz, Sx, om * lx + gv * MX, om * ly + gv * MY, om * lz + gv * MZ, X, Y, Z);
-                const float numx = VnMath::softplus(-X);
-                const float numz = VnMath::softplus(-Z);
-                if constexpr (REGULAR) {
-#pragma unroll
-                    for (int j = 0; j < DV; ++j) px[j] = vn_edge<VnMath>(numx, Z, Y, mx[j]);
-#pragma unroll
-                    for (int j = 0; j < DV; ++j) pz[j] = vn_edge<VnMath>(numz, X, Y, mz[j]);
-                } else {
-                    for (int j = 0; j < dx; ++j) px[j] = vn_edge<VnMath>(numx, Z, Y, k > 0 ? px[j] : 0.0f);
-                    for (int j = 0; j < dz; ++j) pz[j] = vn_edge<VnMath>(numz, X, Y, k > 0 ? pz[j] : 0.0f);
-                }
+                q.store(X, Y, Z, vn_edge<VnMath>, k > 0);
             }
         }
         __syncthreads();
@@ -167,17 +116,13 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_
                 best_w = w;
                 best_r = pend_r;
                 best_k = pend_k;
-                for (int v = lane; v < n; v += a.tpc) {
-                    const unsigned d = dec[v];
-                    a.x_hat[bb * n + v] = (uint8_t)(d & 1u);
-                    a.z_hat[bb * n + v] = (uint8_t)(d >> 1);
-                }
+                step_write_decisions(a, dec, rows.bb, n, lane);
             }
             pending = false;
         }
         if (done && !written) {
             if (lane == 0) {
-                int32_t* st = a.stats + (size_t)b * 4;
+                int32_t* st = a.stats + (size_t)cw.b * 4;
                 st[0] = found;
                 st[1] = best_w;
                 st[2] = best_r;
@@ -185,35 +130,21 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_
             }
             written = true;
         }
-        if (*ndone == nact) break;  // the same word for every thread, last written before the barrier above
+        if (*ndone == cw.nact) break;  // the same word for every thread, last written before the barrier above
         // ---- checks of both graphs: parity of the decisions (k > 0), then the min-sum update (k < T) ----
         if (!done) {
             int i = 0;
             for (int c = lane; c < m; c += a.tpc, ++i) {
-                const unsigned sy = synd_in_reg ? ((synd_bits >> i) & 1u) : synd_of(c);
+                const unsigned sy = synd.at(g, rows, i, c);
                 const bool is_x = c < g.m_x;
-                const int sh = is_x ? 1 : 0;  // hx rows test z_hat (bit 1 of the decision), hz rows x_hat (bit 0)
                 if constexpr (REGULAR) {
-                    const uint4 pk = reinterpret_cast<const uint4*>(g.cslot16)[c];
-                    const unsigned w[4] = {pk.x, pk.y, pk.z, pk.w};
                     unsigned off[DC];
-#pragma unroll
-                    for (int j = 0; j < DC; ++j) off[j] = (w[j >> 1] >> ((j & 1) * 16)) & 0xffffu;
-                    if (k > 0) {
-                        const unsigned base = is_x ? 0u : (unsigned)g.E_x;  // slot base + v * DV + j belongs to qubit v
-                        unsigned par = sy;
-#pragma unroll
-                        for (int j = 0; j < DC; ++j) par ^= ((unsigned)dec[((off[j] >> 2) - base) / DV] >> sh) & 1u;
-                        if (par) stamp[cwl] = step;
-                    }
+                    row_unpack(g, c, off);
+                    if (k > 0 && parity_regular<DV>(g, dec, off, is_x, sy)) stamp[cwl] = step;
                     if (k < T) cn_minsum_regular<DC>(msg, off, DC, sy, a.factor);
                 } else {
                     const int c0 = g.cptr[c], deg = g.cptr[c + 1] - c0;
-                    if (k > 0) {
-                        unsigned par = sy;
-                        for (int j = 0; j < deg; ++j) par ^= ((unsigned)dec[g.cvn[c0 + j]] >> sh) & 1u;
-                        if (par) stamp[cwl] = step;
-                    }
+                    if (k > 0 && parity_csr(g, dec, c0, deg, is_x, sy)) stamp[cwl] = step;
                     if (k < T) cn_update<FGNN_CN_MINSUM, PhiGnn>(msg, g.cslot + c0, deg, sy, a.factor);
                 }
             }
@@ -232,8 +163,11 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_
                     int part = 0;
                     for (int v = lane; v < n; v += a.tpc) {
                         const int d = dec[v];
-                        if (d) part += relay4_weight(d, lch ? lch[v] : a.llr_const, lch ? lch[n + v] : a.llr_const,
-                                                     lch ? lch[2 * n + v] : a.llr_const);
+                        if (d) {
+                            float lx, ly, lz;
+                            rows.llrs(n, v, a.llr_const, lx, ly, lz);
+                            part += relay4_weight(d, lx, ly, lz);
+                        }
                     }
                     if (part) atomicAdd(&wacc[cwl], part);
                     pending = true;
@@ -254,12 +188,6 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_
     }
 }
 
-template <int DV, int DC>
-int launch(const fgnn_graph* g, const Relay4Args& a, const LaunchGeom& L, size_t lds_bytes, hipStream_t st)
-{
-    return fgnn_launch(relay4_kernel<DV, DC>, dim3(L.blocks), dim3(L.threads), lds_bytes, st, g->d, a);
-}
-
 }  // namespace
 
 extern "C" int fgnn_relay4_decode(const fgnn_graph* g, int cn_type, float normalization_factor, int pre_iter, int num_legs, int leg_iter,
@@ -275,40 +203,22 @@ extern "C" int fgnn_relay4_decode(const fgnn_graph* g, int cn_type, float normal
     if (!gamma) return fgnn_fail(FGNN_ERR_ARG, "gamma is NULL");
     if (!x_hat || !z_hat || !stats) return fgnn_fail(FGNN_ERR_ARG, "no output buffer");
     FGNN_DEVICE_GUARD(g->device);
-    LaunchGeom L = fgnn_geom(g, B);
+    const LaunchGeom L = fgnn_geom(g, B);
     Relay4Args a;
-    a.B = B;
+    // the step after a codeword's last weighs its last decision
+    step_args_fill(a, L, B, pre_iter, num_legs - 1, leg_iter, llr_ch, llr_const, synd_x, synd_z, x_hat, z_hat, stats);
     a.pre_iter = pre_iter;
     a.num_legs = num_legs;
     a.leg_iter = leg_iter;
     a.stop_nconv = stop_nconv;
-    // a codeword takes T + 1 steps per leg; one more step weighs its last decision
-    const long long steps = (long long)pre_iter + 1 + (long long)(num_legs - 1) * ((long long)leg_iter + 1) + 1;
-    a.max_steps = (int)std::min<long long>(steps, INT_MAX - 1);
-    a.tpc = L.tpc;
-    a.cpb = L.cpb;
     a.factor = normalization_factor;
-    a.llr_const = llr_const;
     a.gamma = gamma;
-    a.llr_ch = llr_ch;
-    a.synd_x = synd_x;
-    a.synd_z = synd_z;
-    a.x_hat = x_hat;
-    a.z_hat = z_hat;
-    a.stats = stats;
-    // per codeword: E messages, 3n posteriors and n decision bytes, each rounded up to 4 floats; per workgroup: stamp and wacc per
-    // codeword, ndone
-    const size_t m_off = ((size_t)g->d.E + 3) & ~(size_t)3;
-    const size_t d_off = m_off + (((size_t)3 * g->d.n + 3) & ~(size_t)3);
-    const size_t per_cw = d_off + ((((size_t)g->d.n + 3) / 4 + 3) & ~(size_t)3);
-    const size_t lds_bytes = per_cw * sizeof(float) * (size_t)L.cpb + (((size_t)2 * L.cpb + 1 + 3) & ~(size_t)3) * sizeof(int);
-    if (lds_bytes > FGNN_LDS_BUDGET)
-        return fgnn_fail(FGNN_ERR_ARG, "code too large for the LDS-resident Relay-BP4 kernel: " + std::to_string(lds_bytes) +
-                                           " bytes of LDS per workgroup, the limit is " + std::to_string(FGNN_LDS_BUDGET));
+    // per codeword: E messages, 3n posteriors and n decision bytes; per workgroup: stamp and wacc per codeword, ndone
+    const size_t m_off = lds_round4(g->d.E), d_off = m_off + lds_round4((size_t)3 * g->d.n);
+    size_t lds_bytes;
+    if (int err = step_lds_bytes(a, "Relay-BP4", d_off + lds_bytes_as_floats(g->d.n), 0, 2 * L.cpb + 1, &lds_bytes)) return err;
     a.m_off = (int)m_off;
     a.d_off = (int)d_off;
-    a.lds_per_cw = (int)per_cw;
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    if (g->d.cslot16 && !g->force_generic && g->d.dvx == 3 && g->d.dvz == 3 && g->d.dc == 6) return launch<3, 6>(g, a, L, lds_bytes, st);
-    return launch<0, 0>(g, a, L, lds_bytes, st);
+    const auto kernel = step_regular_336(g) ? relay4_kernel<3, 6> : relay4_kernel<0, 0>;
+    return fgnn_launch(kernel, dim3(L.blocks), dim3(L.threads), lds_bytes, static_cast<hipStream_t>(stream), g->d, a);
 }

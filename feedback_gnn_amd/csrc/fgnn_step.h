@@ -1,0 +1,304 @@
+// fgnn_step.h — the frame of the step-loop BP4 decoders: bp4gd_kernel (fgnn_bp4gd.hip), bp4fb_kernel (fgnn_bp4fb.hip), mbp4_kernel
+// (fgnn_mbp4.hip), dsbp4_kernel (fgnn_dsbp4.hip) and relay4_kernel (fgnn_relay4.hip).
+//
+// The five kernels keep several codewords in the LDS of a workgroup and walk each through workgroup steps of one qubit phase, one
+// check phase and a control section.  What is the same in all of them has its one statement here:
+//   StepCw / StepRows / StepSynd   which codeword a thread works on, the codeword's input rows, its syndrome bits staged in a register
+//   QubitSlots<DV>                 a qubit's message slots: pre-clear, fetch with the sums Sz and Sx, store through the kernel's edge rule
+//   row_unpack / parity_*          a check's packed row, and the parity of the decisions over a check's qubits
+//   step_write_decisions / step_finish   dec -> x_hat | z_hat, the four stats words and ndone
+// and on the host StepArgs (the head of every kernel's argument struct), the LDS arithmetic, the LDS refusal and the dispatch over
+// (check rule, regular 3-3-6).  Each kernel keeps its own step loop, barriers, control section, LDS order, waves-per-SIMD value and
+// whatever makes it that decoder.  Every float operation stays where it was: the sums run hz before hx, each ascending from 0.
+#ifndef FGNN_STEP_H
+#define FGNN_STEP_H
+
+#include <algorithm>
+#include <climits>
+#include <type_traits>
+
+#include "fgnn_internal.h"
+#include "fgnn_math.h"
+#include "fgnn_vn.h"
+
+// ---------------------------------------------------------------------------------------------
+// Host side
+// ---------------------------------------------------------------------------------------------
+
+// what every step-loop kernel is told; a kernel's own argument struct derives from it and is passed by value
+struct StepArgs {
+    int B, tpc, cpb, lds_per_cw, d_off, max_steps;  // d_off: the dec bytes of a codeword, in floats from its msg
+    float llr_const;
+    const float* llr_ch;     // [B,3,n] or null
+    const uint8_t* synd_x;   // [B,m_x] or null (all-zero syndrome)
+    const uint8_t* synd_z;   // [B,m_z] or null
+    uint8_t* x_hat;          // [B,n]
+    uint8_t* z_hat;          // [B,n]
+    int32_t* stats;          // [B,4]
+};
+
+// a codeword takes T + 1 steps per run (round, attempt, leg) of T check updates: the first run of pre_iter, `later` more of `iter`;
+// one more step lets the workgroup see its last codeword finished
+inline void step_args_fill(StepArgs& a, const LaunchGeom& L, int B, int pre_iter, long long later, int iter, const float* llr_ch,
+                           float llr_const, const uint8_t* synd_x, const uint8_t* synd_z, uint8_t* x_hat, uint8_t* z_hat, int32_t* stats)
+{
+    const long long steps = (long long)pre_iter + 1 + later * ((long long)iter + 1) + 1;
+    a.B = B;
+    a.tpc = L.tpc;
+    a.cpb = L.cpb;
+    a.max_steps = (int)std::min<long long>(steps, INT_MAX - 1);
+    a.llr_const = llr_const;
+    a.llr_ch = llr_ch;
+    a.synd_x = synd_x;
+    a.synd_z = synd_z;
+    a.x_hat = x_hat;
+    a.z_hat = z_hat;
+    a.stats = stats;
+}
+
+// LDS areas are counted in floats and rounded up to 4 of them; an area of bytes is counted as the floats that hold it
+inline size_t lds_round4(size_t floats) { return (floats + 3) & ~(size_t)3; }
+inline size_t lds_bytes_as_floats(size_t bytes) { return lds_round4((bytes + 3) / 4); }
+
+// the LDS of a launch: per_cw floats for each of the cpb codewords, `table_floats` floats and `words` ints per workgroup.  Sets
+// a.lds_per_cw; a launch over the budget is refused under the decoder's name
+inline int step_lds_bytes(StepArgs& a, const char* decoder, size_t per_cw, size_t table_floats, size_t words, size_t* lds_bytes)
+{
+    *lds_bytes = per_cw * sizeof(float) * (size_t)a.cpb + table_floats * sizeof(float) + lds_round4(words) * sizeof(int);
+    if (*lds_bytes > FGNN_LDS_BUDGET)
+        return fgnn_fail(FGNN_ERR_ARG, std::string("code too large for the LDS-resident ") + decoder + " kernel: " + std::to_string(*lds_bytes) +
+                                           " bytes of LDS per workgroup, the limit is " + std::to_string(FGNN_LDS_BUDGET));
+    a.lds_per_cw = (int)per_cw;
+    return FGNN_OK;
+}
+
+// the checks every CN_TYPE decoder begins with
+inline int step_check_args(const fgnn_graph* g, int cn_type, int B)
+{
+    if (!g) return fgnn_fail(FGNN_ERR_ARG, "graph is NULL");
+    if (g->host_only) return fgnn_fail(FGNN_ERR_ARG, "a host-only graph cannot decode");
+    if (cn_type < 0 || cn_type > 2) return fgnn_fail(FGNN_ERR_ARG, "Unknown node type.");  // decoding_q.py:107
+    if (B < 0) return fgnn_fail(FGNN_ERR_ARG, "B must be >= 0");
+    return FGNN_OK;
+}
+
+// the graphs the (3,3,6) instantiations run: (3,3,6)-regular with packed check rows, unless the tests force the loop
+inline bool step_regular_336(const fgnn_graph* g)
+{
+    return g->d.cslot16 && !g->force_generic && g->d.dvx == 3 && g->d.dvz == 3 && g->d.dc == 6;
+}
+
+// kernel<CN_TYPE, DV, DC> of a launch: boxplus and boxplus-phi run the loop, min-sum the (3,3,6) rows where the graph has them.
+// `launch` is called with the three values as std::integral_constant arguments.
+template <typename LAUNCH>
+int step_dispatch(const fgnn_graph* g, int cn_type, LAUNCH launch)
+{
+    using std::integral_constant;
+    const integral_constant<int, 0> loop;
+    switch (cn_type) {
+    case FGNN_CN_BOXPLUS: return launch(integral_constant<int, FGNN_CN_BOXPLUS>(), loop, loop);
+    case FGNN_CN_BOXPLUS_PHI: return launch(integral_constant<int, FGNN_CN_BOXPLUS_PHI>(), loop, loop);
+    default: break;
+    }
+    if (step_regular_336(g)) return launch(integral_constant<int, FGNN_CN_MINSUM>(), integral_constant<int, 3>(), integral_constant<int, 6>());
+    return launch(integral_constant<int, FGNN_CN_MINSUM>(), loop, loop);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Device side
+// ---------------------------------------------------------------------------------------------
+
+// the codeword of a thread: cwl-th of the workgroup, b-th of the batch (active iff b < B), lane of its tpc threads; nact = the
+// workgroup's active codewords
+struct StepCw {
+    int cwl, lane, b, nact;
+    bool active;
+    __device__ __forceinline__ StepCw(const StepArgs& a)
+    {
+        cwl = threadIdx.x / a.tpc;
+        lane = threadIdx.x - cwl * a.tpc;
+        b = blockIdx.x * a.cpb + cwl;
+        active = b < a.B;
+        nact = min(a.cpb, a.B - (int)blockIdx.x * a.cpb);
+    }
+};
+
+// the input rows of a thread's codeword (row 0 for an inactive one, which reads nothing), one pointer each
+struct StepRows {
+    size_t bb;
+    const float* lch;
+    const uint8_t* sx;
+    const uint8_t* sz;
+    __device__ __forceinline__ StepRows(const GraphDev& g, const StepArgs& a, const StepCw& cw)
+    {
+        bb = cw.active ? (size_t)cw.b : 0;
+        lch = a.llr_ch ? a.llr_ch + bb * 3 * g.n : nullptr;
+        sx = a.synd_x ? a.synd_x + bb * g.m_x : nullptr;
+        sz = a.synd_z ? a.synd_z + bb * g.m_z : nullptr;
+    }
+    // syndrome bit of combined check c (hx rows first)
+    __device__ __forceinline__ unsigned synd_of(const GraphDev& g, const int c) const
+    {
+        const uint8_t* s = c < g.m_x ? sx : sz;
+        return s ? (s[c < g.m_x ? c : c - g.m_x] & 1u) : 0u;
+    }
+    // channel LLRs of qubit v, order X, Y, Z
+    __device__ __forceinline__ void llrs(const int n, const int v, const float llr_const, float& lx, float& ly, float& lz) const
+    {
+        lx = lch ? lch[v] : llr_const;
+        ly = lch ? lch[n + v] : llr_const;
+        lz = lch ? lch[2 * n + v] : llr_const;
+    }
+};
+
+// the syndrome bits of a lane's checks c = lane, lane + tpc, ..: bit i of a register where a lane has 32 checks at the most, else
+// read again from the rows.  ROWS: StepRows, or a kernel's own rows with the same synd_of
+struct StepSynd {
+    bool in_reg;
+    unsigned bits;
+    template <typename ROWS>
+    __device__ __forceinline__ StepSynd(const GraphDev& g, const ROWS& rows, const StepCw& cw, const int tpc)
+    {
+        in_reg = (g.m + tpc - 1) / tpc <= 32;
+        bits = 0;
+        if (cw.active && in_reg) {
+            int i = 0;
+            for (int c = cw.lane; c < g.m; c += tpc, ++i) bits |= rows.synd_of(g, c) << i;
+        }
+    }
+    // of the lane's i-th check, which is c
+    template <typename ROWS>
+    __device__ __forceinline__ unsigned at(const GraphDev& g, const ROWS& rows, const int i, const int c) const
+    {
+        return in_reg ? ((bits >> i) & 1u) : rows.synd_of(g, c);
+    }
+};
+
+// The message slots of qubit v in the codeword's msg: the hx run [x0, x1) at px, the hz run [z0, z1) at pz.  DV > 0: a
+// (DV,DV,.)-regular graph, the messages are fetched into registers once; DV = 0: runtime degrees, they are read where they are used.
+// Only the fetch and the store differ between the two.  The runs are kept by their ends, as vn_sums takes them, and the two pointers
+// are formed once: with degrees kept instead, or the pointers formed again in the store, bp4gd_kernel's boxplus-phi loop takes 75
+// VGPRs instead of 72 and relay4_kernel<3,6> 89 instead of 88.
+template <int DV>
+struct QubitSlots {
+    static constexpr bool REGULAR = DV > 0;
+    float* msg;
+    float* px;
+    float* pz;
+    int x0, z0, x1, z1;
+    float mx[REGULAR ? DV : 1], mz[REGULAR ? DV : 1];
+
+    __device__ __forceinline__ QubitSlots(const GraphDev& g, float* msg_, const int v) : msg(msg_)
+    {
+        x0 = REGULAR ? v * DV : g.vptr_x[v];
+        z0 = REGULAR ? g.E_x + v * DV : g.vptr_z[v];
+        x1 = REGULAR ? x0 + DV : g.vptr_x[v + 1];
+        z1 = REGULAR ? z0 + DV : g.vptr_z[v + 1];
+        px = msg + x0;
+        pz = msg + z0;
+    }
+    // a restarting attempt starts from zero messages: the slots of a qubit are its owner's in the qubit phase
+    __device__ __forceinline__ void clear()
+    {
+        const int dx = x1 - x0, dz = z1 - z0;
+        for (int j = 0; j < dx; ++j) px[j] = 0.0f;
+        for (int j = 0; j < dz; ++j) pz[j] = 0.0f;
+    }
+    // the qubit's c->v messages and their sums, the hz run before the hx run, each ascending.  live = false: no check update has
+    // written the slots yet and the messages count as zeros, whatever the slots hold
+    __device__ __forceinline__ void fetch(float& Sz, float& Sx, const bool live = true)
+    {
+        Sz = 0.0f;
+        Sx = 0.0f;
+        if constexpr (REGULAR) {
+            if (live) {
+#pragma unroll
+                for (int j = 0; j < DV; ++j) { mz[j] = pz[j]; Sz = Sz + mz[j]; }
+#pragma unroll
+                for (int j = 0; j < DV; ++j) { mx[j] = px[j]; Sx = Sx + mx[j]; }
+            } else {
+#pragma unroll
+                for (int j = 0; j < DV; ++j) mz[j] = mx[j] = 0.0f;
+            }
+        } else if (live) {
+            vn_sums(msg, z0, z1, x0, x1, Sz, Sx);
+        }
+    }
+    // the v->c messages from the totals X, Y, Z: edge(num, A, Y, mu) is the kernel's edge rule (vn_edge, vn_edge_own of fgnn_vn.h),
+    // mu the edge's own c->v message as fetched
+    template <typename EDGE>
+    __device__ __forceinline__ void store(const float X, const float Y, const float Z, EDGE edge, const bool live = true)
+    {
+        const float numx = VnMath::softplus(-X);
+        const float numz = VnMath::softplus(-Z);
+        if constexpr (REGULAR) {
+#pragma unroll
+            for (int j = 0; j < DV; ++j) px[j] = edge(numx, Z, Y, mx[j]);
+#pragma unroll
+            for (int j = 0; j < DV; ++j) pz[j] = edge(numz, X, Y, mz[j]);
+        } else {
+            const int dx = x1 - x0, dz = z1 - z0;
+            for (int j = 0; j < dx; ++j) px[j] = edge(numx, Z, Y, live ? px[j] : 0.0f);
+            for (int j = 0; j < dz; ++j) pz[j] = edge(numz, X, Y, live ? pz[j] : 0.0f);
+        }
+    }
+};
+
+// the BYTE offsets of check c's slots from its packed row of g.cslot16
+template <int DC>
+__device__ __forceinline__ void row_unpack(const GraphDev& g, const int c, unsigned (&off)[DC])
+{
+    const uint4 pk = reinterpret_cast<const uint4*>(g.cslot16)[c];
+    const unsigned w[4] = {pk.x, pk.y, pk.z, pk.w};
+#pragma unroll
+    for (int j = 0; j < DC; ++j) off[j] = (w[j >> 1] >> ((j & 1) * 16)) & 0xffffu;
+}
+
+// the qubit of a slot of a (DV,DV,.)-regular graph: slot base + v * DV + j belongs to qubit v, base = 0 (hx) or E_x (hz)
+template <int DV>
+__device__ __forceinline__ unsigned row_qubit(const unsigned byte_off, const unsigned base)
+{
+    return ((byte_off >> 2) - base) / DV;
+}
+__device__ __forceinline__ unsigned row_base(const GraphDev& g, const bool is_x) { return is_x ? 0u : (unsigned)g.E_x; }
+
+// parity of the decisions dec over a check's qubits, starting from `par`: hx rows test z_hat (bit 1 of the decision), hz rows x_hat
+// (bit 0).  On the unpacked row of a regular graph, and on the CSR row [c0, c0 + deg) of g.cvn
+template <int DV, int DC>
+__device__ __forceinline__ unsigned parity_regular(const GraphDev& g, const uint8_t* dec, const unsigned (&off)[DC], const bool is_x, unsigned par)
+{
+    const int sh = is_x ? 1 : 0;
+    const unsigned base = row_base(g, is_x);
+#pragma unroll
+    for (int j = 0; j < DC; ++j) par ^= ((unsigned)dec[row_qubit<DV>(off[j], base)] >> sh) & 1u;
+    return par;
+}
+__device__ __forceinline__ unsigned parity_csr(const GraphDev& g, const uint8_t* dec, const int c0, const int deg, const bool is_x, unsigned par)
+{
+    const int sh = is_x ? 1 : 0;
+    for (int j = 0; j < deg; ++j) par ^= ((unsigned)dec[g.cvn[c0 + j]] >> sh) & 1u;
+    return par;
+}
+
+// the decisions of a codeword into row `row` of x_hat and z_hat
+__device__ __forceinline__ void step_write_decisions(const StepArgs& a, const uint8_t* dec, const size_t row, const int n, const int lane)
+{
+    for (int v = lane; v < n; v += a.tpc) {
+        const unsigned d = dec[v];
+        a.x_hat[row * n + v] = (uint8_t)(d & 1u);
+        a.z_hat[row * n + v] = (uint8_t)(d >> 1);
+    }
+}
+
+// one thread of a finished codeword: its four stats words, and the workgroup counts it
+__device__ __forceinline__ void step_finish(const StepArgs& a, const size_t row, const bool sat, const int r, const int its, const int k, int* ndone)
+{
+    int32_t* st = a.stats + row * 4;
+    st[0] = sat ? 1 : 0;
+    st[1] = r;
+    st[2] = its;
+    st[3] = k;
+    atomicAdd(ndone, 1);
+}
+
+#endif
