@@ -7,6 +7,7 @@ import weakref
 import numpy as np
 import torch
 
+from ._frontend import ShardedModel, bsc_logit, depolarizing_llr
 from ._lib import ROWS_LX, ROWS_LZ
 from .feedback_gnn import Pauli
 
@@ -175,7 +176,7 @@ def _improved(chosen):
     return int(hit.sum())
 
 
-class BP4_OSD_Model:
+class BP4_OSD_Model(ShardedModel):
     """``BP4_OSD_Model(code, bp4_decoder, osd_decoder)``; ``model(batch_size, p)`` → ``(zeros_like(ls_hat), ls_hat)`` with
     ``ls_hat[bs, rows(lz)+rows(lx)] = [lz·x_diff ; lx·z_diff]`` (bp_osd.py:159-191).  BP4 runs on every sample with
     ``llr = log(3(1-p)/p)`` (:106); the samples whose estimate misses the syndrome get both halves re-solved by OSD-0 from
@@ -187,21 +188,17 @@ class BP4_OSD_Model:
         self.graph.set_basis(0, code.pivot_hx)
         self.graph.set_basis(1, code.pivot_hz)
         self.channel = Pauli(self.graph, seed=seed)
-        self.rank, self.world_size, self._next = int(rank), int(world_size), 0
+        self._shard(self.channel.seed, rank, world_size)
         self.last_num_osd = 0
         self.last_osd_improved = 0  # processed samples whose OSD winner is not the OSD-0 solution (OSD_Decoder only)
         self._ws = _OsdWorkspace()  # used only for a basis the LDS-resident kernels refuse
 
     def decode(self, batch_size, p):
         B, g, d = int(batch_size), self.graph, self.bp4_decoder
-        first = self._next + self.rank * B
-        self._next += self.world_size * B
-        ex, ez = self.channel(B, float(p), first)
+        ex, ez = self.channel(B, float(p), self._take(B))
         sx, sz = g.syndrome(ex, ez)
-        pf = np.float32(p)
-        L = float(np.log(np.float32(3.0) * (np.float32(1.0) - pf) / pf, dtype=np.float32))
         decode = g.bp4_decode_layered if getattr(d, "schedule", "flooding") == "layered" else g.bp4_decode
-        out = decode(sx, sz, d.num_iter, d.cn_type, d.normalization_factor, llr_const=L, want_logits=False)
+        out = decode(sx, sz, d.num_iter, d.cn_type, d.normalization_factor, llr_const=depolarizing_llr(p), want_logits=False)
         x_hat, z_hat = out["x_hat"], out["z_hat"]
         _, _, flags = g.residual(ex, ez, x_hat, z_hat, want_arrays=False)  # bit 0 = syndrome missed = `err` (:117-120)
         index, nact = g.compact(flags, 1)
@@ -226,7 +223,7 @@ class BP4_OSD_Model:
     call = __call__
 
 
-class BP2_OSD_Model:
+class BP2_OSD_Model(ShardedModel):
     """``BP2_OSD_Model(pcm, pcm_basis, pivot_pcm, logical_pcm, bp2_decoder, osd_decoder)``; ``model(batch_size, p)`` →
     ``(zeros_like(ls_hat), ls_hat[bs, rows(logical_pcm)])`` (bp_osd.py:194-273): BSC(p) noise, binary syndrome BP with soft
     output, OSD-0 on the samples whose estimate misses the syndrome, ``ls_hat = logical_pcm·(noise xor estimate)``."""
@@ -236,7 +233,7 @@ class BP2_OSD_Model:
         self.pcm, self.logical_pcm, self.bp2_decoder, self.osd_decoder = pcm, logical_pcm, bp2_decoder, osd_decoder
         self.graph = _binary_graph(pcm, logical_pcm, bp2_decoder.graph.device)
         self.graph.set_basis(0, pivot_pcm)
-        self.seed, self.rank, self.world_size, self._next = int(seed), int(rank), int(world_size), 0
+        self._shard(seed, rank, world_size)
         self.last_num_osd = 0
         self.last_osd_improved = 0  # processed samples whose OSD winner is not the OSD-0 solution (OSD_Decoder only)
         self._ws = _OsdWorkspace()  # used only for a basis the LDS-resident kernels refuse
@@ -244,14 +241,10 @@ class BP2_OSD_Model:
     def __call__(self, batch_size, ebno_db=None, **kw):
         p = float(kw.get("p", ebno_db))
         B, g, d = int(batch_size), self.graph, self.bp2_decoder
-        first = self._next + self.rank * B
-        self._next += self.world_size * B
-        pf = np.float32(p)
-        llr_const = float(-np.log((np.float32(1.0) - pf) / pf, dtype=np.float32))  # (:216)
-        noise = g.bsc_noise(self.seed, p, first, B)
+        noise = g.bsc_noise(self.seed, p, self._take(B), B)
         zeros = torch.zeros_like(noise)
         synd, _ = g.syndrome(zeros, noise)
-        soft, noise_hat = g.bp2_decode(synd, d._num_iter, d._cn_type, d._normalization_factor, llr_const=llr_const, B=B)
+        soft, noise_hat = g.bp2_decode(synd, d._num_iter, d._cn_type, d._normalization_factor, llr_const=bsc_logit(p), B=B)  # (:216)
         _, _, flags = g.residual(noise, zeros, noise_hat, zeros, want_arrays=False)
         index, nact = g.compact(flags, 1)
         self.last_num_osd = nact

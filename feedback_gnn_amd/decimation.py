@@ -6,12 +6,12 @@ launch, the messages, decisions and fix marks of a codeword in LDS throughout.  
 inversion.
 """
 import numpy as np
-import torch
 
+from ._frontend import CodeDecoder, DepolarizingBP4Model, alias
 from ._lib import CN_TYPES
 
 
-class BP4GDDecoder:
+class BP4GDDecoder(CodeDecoder):
     """``BP4GDDecoder(code, pre_iter=32, round_iter=4, max_rounds=None, decim_llr=25.0, cn_type="minsum", normalization_factor=0.8)``.
     BP4 runs up to ``pre_iter`` iterations; while no estimate reproduces both syndromes, up to ``max_rounds`` times (``None``: n), the
     free qubit whose decision leads its runner-up by the largest margin is fixed to that decision (its LLRs become ``-decim_llr`` for the
@@ -33,19 +33,10 @@ class BP4GDDecoder:
             raise ValueError("decim_llr must be positive")
         if cn_type not in CN_TYPES:
             raise ValueError("Unknown node type.")
-        self._code = code
         self.pre_iter, self.round_iter = int(pre_iter), int(round_iter)
         self.decim_llr, self.cn_type, self.normalization_factor = float(decim_llr), cn_type, float(normalization_factor)
-        if graph is None:
-            from .graph import TannerGraph
-            graph = TannerGraph(code, stage_one=False, device=device)
-        self.graph = graph
-        self._num_vns, self._num_cns_x, self._num_cns_z = self.graph.n, self.graph.m_x, self.graph.m_z
+        self._attach(code, graph, device)
         self.max_rounds = self._num_vns if max_rounds is None else int(max_rounds)
-        self.last_stats = None
-
-    code = property(lambda self: self._code)
-    num_vns = property(lambda self: self._num_vns)
 
     def decode(self, synd_x, synd_z, llr_ch=None, llr_const=0.0):
         """Estimates and stats for syndromes [B, m_x] / [B, m_z] (uint8, device) under ``llr_ch`` [B, 3, n] or one LLR for everything."""
@@ -54,31 +45,8 @@ class BP4GDDecoder:
         self.last_stats = stats
         return x_hat, z_hat, stats
 
-    def __call__(self, inputs):
-        g = self.graph
-        llr_ch, syndrome_x, syndrome_z = inputs
-        llr_ch = torch.as_tensor(llr_ch, device=g.device)
-        if llr_ch.dtype != torch.float32:
-            raise TypeError('Invalid input dtype.')
-        if llr_ch.shape[-1] != self._num_vns:
-            raise ValueError('Last dimension must be of length n.')
-        if llr_ch.dim() != 3 or llr_ch.shape[1] != 3:
-            raise ValueError('llr_ch must have shape [batch_size, 3, n].')
-        synd = []
-        for s, rows in ((syndrome_x, self._num_cns_x), (syndrome_z, self._num_cns_z)):
-            s = torch.as_tensor(s, device=g.device)
-            if s.dim() != 2 or s.shape[0] != rows:
-                raise ValueError(f"syndrome must have shape [{rows}, batch_size], got {tuple(s.shape)}")
-            if s.shape[1] != llr_ch.shape[0]:
-                raise ValueError('batch sizes of llr_ch and the syndromes differ.')
-            synd.append((s.to(torch.int64) & 1).to(torch.uint8).t().contiguous())
-        x_hat, z_hat, _ = self.decode(synd[0], synd[1], llr_ch=llr_ch.contiguous())
-        return x_hat.to(torch.int64), z_hat.to(torch.float64)
 
-    call = __call__
-
-
-class BP4_GD_Model:
+class BP4_GD_Model(DepolarizingBP4Model):
     """``BP4_GD_Model(code, gd_decoder, p0=None)``; ``model(batch_size, p)`` → ``(s_hat[bs, m_z+m_x], ls_hat[bs,
     rows(hx_perp)+rows(hz_perp)])``, shaped like ``BP4_Relay_Model``: depolarizing noise of rate ``p``, its two syndromes, BP4-GD with
     the prior ``log(3(1-p0)/p0)`` (``p0=None``: of ``p`` itself).  ``s_hat`` is non-zero exactly on the samples for which no solution
@@ -86,30 +54,6 @@ class BP4_GD_Model:
     [bs,4]) and ``last_num_unsolved`` describe that batch.  ``rank`` / ``world_size`` shard the sample stream."""
 
     def __init__(self, code, gd_decoder, p0=None, *, seed=0x5EED, rank=0, world_size=1):
-        self.code, self.gd_decoder, self.p0 = code, gd_decoder, p0
-        self.graph = gd_decoder.graph
-        self.seed, self.rank, self.world_size, self._next = int(seed), int(rank), int(world_size), 0
-        self.last_noise_x = self.last_noise_z = self.last_x_hat = self.last_z_hat = self.last_stats = None
-        self.last_num_unsolved = 0
+        super().__init__(code, gd_decoder, p0, seed=seed, rank=rank, world_size=world_size)
 
-    def next_sample_range(self, batch_size):
-        """``(first, last)``: the half-open range of global sample indices this rank's next batch will draw."""
-        first = self._next + self.rank * int(batch_size)
-        return first, first + int(batch_size)
-
-    def __call__(self, batch_size, ebno_db=None, **kw):
-        p = float(kw.get("p", ebno_db))
-        B, g, d = int(batch_size), self.graph, self.gd_decoder
-        first = self._next + self.rank * B
-        self._next += self.world_size * B
-        p0 = np.float32(p if self.p0 is None else self.p0)
-        llr_const = float(np.log(np.float32(3.0) * (np.float32(1.0) - p0) / p0, dtype=np.float32))
-        ex, ez = g.pauli_noise(self.seed, p, first, B)
-        sx, sz = g.syndrome(ex, ez)
-        x_hat, z_hat, stats = d.decode(sx, sz, llr_const=llr_const)
-        self.last_noise_x, self.last_noise_z, self.last_x_hat, self.last_z_hat, self.last_stats = ex, ez, x_hat, z_hat, stats
-        self.last_num_unsolved = int((stats[:, 0] == 0).sum().item())
-        s_hat, ls_hat, _ = g.residual(ex, ez, x_hat, z_hat, want_arrays=True)
-        return s_hat, ls_hat
-
-    call = __call__
+    gd_decoder = alias("decoder")

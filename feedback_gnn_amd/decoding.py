@@ -9,6 +9,7 @@ import types
 import numpy as np
 import torch
 
+from ._frontend import ShardedModel, bsc_logit
 from ._lib import CN_TYPES
 from .graph import TannerGraph
 
@@ -110,7 +111,7 @@ class LDPCBPDecoder:
     call = __call__
 
 
-class BP_BSC_Model:
+class BP_BSC_Model(ShardedModel):
     """``BP_BSC_Model(pcm, decoder, logical_pcm=None, p0=None)``; ``model(batch_size, p)`` draws BSC(p) noise on the all-zero
     word, decodes its syndrome and returns ``(noise, noise_hat)`` or, with ``logical_pcm``, ``(s_hat[bs,m], ls_hat[bs,rows])``
     (feedback_gnn.py:207-229)."""
@@ -119,17 +120,14 @@ class BP_BSC_Model:
         self.pcm, self.logical_pcm, self.decoder, self.p0 = pcm, logical_pcm, decoder, p0
         self.n = np.asarray(pcm).shape[1]
         self.graph = _binary_graph(pcm, logical_pcm, decoder.graph.device)
-        self.seed, self.rank, self.world_size, self._next = int(seed), int(rank), int(world_size), 0
+        self._shard(seed, rank, world_size)
 
     def __call__(self, batch_size, ebno_db=None, **kw):
         p = float(kw.get("p", ebno_db))
         B = int(batch_size)
         g = self.graph
-        first = self._next + self.rank * B
-        self._next += self.world_size * B
-        p0 = np.float32(p if self.p0 is None else self.p0)
-        llr_const = float(-np.log((np.float32(1.0) - p0) / p0, dtype=np.float32))  # (:210-211)
-        noise = g.bsc_noise(self.seed, p, first, B)
+        llr_const = bsc_logit(p if self.p0 is None else self.p0)  # (:210-211)
+        noise = g.bsc_noise(self.seed, p, self._take(B), B)
         zeros = torch.zeros_like(noise)
         synd, _ = g.syndrome(zeros, noise)  # syndrome_x = hx * noise_z with hx = pcm (:216-217)
         d = self.decoder

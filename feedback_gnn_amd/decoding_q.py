@@ -9,6 +9,7 @@ library's codeword-major layouts.
 import numpy as np
 import torch
 
+from ._frontend import syndrome_in
 from ._lib import CN_TYPES
 from .graph import TannerGraph
 
@@ -115,10 +116,7 @@ class QLDPCBPDecoder:
         return out["x_logit"].t(), out["z_logit"].t()
 
     def _syndrome_in(self, s, rows):
-        s = torch.as_tensor(s, device=self.graph.device)
-        if s.dim() != 2 or s.shape[0] != rows:
-            raise ValueError(f"syndrome must have shape [{rows}, batch_size], got {tuple(s.shape)}")
-        return (s.to(torch.int64) & 1).to(torch.uint8).t().contiguous()
+        return syndrome_in(s, rows, self.graph.device)
 
     def _hard_out_dtypes(self, x_hat, z_hat):
         if self._reference_dtypes:

@@ -250,11 +250,111 @@ class TannerGraph:
     def _new(self, shape, dtype):
         return torch.empty(shape, dtype=dtype, device=self.device)
 
-    # ---- QLDPCBPDecoder.call ---------------------------------------------------------------------
-    def bp4_decode(self, synd_x, synd_z, num_iter, cn_type="boxplus-phi", factor=1.0, llr_ch=None, llr_const=0.0,
-                   msg_init=None, return_msgs=False, want_logits=True):
+    # ---- the input / output frame of the wrappers below: each checks in the order its arguments are listed ----
+    def _opt(self, t, shape, dtype, name):
+        """`_chk` of an input that may be omitted."""
+        return None if t is None else self._chk(t, shape, dtype, name)
+
+    def _opt_any(self, t, dtype, name):
+        """An input of any shape that may be omitted: checked for device and dtype only."""
+        return None if t is None else self._chk(t, tuple(t.shape), dtype, name)
+
+    @staticmethod
+    def _cn(cn_type):
         if cn_type not in CN_TYPES:
             raise ValueError("Unknown node type.")
+        return CN_TYPES[cn_type]
+
+    def _syndromes_in(self, synd_x, synd_z):
+        """(B, synd_x, synd_z) of a call that needs both syndromes."""
+        B = int(synd_x.shape[0])
+        return B, self._chk(synd_x, (B, self.m_x), torch.uint8, "synd_x"), self._chk(synd_z, (B, self.m_z), torch.uint8, "synd_z")
+
+    def _quaternary_in(self, synd_x, synd_z, llr_ch, B, also=(), missing="B is needed when neither syndromes nor llr_ch are given"):
+        """(B, synd_x, synd_z, llr_ch) of a step-loop decoder: each may be None (a syndrome: all-zero; llr_ch: one constant); ``also``
+        are further inputs that can give the batch size: the last one given does, else ``B``, else a ValueError says ``missing``.
+        The checks are written out, not passed through `_opt`: this runs on every decode call."""
+        for t in (synd_x, synd_z, llr_ch, *also):
+            if t is not None:
+                B = int(t.shape[0])
+        if B is None:
+            raise ValueError(missing)
+        if synd_x is not None:
+            synd_x = self._chk(synd_x, (B, self.m_x), torch.uint8, "synd_x")
+        if synd_z is not None:
+            synd_z = self._chk(synd_z, (B, self.m_z), torch.uint8, "synd_z")
+        if llr_ch is not None:
+            llr_ch = self._chk(llr_ch, (B, 3, self.n), torch.float32, "llr_ch")
+        return B, synd_x, synd_z, llr_ch
+
+    def _binary_in(self, synd, llr_ch, B):
+        """(B, synd, llr_ch) of a decoder of the hx graph alone: the syndrome's batch size wins, then ``B``, then llr_ch's."""
+        if synd is not None:
+            B = int(synd.shape[0])
+            synd = self._chk(synd, (B, self.m_x), torch.uint8, "syndrome")
+        if llr_ch is not None:
+            B = int(llr_ch.shape[0]) if B is None else B
+            llr_ch = self._chk(llr_ch, (B, self.n), torch.float32, "llr_ch")
+        return B, synd, llr_ch
+
+    def _gnn_in(self, llr, logit_hx, logit_hz, synd_x, synd_z):
+        """(B, llr, logit_hx, logit_hz, synd_x, synd_z) of the feedback GNN."""
+        B = int(llr.shape[0])
+        return (B, self._chk(llr, (B, 3, self.n), torch.float32, "llr"), self._chk(logit_hx, (B, self.m_x), torch.float32, "logit_hx"),
+                self._chk(logit_hz, (B, self.m_z), torch.float32, "logit_hz"), self._chk(synd_x, (B, self.m_x), torch.uint8, "synd_x"),
+                self._chk(synd_z, (B, self.m_z), torch.uint8, "synd_z"))
+
+    def _residual_in(self, ex, ez, x_hat, z_hat):
+        """(B, ex, ez, x_hat, z_hat): the noise and its estimate, four uint8 [B, n]."""
+        B = int(ex.shape[0])
+        return (B, self._chk(ex, (B, self.n), torch.uint8, "noise_x"), self._chk(ez, (B, self.n), torch.uint8, "noise_z"),
+                self._chk(x_hat, (B, self.n), torch.uint8, "x_hat"), self._chk(z_hat, (B, self.n), torch.uint8, "z_hat"))
+
+    def _gamma_in(self, gamma):
+        """Memory strengths [num_legs, n] float32."""
+        if gamma.dim() != 2 or gamma.shape[0] < 1:
+            raise ValueError("gamma must have shape [num_legs, n]")
+        return self._chk(gamma, (int(gamma.shape[0]), self.n), torch.float32, "gamma")
+
+    @staticmethod
+    def _tables_in(factors, owns):
+        """The per-attempt host tables of `mbp4_decode` / `dsbp4_decode` as flat float32 arrays of one length."""
+        factors = np.ascontiguousarray(np.asarray(factors, dtype=np.float32).reshape(-1))
+        owns = np.ascontiguousarray(np.asarray(owns, dtype=np.float32).reshape(-1))
+        if len(factors) != len(owns):
+            raise ValueError("factors and owns must have the same length")
+        return factors, owns
+
+    def _osd_in(self, side, synd, e_hat, marg, llr_bin, index, chosen=None):
+        """(B, synd, e_hat, marg, llr_bin, index, chosen) of the OSD calls; all but the first two may be None."""
+        B = int(synd.shape[0])
+        synd = self._chk(synd, (B, self.m_x if side == 0 else self.m_z), torch.uint8, "synd")
+        e_hat = self._chk_out(e_hat, (B, self.n), torch.uint8, "e_hat")
+        marg = self._opt_any(marg, torch.float32, "marg")
+        llr_bin = self._opt_any(llr_bin, torch.float32, "llr_bin")
+        index = self._opt_any(index, torch.int32, "index")
+        if chosen is not None:
+            chosen = self._chk_out(chosen, (B,), torch.int32, "chosen")
+        return B, synd, e_hat, marg, llr_bin, index, chosen
+
+    def _chk_counter(self, t, shape, name):
+        """A device counter array the library adds to in place: contiguous int64 (or uint64) of ``shape``."""
+        if t.device != self.device or t.dtype not in (torch.int64, torch.uint64) or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous int64{list(shape)} on {self.device}")
+
+    def _new_xzs(self, B):
+        """The outputs of a step-loop decoder: x_hat, z_hat [B, n] uint8 and stats [B, 4] int32."""
+        return self._new((B, self.n), torch.uint8), self._new((B, self.n), torch.uint8), self._new((B, 4), torch.int32)
+
+    def _noise_out(self, B, out):
+        """(ex, ez) [B, n] uint8 of a noise call: new ones, or the caller's ``out=(ex, ez)`` checked as in-place buffers."""
+        if out is None:
+            return self._new((B, self.n), torch.uint8), self._new((B, self.n), torch.uint8)
+        return self._chk_out(out[0], (B, self.n), torch.uint8, "noise_x"), self._chk_out(out[1], (B, self.n), torch.uint8, "noise_z")
+
+    # ---- QLDPCBPDecoder.call ---------------------------------------------------------------------
+    def _bp4_in(self, synd_x, synd_z, llr_ch, msg_init):
+        """(B, synd_x, synd_z, llr_ch, msg_init_x, msg_init_z) of `bp4_decode`, `bp4_decode_layered` and `bp4_decode_trace`."""
         B = int(synd_x.shape[0])
         synd_x = self._chk(synd_x, (B, self.m_x), torch.uint8, "synd_x")
         synd_z = self._chk(synd_z, (B, self.m_z), torch.uint8, "synd_z")
@@ -264,6 +364,12 @@ class TannerGraph:
         if msg_init is not None:
             mix = self._chk(msg_init[0], (B, self.E_x), torch.float32, "msg_init_x")
             miz = self._chk(msg_init[1], (B, self.E_z), torch.float32, "msg_init_z")
+        return B, synd_x, synd_z, llr_ch, mix, miz
+
+    def _bp4_run(self, fn, synd_x, synd_z, num_iter, cn_type, factor, llr_ch, llr_const, msg_init, return_msgs, want_logits):
+        """The body of `bp4_decode` and `bp4_decode_layered`: ``fn`` is `fgnn_bp4_decode` or `fgnn_bp4_decode_layered` (one signature)."""
+        cn = self._cn(cn_type)
+        B, synd_x, synd_z, llr_ch, mix, miz = self._bp4_in(synd_x, synd_z, llr_ch, msg_init)
         llr = self._new((B, 3, self.n), torch.float32)
         xh = self._new((B, self.n), torch.uint8)
         zh = self._new((B, self.n), torch.uint8)
@@ -271,13 +377,17 @@ class TannerGraph:
         zl = self._new((B, self.rows_zp), torch.float32) if want_logits else None
         mox = self._new((B, self.E_x), torch.float32) if return_msgs else None
         moz = self._new((B, self.E_z), torch.float32) if return_msgs else None
-        check(_lib.lib().fgnn_bp4_decode(self.handle, CN_TYPES[cn_type], int(num_iter), float(factor), _ptr(llr_ch),
-                                         float(llr_const), _ptr(synd_x), _ptr(synd_z), B, _ptr(mix), _ptr(miz), _ptr(llr),
-                                         _ptr(xh), _ptr(zh), _ptr(xl), _ptr(zl), _ptr(mox), _ptr(moz), _stream(self.device)))
+        check(fn(self.handle, cn, int(num_iter), float(factor), _ptr(llr_ch), float(llr_const), _ptr(synd_x), _ptr(synd_z), B, _ptr(mix),
+                 _ptr(miz), _ptr(llr), _ptr(xh), _ptr(zh), _ptr(xl), _ptr(zl), _ptr(mox), _ptr(moz), _stream(self.device)))
         out = dict(llr=llr, x_hat=xh, z_hat=zh, x_logit=xl, z_logit=zl)
         if return_msgs:
             out["msg_x"], out["msg_z"] = mox, moz
         return out
+
+    def bp4_decode(self, synd_x, synd_z, num_iter, cn_type="boxplus-phi", factor=1.0, llr_ch=None, llr_const=0.0,
+                   msg_init=None, return_msgs=False, want_logits=True):
+        return self._bp4_run(_lib.lib().fgnn_bp4_decode, synd_x, synd_z, num_iter, cn_type, factor, llr_ch, llr_const, msg_init,
+                             return_msgs, want_logits)
 
     # ---- layered (serial) schedule ---------------------------------------------------------------
     def set_layers(self, layer_of=None):
@@ -307,31 +417,8 @@ class TannerGraph:
         """`bp4_decode` in the layered (serial) schedule (fgnn_bp4_decode_layered): the checks are updated layer by layer, every update
         sees the results of the layers before it.  Same keywords and the same result dict; a graph without a layering gets the greedy
         one (`set_layers`)."""
-        if cn_type not in CN_TYPES:
-            raise ValueError("Unknown node type.")
-        B = int(synd_x.shape[0])
-        synd_x = self._chk(synd_x, (B, self.m_x), torch.uint8, "synd_x")
-        synd_z = self._chk(synd_z, (B, self.m_z), torch.uint8, "synd_z")
-        if llr_ch is not None:
-            llr_ch = self._chk(llr_ch, (B, 3, self.n), torch.float32, "llr_ch")
-        mix = miz = None
-        if msg_init is not None:
-            mix = self._chk(msg_init[0], (B, self.E_x), torch.float32, "msg_init_x")
-            miz = self._chk(msg_init[1], (B, self.E_z), torch.float32, "msg_init_z")
-        llr = self._new((B, 3, self.n), torch.float32)
-        xh = self._new((B, self.n), torch.uint8)
-        zh = self._new((B, self.n), torch.uint8)
-        xl = self._new((B, self.rows_xp), torch.float32) if want_logits else None
-        zl = self._new((B, self.rows_zp), torch.float32) if want_logits else None
-        mox = self._new((B, self.E_x), torch.float32) if return_msgs else None
-        moz = self._new((B, self.E_z), torch.float32) if return_msgs else None
-        check(_lib.lib().fgnn_bp4_decode_layered(self.handle, CN_TYPES[cn_type], int(num_iter), float(factor), _ptr(llr_ch),
-                                                 float(llr_const), _ptr(synd_x), _ptr(synd_z), B, _ptr(mix), _ptr(miz), _ptr(llr),
-                                                 _ptr(xh), _ptr(zh), _ptr(xl), _ptr(zl), _ptr(mox), _ptr(moz), _stream(self.device)))
-        out = dict(llr=llr, x_hat=xh, z_hat=zh, x_logit=xl, z_logit=zl)
-        if return_msgs:
-            out["msg_x"], out["msg_z"] = mox, moz
-        return out
+        return self._bp4_run(_lib.lib().fgnn_bp4_decode_layered, synd_x, synd_z, num_iter, cn_type, factor, llr_ch, llr_const, msg_init,
+                             return_msgs, want_logits)
 
     def bp4_decode_trace(self, synd_x, synd_z, num_iter, cn_type="boxplus-phi", factor=1.0, llr_ch=None, llr_const=0.0,
                          msg_init=None, want_tape=False):
@@ -339,17 +426,8 @@ class TannerGraph:
         (fgnn_bp4_decode_trace: the reference's trainable / stage_two return mode, decoding_q.py:743-746).  Returns
         dict(llr, x_hat, z_hat, x_logit [T+1,B,rows0], z_logit [T+1,B,rows1]) and, with ``want_tape``, tape_x [T+1,B,E_x] /
         tape_z [T+1,B,E_z] (the c->v messages before every iteration, the last slot after the last one)."""
-        if cn_type not in CN_TYPES:
-            raise ValueError("Unknown node type.")
-        B, T = int(synd_x.shape[0]), int(num_iter)
-        synd_x = self._chk(synd_x, (B, self.m_x), torch.uint8, "synd_x")
-        synd_z = self._chk(synd_z, (B, self.m_z), torch.uint8, "synd_z")
-        if llr_ch is not None:
-            llr_ch = self._chk(llr_ch, (B, 3, self.n), torch.float32, "llr_ch")
-        mix = miz = None
-        if msg_init is not None:
-            mix = self._chk(msg_init[0], (B, self.E_x), torch.float32, "msg_init_x")
-            miz = self._chk(msg_init[1], (B, self.E_z), torch.float32, "msg_init_z")
+        cn, T = self._cn(cn_type), int(num_iter)
+        B, synd_x, synd_z, llr_ch, mix, miz = self._bp4_in(synd_x, synd_z, llr_ch, msg_init)
         llr = self._new((B, 3, self.n), torch.float32)
         xh = self._new((B, self.n), torch.uint8)
         zh = self._new((B, self.n), torch.uint8)
@@ -357,7 +435,7 @@ class TannerGraph:
         zl = self._new((T + 1, B, self.rows_zp), torch.float32)
         tx = self._new((T + 1, B, self.E_x), torch.float32) if want_tape else None
         tz = self._new((T + 1, B, self.E_z), torch.float32) if want_tape else None
-        check(_lib.lib().fgnn_bp4_decode_trace(self.handle, CN_TYPES[cn_type], T, float(factor), _ptr(llr_ch), float(llr_const),
+        check(_lib.lib().fgnn_bp4_decode_trace(self.handle, cn, T, float(factor), _ptr(llr_ch), float(llr_const),
                                                _ptr(synd_x), _ptr(synd_z), B, _ptr(mix), _ptr(miz), _ptr(llr), _ptr(xh), _ptr(zh),
                                                _ptr(xl), _ptr(zl), _ptr(tx), _ptr(tz), _stream(self.device)))
         out = dict(llr=llr, x_hat=xh, z_hat=zh, x_logit=xl, z_logit=zl)
@@ -367,12 +445,7 @@ class TannerGraph:
 
     # ---- Feedback_GNN.call -------------------------------------------------------------------------
     def feedback_gnn(self, weights, llr, logit_hx, logit_hz, synd_x, synd_z):
-        B = int(llr.shape[0])
-        llr = self._chk(llr, (B, 3, self.n), torch.float32, "llr")
-        logit_hx = self._chk(logit_hx, (B, self.m_x), torch.float32, "logit_hx")
-        logit_hz = self._chk(logit_hz, (B, self.m_z), torch.float32, "logit_hz")
-        synd_x = self._chk(synd_x, (B, self.m_x), torch.uint8, "synd_x")
-        synd_z = self._chk(synd_z, (B, self.m_z), torch.uint8, "synd_z")
+        B, llr, logit_hx, logit_hz, synd_x, synd_z = self._gnn_in(llr, logit_hx, logit_hz, synd_x, synd_z)
         out = self._new((B, 3, self.n), torch.float32)
         check(_lib.lib().fgnn_feedback_gnn(self.handle, weights.handle, _ptr(llr), _ptr(logit_hx), _ptr(logit_hz),
                                            _ptr(synd_x), _ptr(synd_z), B, _ptr(out), _stream(self.device)))
@@ -419,12 +492,7 @@ class TannerGraph:
     def feedback_gnn_backward(self, weights, llr, logit_hx, logit_hz, synd_x, synd_z, grad_out):
         """Weight gradients (12 tensors, Keras order) of sum(grad_out * Feedback_GNN(...)): the HIP kernel leaves the
         (activation, delta) pairs of the four Dense layers in HBM, the reductions over batch x edges are library GEMMs."""
-        B = int(llr.shape[0])
-        llr = self._chk(llr, (B, 3, self.n), torch.float32, "llr")
-        logit_hx = self._chk(logit_hx, (B, self.m_x), torch.float32, "logit_hx")
-        logit_hz = self._chk(logit_hz, (B, self.m_z), torch.float32, "logit_hz")
-        synd_x = self._chk(synd_x, (B, self.m_x), torch.uint8, "synd_x")
-        synd_z = self._chk(synd_z, (B, self.m_z), torch.uint8, "synd_z")
+        B, llr, logit_hx, logit_hz, synd_x, synd_z = self._gnn_in(llr, logit_hx, logit_hz, synd_x, synd_z)
         grad_out = self._chk(grad_out, (B, 3, self.n), torch.float32, "grad_out")
         if weights.general:
             # any constructor setting (fgnn_feedback_gnn_backward_general): one (input activations, pre-activation delta) pair per Dense
@@ -473,12 +541,7 @@ class TannerGraph:
         """``out=(ex, ez)``: write into the given contiguous uint8 [B, n] tensors (row slices of a larger batch).  ``first_dev`` (device
         int64 / uint64 [1]): the stream position is read on the device, sample b = ``first_dev[0] + first_sample + b``
         (fgnn_pauli_noise_dev: Monte-Carlo loops captured in a hipGraph)."""
-        if out is None:
-            ex = self._new((B, self.n), torch.uint8)
-            ez = self._new((B, self.n), torch.uint8)
-        else:
-            ex = self._chk_out(out[0], (B, self.n), torch.uint8, "noise_x")
-            ez = self._chk_out(out[1], (B, self.n), torch.uint8, "noise_z")
+        ex, ez = self._noise_out(B, out)
         with torch.cuda.device(self.device):  # graph-less entry points run on the current device
             if first_dev is None:
                 check(_lib.lib().fgnn_pauli_noise(int(seed), float(np.float32(p)), int(first_sample), B, self.n, _ptr(ex), _ptr(ez),
@@ -492,24 +555,14 @@ class TannerGraph:
 
     def pauli_noise_xyz(self, seed, px, py, pz, first_sample, B, out=None):
         """Pauli.call for any triple (px, py, pz), pauli.py:98-108 (fgnn_pauli_noise_xyz): the same Philox uniforms as `pauli_noise`."""
-        if out is None:
-            ex = self._new((B, self.n), torch.uint8)
-            ez = self._new((B, self.n), torch.uint8)
-        else:
-            ex = self._chk_out(out[0], (B, self.n), torch.uint8, "noise_x")
-            ez = self._chk_out(out[1], (B, self.n), torch.uint8, "noise_z")
+        ex, ez = self._noise_out(B, out)
         with torch.cuda.device(self.device):
             check(_lib.lib().fgnn_pauli_noise_xyz(int(seed), float(np.float32(px)), float(np.float32(py)), float(np.float32(pz)),
                                                   int(first_sample), B, self.n, _ptr(ex), _ptr(ez), _stream(self.device)))
         return ex, ez
 
     def pauli_noise_wt(self, seed, wt, first_sample, B, out=None):
-        if out is None:
-            ex = self._new((B, self.n), torch.uint8)
-            ez = self._new((B, self.n), torch.uint8)
-        else:
-            ex = self._chk_out(out[0], (B, self.n), torch.uint8, "noise_x")
-            ez = self._chk_out(out[1], (B, self.n), torch.uint8, "noise_z")
+        ex, ez = self._noise_out(B, out)
         with torch.cuda.device(self.device):
             check(_lib.lib().fgnn_pauli_noise_wt(int(seed), int(wt), int(first_sample), B, self.n, _ptr(ex), _ptr(ez),
                                                  _stream(self.device)))
@@ -547,11 +600,7 @@ class TannerGraph:
                                         _stream(self.device)))
 
     def residual(self, ex, ez, x_hat, z_hat, want_arrays=True):
-        B = int(ex.shape[0])
-        ex = self._chk(ex, (B, self.n), torch.uint8, "noise_x")
-        ez = self._chk(ez, (B, self.n), torch.uint8, "noise_z")
-        x_hat = self._chk(x_hat, (B, self.n), torch.uint8, "x_hat")
-        z_hat = self._chk(z_hat, (B, self.n), torch.uint8, "z_hat")
+        B, ex, ez, x_hat, z_hat = self._residual_in(ex, ez, x_hat, z_hat)
         s_hat = self._new((B, self.m_z + self.m_x), torch.uint8) if want_arrays else None
         ls_hat = self._new((B, self.rows_hxp + self.rows_hzp), torch.uint8) if want_arrays else None
         flags = self._new((B,), torch.uint8)
@@ -562,9 +611,7 @@ class TannerGraph:
     def count_flags(self, flags, counts):
         """counts (uint64/int64 [3] on device) += (#flagged, #block errors, #samples)."""
         flags = self._chk(flags, (int(flags.shape[0]),), torch.uint8, "flags")
-        if counts.device != self.device or counts.dtype not in (torch.int64, torch.uint64) or tuple(counts.shape) != (3,) \
-                or not counts.is_contiguous():
-            raise ValueError(f"counts must be a contiguous int64[3] on {self.device}")
+        self._chk_counter(counts, (3,), "counts")
         with torch.cuda.device(self.device):  # fgnn_count_flags takes no graph: it runs on the current device
             check(_lib.lib().fgnn_count_flags(_ptr(flags), int(flags.shape[0]), _ptr(counts), _stream(self.device)))
         return counts
@@ -577,9 +624,8 @@ class TannerGraph:
             raise ValueError("flags must hold a whole number of batches")
         k = B // batch
         flags = self._chk(flags, (B,), torch.uint8, "flags")
-        for t, shape, name in ((counts, (3,), "counts"), (ring, (k, 3), "ring")):
-            if t.device != self.device or t.dtype not in (torch.int64, torch.uint64) or tuple(t.shape) != shape or not t.is_contiguous():
-                raise ValueError(f"{name} must be a contiguous int64{list(shape)} on {self.device}")
+        self._chk_counter(counts, (3,), "counts")
+        self._chk_counter(ring, (k, 3), "ring")
         scratch = self._new((2 * k,), torch.int32)
         with torch.cuda.device(self.device):
             check(_lib.lib().fgnn_count_flags_batches(_ptr(flags), k, batch, _ptr(counts), _ptr(ring), _ptr(scratch),
@@ -608,9 +654,7 @@ class TannerGraph:
         fa = np.asarray(factors, dtype=np.float32)
         ct = np.asarray([CN_TYPES[c] for c in cn_types], dtype=np.int32)
         wh = (C.c_void_p * max(1, num_layers - 1))(*[w.handle for w in weights_list])
-        B = int(synd_x.shape[0])
-        synd_x = self._chk(synd_x, (B, self.m_x), torch.uint8, "synd_x")
-        synd_z = self._chk(synd_z, (B, self.m_z), torch.uint8, "synd_z")
+        B, synd_x, synd_z = self._syndromes_in(synd_x, synd_z)
         if workspace is None:
             workspace = self.sandwich_workspace(B)
         xh = self._new((B, self.n), torch.uint8)
@@ -693,15 +737,7 @@ class TannerGraph:
 
     def osd0(self, side, synd, e_hat, marg=None, llr_bin=None, index=None, nact=0):
         """Overwrite e_hat[b] (uint8 [B,n]) for the listed samples with the OSD-0 solution of side 0 (hx) / 1 (hz)."""
-        B = int(synd.shape[0])
-        synd = self._chk(synd, (B, self.m_x if side == 0 else self.m_z), torch.uint8, "synd")
-        e_hat = self._chk_out(e_hat, (B, self.n), torch.uint8, "e_hat")
-        if marg is not None:
-            marg = self._chk(marg, tuple(marg.shape), torch.float32, "marg")
-        if llr_bin is not None:
-            llr_bin = self._chk(llr_bin, tuple(llr_bin.shape), torch.float32, "llr_bin")
-        if index is not None:
-            index = self._chk(index, tuple(index.shape), torch.int32, "index")
+        B, synd, e_hat, marg, llr_bin, index, _ = self._osd_in(side, synd, e_hat, marg, llr_bin, index)
         check(_lib.lib().fgnn_osd0(self.handle, int(side), _ptr(marg), _ptr(llr_bin), _ptr(synd), B, _ptr(index), int(nact),
                                    _ptr(e_hat), _stream(self.device)))
         return e_hat
@@ -711,17 +747,7 @@ class TannerGraph:
         name of `OSD_METHODS` or its FGNN_OSD_* id, `order` the search depth.  `chosen` (int32 [B], optional) receives the winning
         candidate index of every processed sample (0 = the OSD-0 solution)."""
         method = osd_method_id(method)
-        B = int(synd.shape[0])
-        synd = self._chk(synd, (B, self.m_x if side == 0 else self.m_z), torch.uint8, "synd")
-        e_hat = self._chk_out(e_hat, (B, self.n), torch.uint8, "e_hat")
-        if marg is not None:
-            marg = self._chk(marg, tuple(marg.shape), torch.float32, "marg")
-        if llr_bin is not None:
-            llr_bin = self._chk(llr_bin, tuple(llr_bin.shape), torch.float32, "llr_bin")
-        if index is not None:
-            index = self._chk(index, tuple(index.shape), torch.int32, "index")
-        if chosen is not None:
-            chosen = self._chk_out(chosen, (B,), torch.int32, "chosen")
+        B, synd, e_hat, marg, llr_bin, index, chosen = self._osd_in(side, synd, e_hat, marg, llr_bin, index, chosen)
         check(_lib.lib().fgnn_osd(self.handle, int(side), method, int(order), _ptr(marg), _ptr(llr_bin), _ptr(synd), B, _ptr(index),
                                   int(nact), _ptr(e_hat), _ptr(chosen), _stream(self.device)))
         return e_hat
@@ -763,17 +789,7 @@ class TannerGraph:
         """`osd` (method "osd0": `osd0`) on a device workspace (`fgnn_osd_ws`): any basis with n <= 16384, the same outputs bit for
         bit.  `workspace` (uint8, from `osd_workspace`) sets the slot count; None allocates one with the default slot count."""
         method = osd_method_id(method)
-        B = int(synd.shape[0])
-        synd = self._chk(synd, (B, self.m_x if side == 0 else self.m_z), torch.uint8, "synd")
-        e_hat = self._chk_out(e_hat, (B, self.n), torch.uint8, "e_hat")
-        if marg is not None:
-            marg = self._chk(marg, tuple(marg.shape), torch.float32, "marg")
-        if llr_bin is not None:
-            llr_bin = self._chk(llr_bin, tuple(llr_bin.shape), torch.float32, "llr_bin")
-        if index is not None:
-            index = self._chk(index, tuple(index.shape), torch.int32, "index")
-        if chosen is not None:
-            chosen = self._chk_out(chosen, (B,), torch.int32, "chosen")
+        B, synd, e_hat, marg, llr_bin, index, chosen = self._osd_in(side, synd, e_hat, marg, llr_bin, index, chosen)
         if workspace is None:
             workspace = self.osd_workspace(side, method, order)
         workspace = self._chk_out(workspace, (workspace.numel(),), torch.uint8, "workspace")
@@ -782,11 +798,7 @@ class TannerGraph:
         return e_hat
 
     def residual_rows(self, rows_x, rows_z, ex, ez, x_hat, z_hat):
-        B = int(ex.shape[0])
-        ex = self._chk(ex, (B, self.n), torch.uint8, "noise_x")
-        ez = self._chk(ez, (B, self.n), torch.uint8, "noise_z")
-        x_hat = self._chk(x_hat, (B, self.n), torch.uint8, "x_hat")
-        z_hat = self._chk(z_hat, (B, self.n), torch.uint8, "z_hat")
+        B, ex, ez, x_hat, z_hat = self._residual_in(ex, ez, x_hat, z_hat)
         ls_hat = self._new((B, self._row_count(rows_x) + self._row_count(rows_z)), torch.uint8)
         flags = self._new((B,), torch.uint8)
         check(_lib.lib().fgnn_residual_rows(self.handle, int(rows_x), int(rows_z), _ptr(ex), _ptr(ez), _ptr(x_hat), _ptr(z_hat), B, None,
@@ -799,32 +811,19 @@ class TannerGraph:
     # ---- binary syndrome BP on the hx graph (LDPCBPDecoder, is_syndrome=True) ----------------------------------
     def bp2_decode(self, synd, num_iter, cn_type="boxplus-phi", factor=1.0, llr_ch=None, llr_const=0.0, B=None, want_soft=True,
                    want_hard=True):
-        if cn_type not in CN_TYPES:
-            raise ValueError("Unknown node type.")
-        if synd is not None:
-            B = int(synd.shape[0])
-            synd = self._chk(synd, (B, self.m_x), torch.uint8, "syndrome")
-        if llr_ch is not None:
-            B = int(llr_ch.shape[0]) if B is None else B
-            llr_ch = self._chk(llr_ch, (B, self.n), torch.float32, "llr_ch")
+        cn = self._cn(cn_type)
+        B, synd, llr_ch = self._binary_in(synd, llr_ch, B)
         soft = self._new((B, self.n), torch.float32) if want_soft else None
         hard = self._new((B, self.n), torch.uint8) if want_hard else None
-        check(_lib.lib().fgnn_bp2_decode(self.handle, CN_TYPES[cn_type], int(num_iter), float(factor), _ptr(llr_ch), float(llr_const),
+        check(_lib.lib().fgnn_bp2_decode(self.handle, cn, int(num_iter), float(factor), _ptr(llr_ch), float(llr_const),
                                          _ptr(synd), B, _ptr(soft), _ptr(hard), _stream(self.device)))
         return soft, hard
 
     def relay_decode(self, synd, gamma, pre_iter, leg_iter, stop_nconv, factor=1.0, llr_ch=None, llr_const=0.0, B=None):
         """Relay-BP on the hx graph (`fgnn_relay_decode`): `gamma` [num_legs, n] float32 on the device, one row of memory strengths per
         leg.  Returns `(hard [B,n] uint8, stats [B,4] int32 = found, weight, leg, k)`."""
-        if synd is not None:
-            B = int(synd.shape[0])
-            synd = self._chk(synd, (B, self.m_x), torch.uint8, "syndrome")
-        if llr_ch is not None:
-            B = int(llr_ch.shape[0]) if B is None else B
-            llr_ch = self._chk(llr_ch, (B, self.n), torch.float32, "llr_ch")
-        if gamma.dim() != 2 or gamma.shape[0] < 1:
-            raise ValueError("gamma must have shape [num_legs, n]")
-        gamma = self._chk(gamma, (int(gamma.shape[0]), self.n), torch.float32, "gamma")
+        B, synd, llr_ch = self._binary_in(synd, llr_ch, B)
+        gamma = self._gamma_in(gamma)
         hard = self._new((B, self.n), torch.uint8)
         stats = self._new((B, 4), torch.int32)
         check(_lib.lib().fgnn_relay_decode(self.handle, float(factor), int(pre_iter), int(gamma.shape[0]), int(leg_iter), int(stop_nconv),
@@ -837,28 +836,13 @@ class TannerGraph:
         """Relay-BP4 on both graphs (`fgnn_relay4_decode`): `gamma` [num_legs, n] float32 on the device, one row of memory strengths per
         leg; `llr_ch` [B, 3, n] or one `llr_const` for all three LLRs of every qubit; a syndrome that is None is all-zero.  Returns
         `(x_hat [B,n] uint8, z_hat [B,n] uint8, stats [B,4] int32 = found, weight, leg, k)`."""
-        if cn_type not in CN_TYPES:
-            raise ValueError("Unknown node type.")
-        for s in (synd_x, synd_z, llr_ch):
-            if s is not None:
-                B = int(s.shape[0])
-        if B is None:
-            raise ValueError("B is needed when neither syndromes nor llr_ch are given")
-        if synd_x is not None:
-            synd_x = self._chk(synd_x, (B, self.m_x), torch.uint8, "synd_x")
-        if synd_z is not None:
-            synd_z = self._chk(synd_z, (B, self.m_z), torch.uint8, "synd_z")
-        if llr_ch is not None:
-            llr_ch = self._chk(llr_ch, (B, 3, self.n), torch.float32, "llr_ch")
+        cn = self._cn(cn_type)
+        B, synd_x, synd_z, llr_ch = self._quaternary_in(synd_x, synd_z, llr_ch, B)
         if gamma is not None:
-            if gamma.dim() != 2 or gamma.shape[0] < 1:
-                raise ValueError("gamma must have shape [num_legs, n]")
-            gamma = self._chk(gamma, (int(gamma.shape[0]), self.n), torch.float32, "gamma")
+            gamma = self._gamma_in(gamma)
         num_legs = int(gamma.shape[0]) if gamma is not None else 1
-        xh = self._new((B, self.n), torch.uint8)
-        zh = self._new((B, self.n), torch.uint8)
-        stats = self._new((B, 4), torch.int32)
-        check(_lib.lib().fgnn_relay4_decode(self.handle, CN_TYPES[cn_type], float(factor), int(pre_iter), num_legs, int(leg_iter),
+        xh, zh, stats = self._new_xzs(B)
+        check(_lib.lib().fgnn_relay4_decode(self.handle, cn, float(factor), int(pre_iter), num_legs, int(leg_iter),
                                             int(stop_nconv), _ptr(gamma), _ptr(llr_ch), float(llr_const), _ptr(synd_x), _ptr(synd_z), B,
                                             _ptr(xh), _ptr(zh), _ptr(stats), _stream(self.device)))
         return xh, zh, stats
@@ -869,24 +853,11 @@ class TannerGraph:
         n) rounds that fix the free qubit of largest margin to its decision (LLR magnitude `decim_llr`) and run up to `round_iter`
         iterations more; `llr_ch` [B, 3, n] or one `llr_const` for all three LLRs of every qubit; a syndrome that is None is all-zero.
         Returns `(x_hat [B,n] uint8, z_hat [B,n] uint8, stats [B,4] int32 = found, qubits fixed, iterations, k of the last test)`."""
-        if cn_type not in CN_TYPES:
-            raise ValueError("Unknown node type.")
-        for s in (synd_x, synd_z, llr_ch):
-            if s is not None:
-                B = int(s.shape[0])
-        if B is None:
-            raise ValueError("B is needed when neither syndromes nor llr_ch are given")
-        if synd_x is not None:
-            synd_x = self._chk(synd_x, (B, self.m_x), torch.uint8, "synd_x")
-        if synd_z is not None:
-            synd_z = self._chk(synd_z, (B, self.m_z), torch.uint8, "synd_z")
-        if llr_ch is not None:
-            llr_ch = self._chk(llr_ch, (B, 3, self.n), torch.float32, "llr_ch")
+        cn = self._cn(cn_type)
+        B, synd_x, synd_z, llr_ch = self._quaternary_in(synd_x, synd_z, llr_ch, B)
         max_rounds = self.n if max_rounds is None else int(max_rounds)
-        xh = self._new((B, self.n), torch.uint8)
-        zh = self._new((B, self.n), torch.uint8)
-        stats = self._new((B, 4), torch.int32)
-        check(_lib.lib().fgnn_bp4gd_decode(self.handle, CN_TYPES[cn_type], float(factor), int(pre_iter), int(round_iter), max_rounds,
+        xh, zh, stats = self._new_xzs(B)
+        check(_lib.lib().fgnn_bp4gd_decode(self.handle, cn, float(factor), int(pre_iter), int(round_iter), max_rounds,
                                            float(decim_llr), _ptr(llr_ch), float(llr_const), _ptr(synd_x), _ptr(synd_z), B, _ptr(xh),
                                            _ptr(zh), _ptr(stats), _stream(self.device)))
         return xh, zh, stats
@@ -899,27 +870,14 @@ class TannerGraph:
         Philox stream of `seed` at the global sample indices `first_sample` .. `first_sample + B - 1`; `llr_ch` [B, 3, n] or one
         `llr_const` for all three LLRs of every qubit; a syndrome that is None is all-zero.  Returns `(x_hat [B,n] uint8, z_hat [B,n]
         uint8, stats [B,4] int32 = found, feedback steps made, iterations, k of the last test)`."""
-        if cn_type not in CN_TYPES:
-            raise ValueError("Unknown node type.")
+        cn = self._cn(cn_type)
         if rule not in _lib.FB_RULES:
             raise ValueError('rule must be "perturb" or "enhanced"')
-        for s in (synd_x, synd_z, llr_ch):
-            if s is not None:
-                B = int(s.shape[0])
-        if B is None:
-            raise ValueError("B is needed when neither syndromes nor llr_ch are given")
-        if synd_x is not None:
-            synd_x = self._chk(synd_x, (B, self.m_x), torch.uint8, "synd_x")
-        if synd_z is not None:
-            synd_z = self._chk(synd_z, (B, self.m_z), torch.uint8, "synd_z")
-        if llr_ch is not None:
-            llr_ch = self._chk(llr_ch, (B, 3, self.n), torch.float32, "llr_ch")
+        B, synd_x, synd_z, llr_ch = self._quaternary_in(synd_x, synd_z, llr_ch, B)
         if not 0 <= int(seed) < 1 << 64 or not 0 <= int(first_sample) < 1 << 64:
             raise ValueError("seed and first_sample must fit 64 unsigned bits")
-        xh = self._new((B, self.n), torch.uint8)
-        zh = self._new((B, self.n), torch.uint8)
-        stats = self._new((B, 4), torch.int32)
-        check(_lib.lib().fgnn_bp4fb_decode(self.handle, _lib.FB_RULES[rule], CN_TYPES[cn_type], float(factor), int(pre_iter),
+        xh, zh, stats = self._new_xzs(B)
+        check(_lib.lib().fgnn_bp4fb_decode(self.handle, _lib.FB_RULES[rule], cn, float(factor), int(pre_iter),
                                            int(attempt_iter), int(max_attempts), float(strength), int(restart), int(seed),
                                            int(first_sample), _ptr(llr_ch), float(llr_const), _ptr(synd_x), _ptr(synd_z), B, _ptr(xh),
                                            _ptr(zh), _ptr(stats), _stream(self.device)))
@@ -934,27 +892,11 @@ class TannerGraph:
         base / alpha_a); with `restart` every attempt after the first starts from zero messages; `llr_ch` [B, 3, n] or one
         `llr_const` for all three LLRs of every qubit; a syndrome that is None is all-zero.  Returns `(x_hat [B,n] uint8, z_hat [B,n]
         uint8, stats [B,4] int32 = found, the attempt of the last test, iterations, k of the last test)`."""
-        if cn_type not in CN_TYPES:
-            raise ValueError("Unknown node type.")
-        factors = np.ascontiguousarray(np.asarray(factors, dtype=np.float32).reshape(-1))
-        owns = np.ascontiguousarray(np.asarray(owns, dtype=np.float32).reshape(-1))
-        if len(factors) != len(owns):
-            raise ValueError("factors and owns must have the same length")
-        for s in (synd_x, synd_z, llr_ch):
-            if s is not None:
-                B = int(s.shape[0])
-        if B is None:
-            raise ValueError("B is needed when neither syndromes nor llr_ch are given")
-        if synd_x is not None:
-            synd_x = self._chk(synd_x, (B, self.m_x), torch.uint8, "synd_x")
-        if synd_z is not None:
-            synd_z = self._chk(synd_z, (B, self.m_z), torch.uint8, "synd_z")
-        if llr_ch is not None:
-            llr_ch = self._chk(llr_ch, (B, 3, self.n), torch.float32, "llr_ch")
-        xh = self._new((B, self.n), torch.uint8)
-        zh = self._new((B, self.n), torch.uint8)
-        stats = self._new((B, 4), torch.int32)
-        check(_lib.lib().fgnn_mbp4_decode(self.handle, CN_TYPES[cn_type], len(factors), factors.ctypes.data, owns.ctypes.data,
+        cn = self._cn(cn_type)
+        factors, owns = self._tables_in(factors, owns)
+        B, synd_x, synd_z, llr_ch = self._quaternary_in(synd_x, synd_z, llr_ch, B)
+        xh, zh, stats = self._new_xzs(B)
+        check(_lib.lib().fgnn_mbp4_decode(self.handle, cn, len(factors), factors.ctypes.data, owns.ctypes.data,
                                           int(pre_iter), int(attempt_iter), int(restart), _ptr(llr_ch), float(llr_const), _ptr(synd_x),
                                           _ptr(synd_z), B, _ptr(xh), _ptr(zh), _ptr(stats), _stream(self.device)))
         return xh, zh, stats
@@ -968,33 +910,18 @@ class TannerGraph:
         estimate reproduces `synd ^ u_hat` on both graphs.  Every other argument is `mbp4_decode`'s.  Returns `(x_hat [B,n], z_hat
         [B,n], u_x_hat [B,m_x], u_z_hat [B,m_z]` uint8, `stats [B,4]` int32 = found, the attempt of the last test, iterations, k of the
         last test)`."""
-        if cn_type not in CN_TYPES:
-            raise ValueError("Unknown node type.")
-        factors = np.ascontiguousarray(np.asarray(factors, dtype=np.float32).reshape(-1))
-        owns = np.ascontiguousarray(np.asarray(owns, dtype=np.float32).reshape(-1))
-        if len(factors) != len(owns):
-            raise ValueError("factors and owns must have the same length")
-        for s in (synd_x, synd_z, llr_ch, synd_llr_x, synd_llr_z):
-            if s is not None:
-                B = int(s.shape[0])
-        if B is None:
-            raise ValueError("B is needed when neither syndromes nor llr_ch nor syndrome LLRs are given")
-        if synd_x is not None:
-            synd_x = self._chk(synd_x, (B, self.m_x), torch.uint8, "synd_x")
-        if synd_z is not None:
-            synd_z = self._chk(synd_z, (B, self.m_z), torch.uint8, "synd_z")
-        if llr_ch is not None:
-            llr_ch = self._chk(llr_ch, (B, 3, self.n), torch.float32, "llr_ch")
-        if synd_llr_x is not None:
-            synd_llr_x = self._chk(synd_llr_x, (B, self.m_x), torch.float32, "synd_llr_x")
-        if synd_llr_z is not None:
-            synd_llr_z = self._chk(synd_llr_z, (B, self.m_z), torch.float32, "synd_llr_z")
+        cn = self._cn(cn_type)
+        factors, owns = self._tables_in(factors, owns)
+        B, synd_x, synd_z, llr_ch = self._quaternary_in(synd_x, synd_z, llr_ch, B, also=(synd_llr_x, synd_llr_z),
+                                                        missing="B is needed when neither syndromes nor llr_ch nor syndrome LLRs are given")
+        synd_llr_x = self._opt(synd_llr_x, (B, self.m_x), torch.float32, "synd_llr_x")
+        synd_llr_z = self._opt(synd_llr_z, (B, self.m_z), torch.float32, "synd_llr_z")
         xh = self._new((B, self.n), torch.uint8)
         zh = self._new((B, self.n), torch.uint8)
         uxh = self._new((B, self.m_x), torch.uint8)
         uzh = self._new((B, self.m_z), torch.uint8)
         stats = self._new((B, 4), torch.int32)
-        check(_lib.lib().fgnn_dsbp4_decode(self.handle, CN_TYPES[cn_type], len(factors), factors.ctypes.data, owns.ctypes.data,
+        check(_lib.lib().fgnn_dsbp4_decode(self.handle, cn, len(factors), factors.ctypes.data, owns.ctypes.data,
                                            int(pre_iter), int(attempt_iter), int(restart), _ptr(llr_ch), float(llr_const), _ptr(synd_x),
                                            _ptr(synd_z), _ptr(synd_llr_x), float(gamma_x), _ptr(synd_llr_z), float(gamma_z), B, _ptr(xh),
                                            _ptr(zh), _ptr(uxh), _ptr(uzh), _ptr(stats), _stream(self.device)))
@@ -1029,9 +956,7 @@ class TannerGraph:
 
     # ---- GNN_BP4 -----------------------------------------------------------------------------------------
     def gnn_bp4_decode(self, weights, synd_x, synd_z, num_iter, return_logits=True, workspace=None):
-        B = int(synd_x.shape[0])
-        synd_x = self._chk(synd_x, (B, self.m_x), torch.uint8, "synd_x")
-        synd_z = self._chk(synd_z, (B, self.m_z), torch.uint8, "synd_z")
+        B, synd_x, synd_z = self._syndromes_in(synd_x, synd_z)
         nbytes = _lib.lib().fgnn_gnnbp4_weights_workspace_bytes(self.handle, weights.handle, B)
         if workspace is None:
             workspace = self._new((nbytes,), torch.uint8)
@@ -1071,9 +996,8 @@ class TannerGraph:
         """GNN_BP4.call with a tape for `gnn_bp4_backward` (fgnn_gnnbp4_forward_tape): the soft syndromes of `gnn_bp4_decode` on the
         same runtime-shaped weight set, bit for bit, and the activation tape (a float32 tensor; pass one to reuse it)."""
         self._gnn_bp4_trainable(weights)
-        B, T = int(synd_x.shape[0]), int(num_iter)
-        synd_x = self._chk(synd_x, (B, self.m_x), torch.uint8, "synd_x")
-        synd_z = self._chk(synd_z, (B, self.m_z), torch.uint8, "synd_z")
+        T = int(num_iter)
+        B, synd_x, synd_z = self._syndromes_in(synd_x, synd_z)
         if tape is None:
             tape = self._new((self.gnn_bp4_tape_bytes(weights, T, B) // 4,), torch.float32)
         xl = self._new((T, B, self.m_z + self.rows_lz), torch.float32)
@@ -1087,13 +1011,10 @@ class TannerGraph:
         """d loss / d (every Dense array of `weights`), summed over the batch, from d loss / d (x_logit_all, z_logit_all) of
         `gnn_bp4_forward_tape` (either may be None) — fgnn_gnnbp4_backward.  Returns one flat float32 tensor in weight-list order."""
         self._gnn_bp4_trainable(weights)
-        B, T = int(synd_x.shape[0]), int(num_iter)
-        synd_x = self._chk(synd_x, (B, self.m_x), torch.uint8, "synd_x")
-        synd_z = self._chk(synd_z, (B, self.m_z), torch.uint8, "synd_z")
-        if grad_x_logit_all is not None:
-            grad_x_logit_all = self._chk(grad_x_logit_all, (T, B, self.m_z + self.rows_lz), torch.float32, "grad_x_logit_all")
-        if grad_z_logit_all is not None:
-            grad_z_logit_all = self._chk(grad_z_logit_all, (T, B, self.m_x + self.rows_lx), torch.float32, "grad_z_logit_all")
+        T = int(num_iter)
+        B, synd_x, synd_z = self._syndromes_in(synd_x, synd_z)
+        grad_x_logit_all = self._opt(grad_x_logit_all, (T, B, self.m_z + self.rows_lz), torch.float32, "grad_x_logit_all")
+        grad_z_logit_all = self._opt(grad_z_logit_all, (T, B, self.m_x + self.rows_lx), torch.float32, "grad_z_logit_all")
         count = C.c_int()
         check(_lib.lib().fgnn_gnnbp4_grad_count(self.handle, weights.handle, C.byref(count)))
         if workspace is None:

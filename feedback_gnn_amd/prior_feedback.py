@@ -11,15 +11,15 @@ The algorithm is stated at `fgnn_bp4fb_decode` in include/fgnn.h; the kernel is 
 attempts of a codeword with its messages, decisions and marks in LDS throughout.  Neither rule needs training or a matrix inversion.
 """
 import numpy as np
-import torch
 
+from ._frontend import CodeDecoder, DepolarizingBP4Model
 from ._lib import CN_TYPES, FB_RULES
 
 # attempt_iter, max_attempts, strength where the constructor gets None: from a CPU prototype on [[882,24]] at p = 0.10
 RULE_DEFAULTS = {"perturb": (8, 40, 2.0), "enhanced": (16, 20, 10.0)}
 
 
-class BP4FeedbackDecoder:
+class BP4FeedbackDecoder(CodeDecoder):
     """``BP4FeedbackDecoder(code, rule="perturb", pre_iter=32, attempt_iter=None, max_attempts=None, strength=None, restart=False,
     cn_type="minsum", normalization_factor=0.8, seed=0x5EED)``.  BP4 runs up to ``pre_iter`` iterations; while no estimate reproduces
     both syndromes, up to ``max_attempts`` times, ``rule`` re-initialises the priors from the channel LLRs and the unsatisfied checks
@@ -48,19 +48,10 @@ class BP4FeedbackDecoder:
             raise ValueError("strength must be finite and cannot be negative")
         if cn_type not in CN_TYPES:
             raise ValueError("Unknown node type.")
-        self._code = code
         self.rule, self.pre_iter, self.attempt_iter, self.max_attempts = rule, int(pre_iter), int(attempt_iter), int(max_attempts)
         self.strength, self.restart, self.seed = float(strength), bool(restart), int(seed)
         self.cn_type, self.normalization_factor = cn_type, float(normalization_factor)
-        if graph is None:
-            from .graph import TannerGraph
-            graph = TannerGraph(code, stage_one=False, device=device)
-        self.graph = graph
-        self._num_vns, self._num_cns_x, self._num_cns_z = self.graph.n, self.graph.m_x, self.graph.m_z
-        self.last_stats = None
-
-    code = property(lambda self: self._code)
-    num_vns = property(lambda self: self._num_vns)
+        self._attach(code, graph, device)
 
     def decode(self, synd_x, synd_z, llr_ch=None, llr_const=0.0, first_sample=0, seed=None):
         """Estimates and stats for syndromes [B, m_x] / [B, m_z] (uint8, device) under ``llr_ch`` [B, 3, n] or one LLR for everything;
@@ -72,31 +63,8 @@ class BP4FeedbackDecoder:
         self.last_stats = stats
         return x_hat, z_hat, stats
 
-    def __call__(self, inputs):
-        g = self.graph
-        llr_ch, syndrome_x, syndrome_z = inputs
-        llr_ch = torch.as_tensor(llr_ch, device=g.device)
-        if llr_ch.dtype != torch.float32:
-            raise TypeError('Invalid input dtype.')
-        if llr_ch.shape[-1] != self._num_vns:
-            raise ValueError('Last dimension must be of length n.')
-        if llr_ch.dim() != 3 or llr_ch.shape[1] != 3:
-            raise ValueError('llr_ch must have shape [batch_size, 3, n].')
-        synd = []
-        for s, rows in ((syndrome_x, self._num_cns_x), (syndrome_z, self._num_cns_z)):
-            s = torch.as_tensor(s, device=g.device)
-            if s.dim() != 2 or s.shape[0] != rows:
-                raise ValueError(f"syndrome must have shape [{rows}, batch_size], got {tuple(s.shape)}")
-            if s.shape[1] != llr_ch.shape[0]:
-                raise ValueError('batch sizes of llr_ch and the syndromes differ.')
-            synd.append((s.to(torch.int64) & 1).to(torch.uint8).t().contiguous())
-        x_hat, z_hat, _ = self.decode(synd[0], synd[1], llr_ch=llr_ch.contiguous())
-        return x_hat.to(torch.int64), z_hat.to(torch.float64)
 
-    call = __call__
-
-
-class BP4_Feedback_Model:
+class BP4_Feedback_Model(DepolarizingBP4Model):
     """``BP4_Feedback_Model(code, decoder, p0=None)``; ``model(batch_size, p)`` → ``(s_hat[bs, m_z+m_x], ls_hat[bs,
     rows(hx_perp)+rows(hz_perp)])``, shaped like ``BP4_GD_Model``: depolarizing noise of rate ``p``, its two syndromes, BP4 with prior
     feedback under the prior ``log(3(1-p0)/p0)`` (``p0=None``: of ``p`` itself).  The feedback draws use the model's ``seed`` and the
@@ -105,31 +73,5 @@ class BP4_Feedback_Model:
     [bs,n]), ``last_stats`` (int32 [bs,4]) and ``last_num_unsolved`` describe that batch.  ``rank`` / ``world_size`` shard the sample
     stream."""
 
-    def __init__(self, code, decoder, p0=None, *, seed=0x5EED, rank=0, world_size=1):
-        self.code, self.decoder, self.p0 = code, decoder, p0
-        self.graph = decoder.graph
-        self.seed, self.rank, self.world_size, self._next = int(seed), int(rank), int(world_size), 0
-        self.last_noise_x = self.last_noise_z = self.last_x_hat = self.last_z_hat = self.last_stats = None
-        self.last_num_unsolved = 0
-
-    def next_sample_range(self, batch_size):
-        """``(first, last)``: the half-open range of global sample indices this rank's next batch will draw."""
-        first = self._next + self.rank * int(batch_size)
-        return first, first + int(batch_size)
-
-    def __call__(self, batch_size, ebno_db=None, **kw):
-        p = float(kw.get("p", ebno_db))
-        B, g, d = int(batch_size), self.graph, self.decoder
-        first = self._next + self.rank * B
-        self._next += self.world_size * B
-        p0 = np.float32(p if self.p0 is None else self.p0)
-        llr_const = float(np.log(np.float32(3.0) * (np.float32(1.0) - p0) / p0, dtype=np.float32))
-        ex, ez = g.pauli_noise(self.seed, p, first, B)
-        sx, sz = g.syndrome(ex, ez)
-        x_hat, z_hat, stats = d.decode(sx, sz, llr_const=llr_const, first_sample=first, seed=self.seed)
-        self.last_noise_x, self.last_noise_z, self.last_x_hat, self.last_z_hat, self.last_stats = ex, ez, x_hat, z_hat, stats
-        self.last_num_unsolved = int((stats[:, 0] == 0).sum().item())
-        s_hat, ls_hat, _ = g.residual(ex, ez, x_hat, z_hat, want_arrays=True)
-        return s_hat, ls_hat
-
-    call = __call__
+    def _decode(self, sx, sz, llr_const, first):
+        return self.decoder.decode(sx, sz, llr_const=llr_const, first_sample=first, seed=self.seed)

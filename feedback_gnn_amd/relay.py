@@ -10,6 +10,7 @@ three LLRs, both Tanner graphs of a CSS code in one kernel (`fgnn_relay4_decode`
 import numpy as np
 import torch
 
+from ._frontend import CodeDecoder, DepolarizingBP4Model, ShardedModel, alias, bsc_logit
 from .decoding import _binary_graph
 
 
@@ -103,7 +104,7 @@ class RelayBPDecoder:
     call = __call__
 
 
-class BP2_Relay_Model:
+class BP2_Relay_Model(ShardedModel):
     """``BP2_Relay_Model(pcm, logical_pcm, relay_decoder)``; ``model(batch_size, p)`` → ``(s_hat[bs,m], ls_hat[bs,rows(logical_pcm)])``,
     shaped like ``BP2_OSD_Model``: BSC(p) noise, its syndrome, Relay-BP.  ``s_hat = pcm·(noise xor estimate)`` is non-zero exactly on
     the samples for which no solution was found, ``ls_hat = logical_pcm·(noise xor estimate)``.  After a call ``last_noise``,
@@ -112,22 +113,18 @@ class BP2_Relay_Model:
     def __init__(self, pcm, logical_pcm, relay_decoder, *, seed=0x5EED, rank=0, world_size=1):
         self.pcm, self.logical_pcm, self.relay_decoder = pcm, logical_pcm, relay_decoder
         self.graph = _binary_graph(pcm, logical_pcm, relay_decoder.graph.device)
-        self.seed, self.rank, self.world_size, self._next = int(seed), int(rank), int(world_size), 0
+        self._shard(seed, rank, world_size)
         self.last_noise = self.last_estimate = self.last_stats = None
         self.last_num_unsolved = 0
 
     def __call__(self, batch_size, ebno_db=None, **kw):
         p = float(kw.get("p", ebno_db))
         B, g, d = int(batch_size), self.graph, self.relay_decoder
-        first = self._next + self.rank * B
-        self._next += self.world_size * B
-        pf = np.float32(p)
-        llr_const = float(-np.log((np.float32(1.0) - pf) / pf, dtype=np.float32))
-        noise = g.bsc_noise(self.seed, p, first, B)
+        noise = g.bsc_noise(self.seed, p, self._take(B), B)
         zeros = torch.zeros_like(noise)
         synd, _ = g.syndrome(zeros, noise)
         noise_hat, stats = g.relay_decode(synd, d.gamma, d.pre_iter, d.set_max_iter, d.stop_nconv, d.normalization_factor,
-                                          llr_const=llr_const, B=B)
+                                          llr_const=bsc_logit(p), B=B)
         d.last_stats = stats
         self.last_noise, self.last_estimate, self.last_stats = noise, noise_hat, stats
         self.last_num_unsolved = int((stats[:, 0] == 0).sum().item())
@@ -137,7 +134,7 @@ class BP2_Relay_Model:
     call = __call__
 
 
-class RelayBP4Decoder:
+class RelayBP4Decoder(CodeDecoder):
     """``RelayBP4Decoder(code, gamma0=0.125, pre_iter=80, num_sets=60, set_max_iter=60, gamma_dist_interval=(-0.24, 0.66),
     stop_nconv=1, normalization_factor=1.0, seed=0)``: Relay-BP on the quaternary decoder.  The schedule and the memory strengths are
     `RelayBPDecoder`'s (one strength per qubit and leg, applied to the qubit's three LLRs); every leg is min-sum BP4 on both Tanner
@@ -151,20 +148,12 @@ class RelayBP4Decoder:
     def __init__(self, code, gamma0=0.125, pre_iter=80, num_sets=60, set_max_iter=60, gamma_dist_interval=(-0.24, 0.66), stop_nconv=1,
                  normalization_factor=1.0, seed=0, device=None, graph=None):
         lo, hi = _relay_schedule(pre_iter, num_sets, set_max_iter, gamma_dist_interval, stop_nconv)
-        self._code = code
         self.pre_iter, self.num_sets, self.set_max_iter, self.stop_nconv = int(pre_iter), int(num_sets), int(set_max_iter), int(stop_nconv)
         self.gamma0, self.gamma_dist_interval, self.seed = float(gamma0), (lo, hi), int(seed)
         self.normalization_factor = float(normalization_factor)
-        if graph is None:
-            from .graph import TannerGraph
-            graph = TannerGraph(code, stage_one=False, device=device)
-        self.graph = graph
-        self._num_vns, self._num_cns_x, self._num_cns_z = self.graph.n, self.graph.m_x, self.graph.m_z
+        self._attach(code, graph, device)
         self.gamma = _draw_gamma(self.gamma0, self.num_sets, self._num_vns, lo, hi, self.seed)
-        self.last_stats = None
 
-    code = property(lambda self: self._code)
-    num_vns = property(lambda self: self._num_vns)
     num_legs = property(lambda self: 1 + self.num_sets)
     gamma = RelayBPDecoder.gamma
 
@@ -175,31 +164,8 @@ class RelayBP4Decoder:
         self.last_stats = stats
         return x_hat, z_hat, stats
 
-    def __call__(self, inputs):
-        g = self.graph
-        llr_ch, syndrome_x, syndrome_z = inputs
-        llr_ch = torch.as_tensor(llr_ch, device=g.device)
-        if llr_ch.dtype != torch.float32:
-            raise TypeError('Invalid input dtype.')
-        if llr_ch.shape[-1] != self._num_vns:
-            raise ValueError('Last dimension must be of length n.')
-        if llr_ch.dim() != 3 or llr_ch.shape[1] != 3:
-            raise ValueError('llr_ch must have shape [batch_size, 3, n].')
-        synd = []
-        for s, rows in ((syndrome_x, self._num_cns_x), (syndrome_z, self._num_cns_z)):
-            s = torch.as_tensor(s, device=g.device)
-            if s.dim() != 2 or s.shape[0] != rows:
-                raise ValueError(f"syndrome must have shape [{rows}, batch_size], got {tuple(s.shape)}")
-            if s.shape[1] != llr_ch.shape[0]:
-                raise ValueError('batch sizes of llr_ch and the syndromes differ.')
-            synd.append((s.to(torch.int64) & 1).to(torch.uint8).t().contiguous())
-        x_hat, z_hat, _ = self.decode(synd[0], synd[1], llr_ch=llr_ch.contiguous())
-        return x_hat.to(torch.int64), z_hat.to(torch.float64)
 
-    call = __call__
-
-
-class BP4_Relay_Model:
+class BP4_Relay_Model(DepolarizingBP4Model):
     """``BP4_Relay_Model(code, relay_decoder, p0=None)``; ``model(batch_size, p)`` → ``(s_hat[bs, m_z+m_x], ls_hat[bs,
     rows(hx_perp)+rows(hz_perp)])``, shaped like ``Sandwich_BP_GNN_Evaluation_Model``: depolarizing noise of rate ``p``, its two
     syndromes, Relay-BP4 with the prior ``log(3(1-p0)/p0)`` (``p0=None``: of ``p`` itself).  ``s_hat`` is non-zero exactly on the samples
@@ -207,30 +173,6 @@ class BP4_Relay_Model:
     ``last_stats`` (int32 [bs,4]) and ``last_num_unsolved`` describe that batch.  ``rank`` / ``world_size`` shard the sample stream."""
 
     def __init__(self, code, relay_decoder, p0=None, *, seed=0x5EED, rank=0, world_size=1):
-        self.code, self.relay_decoder, self.p0 = code, relay_decoder, p0
-        self.graph = relay_decoder.graph
-        self.seed, self.rank, self.world_size, self._next = int(seed), int(rank), int(world_size), 0
-        self.last_noise_x = self.last_noise_z = self.last_x_hat = self.last_z_hat = self.last_stats = None
-        self.last_num_unsolved = 0
+        super().__init__(code, relay_decoder, p0, seed=seed, rank=rank, world_size=world_size)
 
-    def next_sample_range(self, batch_size):
-        """``(first, last)``: the half-open range of global sample indices this rank's next batch will draw."""
-        first = self._next + self.rank * int(batch_size)
-        return first, first + int(batch_size)
-
-    def __call__(self, batch_size, ebno_db=None, **kw):
-        p = float(kw.get("p", ebno_db))
-        B, g, d = int(batch_size), self.graph, self.relay_decoder
-        first = self._next + self.rank * B
-        self._next += self.world_size * B
-        p0 = np.float32(p if self.p0 is None else self.p0)
-        llr_const = float(np.log(np.float32(3.0) * (np.float32(1.0) - p0) / p0, dtype=np.float32))
-        ex, ez = g.pauli_noise(self.seed, p, first, B)
-        sx, sz = g.syndrome(ex, ez)
-        x_hat, z_hat, stats = d.decode(sx, sz, llr_const=llr_const)
-        self.last_noise_x, self.last_noise_z, self.last_x_hat, self.last_z_hat, self.last_stats = ex, ez, x_hat, z_hat, stats
-        self.last_num_unsolved = int((stats[:, 0] == 0).sum().item())
-        s_hat, ls_hat, _ = g.residual(ex, ez, x_hat, z_hat, want_arrays=True)
-        return s_hat, ls_hat
-
-    call = __call__
+    relay_decoder = alias("decoder")

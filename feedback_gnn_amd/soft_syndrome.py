@@ -11,11 +11,11 @@ messages, decisions and ``u_hat`` bytes of a codeword in LDS throughout, and AMB
 import numpy as np
 import torch
 
-from ._lib import CN_TYPES
+from ._frontend import CodeDecoder, DepolarizingBP4Model, alpha_list, bsc_logit, llr_ch_in, syndrome_in
 from .mbp import MAX_ALPHAS, mbp4_tables
 
 
-class SoftSyndromeBP4Decoder:
+class SoftSyndromeBP4Decoder(CodeDecoder):
     """``SoftSyndromeBP4Decoder(code, alphas=(1.0,), num_iter=64, cn_type="minsum", factor=0.8, restart=True)``.  One alpha of 1.0 is
     plain soft-syndrome flooding BP4; a descending list is Kuo, Chern and Lai's MBP4 on the data-syndrome code: for every alpha in turn
     up to ``num_iter`` iterations with the check outputs multiplied by ``factor / alpha``, from zero messages or, with
@@ -28,31 +28,13 @@ class SoftSyndromeBP4Decoder:
     that alpha of the last test; ``last_u_x_hat[bs,m_x]`` and ``last_u_z_hat[bs,m_z]`` (uint8) = the syndrome bits estimated wrong."""
 
     def __init__(self, code, alphas=(1.0,), num_iter=64, cn_type="minsum", factor=0.8, restart=True, device=None, graph=None):
-        alphas = tuple(float(x) for x in alphas)
-        if not 1 <= len(alphas) <= MAX_ALPHAS:
-            raise ValueError(f"alphas must hold 1 .. {MAX_ALPHAS} values")
-        if not all(np.isfinite(x) and x > 0 for x in alphas):
-            raise ValueError("every alpha must be finite and positive")
-        if not isinstance(num_iter, (int, np.integer)) or num_iter < 1:
-            raise ValueError("num_iter must be a positive integer")
-        if not (np.isfinite(float(factor)) and float(factor) > 0):
-            raise ValueError("factor must be finite and positive")
-        if cn_type not in CN_TYPES:
-            raise ValueError("Unknown node type.")
-        self._code = code
+        alphas = alpha_list(alphas, MAX_ALPHAS, num_iter, factor, cn_type)
         self.alphas, self.num_iter, self.cn_type, self.factor, self.restart = alphas, int(num_iter), cn_type, float(factor), bool(restart)
         self.factors, self.owns = mbp4_tables(alphas, factor)
         if not np.isfinite(self.factors).all():
             raise ValueError("factor / alpha must be finite in float32")
-        if graph is None:
-            from .graph import TannerGraph
-            graph = TannerGraph(code, stage_one=False, device=device)
-        self.graph = graph
-        self._num_vns, self._num_cns_x, self._num_cns_z = self.graph.n, self.graph.m_x, self.graph.m_z
-        self.last_stats = self.last_u_x_hat = self.last_u_z_hat = None
-
-    code = property(lambda self: self._code)
-    num_vns = property(lambda self: self._num_vns)
+        self._attach(code, graph, device)
+        self.last_u_x_hat = self.last_u_z_hat = None
 
     @staticmethod
     def from_soft(values):
@@ -71,36 +53,25 @@ class SoftSyndromeBP4Decoder:
         return x_hat, z_hat, u_x_hat, u_z_hat, stats
 
     def __call__(self, inputs):
-        g = self.graph
+        device = self.graph.device
         llr_ch, syndrome_x, syndrome_z, synd_llr_x, synd_llr_z = inputs
-        llr_ch = torch.as_tensor(llr_ch, device=g.device)
-        if llr_ch.dtype != torch.float32:
-            raise TypeError('Invalid input dtype.')
-        if llr_ch.shape[-1] != self._num_vns:
-            raise ValueError('Last dimension must be of length n.')
-        if llr_ch.dim() != 3 or llr_ch.shape[1] != 3:
-            raise ValueError('llr_ch must have shape [batch_size, 3, n].')
+        llr_ch = llr_ch_in(llr_ch, self._num_vns, device)
         synd, soft = [], []
         for s, lr, rows in ((syndrome_x, synd_llr_x, self._num_cns_x), (syndrome_z, synd_llr_z, self._num_cns_z)):
-            s = torch.as_tensor(s, device=g.device)
-            if s.dim() != 2 or s.shape[0] != rows:
-                raise ValueError(f"syndrome must have shape [{rows}, batch_size], got {tuple(s.shape)}")
-            if s.shape[1] != llr_ch.shape[0]:
-                raise ValueError('batch sizes of llr_ch and the syndromes differ.')
-            synd.append((s.to(torch.int64) & 1).to(torch.uint8).t().contiguous())
+            synd.append(syndrome_in(s, rows, device, llr_ch.shape[0]))
             if lr is not None:
-                lr = torch.as_tensor(lr, device=g.device)
-                if tuple(lr.shape) != tuple(s.shape):
-                    raise ValueError(f"syndrome LLRs must have shape {tuple(s.shape)}, got {tuple(lr.shape)}")
+                lr = torch.as_tensor(lr, device=device)
+                if tuple(lr.shape) != (rows, llr_ch.shape[0]):
+                    raise ValueError(f"syndrome LLRs must have shape {(rows, llr_ch.shape[0])}, got {tuple(lr.shape)}")
                 lr = lr.to(torch.float32).t().contiguous()
             soft.append(lr)
-        x_hat, z_hat, _, _, _ = self.decode(synd[0], synd[1], soft[0], soft[1], llr_ch=llr_ch.contiguous())
+        x_hat, z_hat = self.decode(synd[0], synd[1], soft[0], soft[1], llr_ch=llr_ch)[:2]
         return x_hat.to(torch.int64), z_hat.to(torch.float64)
 
     call = __call__
 
 
-class BP4_SoftSyndrome_Model:
+class BP4_SoftSyndrome_Model(DepolarizingBP4Model):
     """``BP4_SoftSyndrome_Model(code, decoder, q, p0=None, q0=None, seed=..)``; ``model(batch_size, p)`` → ``(s_hat[bs, m_z+m_x],
     ls_hat[bs, rows(hx_perp)+rows(hz_perp)])``, shaped like ``BP4_AMBP_Model``: depolarizing noise of rate ``p`` from the stream of
     ``seed``, its two syndromes ``s``, measurement flips ``u`` of rate ``q`` (`TannerGraph.syndrome_noise` on the same ``seed``), and
@@ -119,45 +90,25 @@ class BP4_SoftSyndrome_Model:
             raise ValueError("q must be in [0, 1)")
         if q0 is not None and not 0.0 <= float(q0) < 1.0:
             raise ValueError("q0 must be in [0, 1)")
-        self.code, self.decoder, self.q, self.p0, self.q0 = code, decoder, q, p0, q0
-        self.graph = decoder.graph
-        self.seed, self.rank, self.world_size, self._next = int(seed), int(rank), int(world_size), 0
-        self.last_noise_x = self.last_noise_z = self.last_x_hat = self.last_z_hat = self.last_stats = None
+        super().__init__(code, decoder, p0, seed=seed, rank=rank, world_size=world_size)
+        self.q, self.q0 = q, q0
         self.last_u_x = self.last_u_z = self.last_u_x_hat = self.last_u_z_hat = None
-        self.last_num_unsolved = 0
 
     @property
     def gamma(self):
         """``log((1-q0)/q0)`` in float32 arithmetic, +inf for ``q0 = 0``."""
-        q0 = np.float32(self.q if self.q0 is None else self.q0)
-        if q0 == 0:
-            return float("inf")
-        return float(np.log((np.float32(1.0) - q0) / q0, dtype=np.float32))
+        q0 = self.q if self.q0 is None else self.q0
+        return float("inf") if np.float32(q0) == 0 else -bsc_logit(q0)
 
-    def next_sample_range(self, batch_size):
-        """``(first, last)``: the half-open range of global sample indices this rank's next batch will draw."""
-        first = self._next + self.rank * int(batch_size)
-        return first, first + int(batch_size)
-
-    def __call__(self, batch_size, ebno_db=None, **kw):
-        p = float(kw.get("p", ebno_db))
-        B, g, d = int(batch_size), self.graph, self.decoder
-        first = self._next + self.rank * B
-        self._next += self.world_size * B
-        p0 = np.float32(p if self.p0 is None else self.p0)
-        llr_const = float(np.log(np.float32(3.0) * (np.float32(1.0) - p0) / p0, dtype=np.float32))
-        ex, ez = g.pauli_noise(self.seed, p, first, B)
-        sx, sz = g.syndrome(ex, ez)
+    def _measure(self, sx, sz, first, B):
         if self.q > 0:
-            ux, uz = g.syndrome_noise(self.seed, self.q, first, B)
+            ux, uz = self.graph.syndrome_noise(self.seed, self.q, first, B)
             sx, sz = sx ^ ux, sz ^ uz
         else:
             ux, uz = torch.zeros_like(sx), torch.zeros_like(sz)
-        x_hat, z_hat, u_x_hat, u_z_hat, stats = d.decode(sx, sz, gamma=self.gamma, llr_const=llr_const)
-        self.last_noise_x, self.last_noise_z, self.last_x_hat, self.last_z_hat, self.last_stats = ex, ez, x_hat, z_hat, stats
-        self.last_u_x, self.last_u_z, self.last_u_x_hat, self.last_u_z_hat = ux, uz, u_x_hat, u_z_hat
-        self.last_num_unsolved = int((stats[:, 0] == 0).sum().item())
-        s_hat, ls_hat, _ = g.residual(ex, ez, x_hat, z_hat, want_arrays=True)
-        return s_hat, ls_hat
+        self.last_u_x, self.last_u_z = ux, uz
+        return sx, sz
 
-    call = __call__
+    def _decode(self, sx, sz, llr_const, first):
+        x_hat, z_hat, self.last_u_x_hat, self.last_u_z_hat, stats = self.decoder.decode(sx, sz, gamma=self.gamma, llr_const=llr_const)
+        return x_hat, z_hat, stats
