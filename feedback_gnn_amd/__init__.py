@@ -46,6 +46,9 @@ def __getattr__(name):
     if name in ("SoftSyndromeBP4Decoder", "BP4_SoftSyndrome_Model"):
         from . import soft_syndrome as _ss
         return getattr(_ss, name)
+    if name in ("SpaceTimeBP4Decoder", "BP4_Phenomenological_Model"):
+        from . import space_time as _st
+        return getattr(_st, name)
     if name in ("GNN_BP4", "MLP"):
         from . import gnn as _gn
         return getattr(_gn, name)

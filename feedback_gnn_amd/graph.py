@@ -927,6 +927,54 @@ class TannerGraph:
                                            _ptr(zh), _ptr(uxh), _ptr(uzh), _ptr(stats), _stream(self.device)))
         return xh, zh, uxh, uzh, stats
 
+    def stbp4_decode(self, synd_x, synd_z, factors, owns, pre_iter, attempt_iter, cn_type="minsum", restart=True, rounds=None,
+                     prev_x=None, prev_z=None, llr_ch=None, llr_const=0.0, synd_llr_x=None, synd_llr_z=None, gamma_x=float("inf"),
+                     gamma_z=float("inf"), gamma_last_x=float("inf"), gamma_last_z=float("inf"), B=None):
+        """Space-time BP4 on a window of `rounds` repeated measurements (`fgnn_stbp4_decode`): `dsbp4_decode` on R copies of the two
+        graphs, coupled by one time variable per check and round.  `synd_x` [B, R, m_x] / `synd_z` [B, R, m_z] (uint8) are the raw
+        measured syndromes (None: all-zero), `prev_x` [B, m_x] / `prev_z` [B, m_z] the syndrome the window starts from (None: zero);
+        the library forms the differences of consecutive rounds itself.  `llr_ch` [B, 3, n] or `llr_const` is the prior of a qubit in
+        every round.  `gamma_x` / `gamma_z` are the syndrome LLRs of rounds 0 .. R-2 and `gamma_last_x` / `gamma_last_z` that of round
+        R-1 (+inf, the default: a perfect read-out; NaN is refused); `synd_llr_x` [B, R, m_x] / `synd_llr_z` [B, R, m_z] (float32)
+        replace both scalars of their side.  `rounds` = None takes R from the first of the syndromes and syndrome LLRs that is given.
+        Every other argument is `mbp4_decode`'s.  Returns `(x_hat [B,R,n], z_hat [B,R,n]` = the error estimated for each round, not
+        cumulative, `u_x_hat [B,R,m_x], u_z_hat [B,R,m_z]` uint8, `stats [B,4]` int32 = found, the attempt of the last test,
+        iterations, k of the last test)`, per window.  A window that does not fit the LDS is refused with a ValueError that names the
+        largest number of rounds that fits."""
+        cn = self._cn(cn_type)
+        factors, owns = self._tables_in(factors, owns)
+        windows = (synd_x, synd_z, synd_llr_x, synd_llr_z)
+        if rounds is None:
+            rounds = next((int(t.shape[1]) for t in windows if t is not None and t.dim() == 3), None)
+            if rounds is None:
+                raise ValueError("rounds is needed when neither syndromes nor syndrome LLRs are given")
+        R = int(rounds)
+        if R < 1:
+            raise ValueError("rounds must be >= 1")
+        for t in (synd_x, synd_z, prev_x, prev_z, llr_ch, synd_llr_x, synd_llr_z):
+            if t is not None:
+                B = int(t.shape[0])
+        if B is None:
+            raise ValueError("B is needed when neither syndromes nor llr_ch nor syndrome LLRs are given")
+        synd_x = self._opt(synd_x, (B, R, self.m_x), torch.uint8, "synd_x")
+        synd_z = self._opt(synd_z, (B, R, self.m_z), torch.uint8, "synd_z")
+        prev_x = self._opt(prev_x, (B, self.m_x), torch.uint8, "prev_x")
+        prev_z = self._opt(prev_z, (B, self.m_z), torch.uint8, "prev_z")
+        llr_ch = self._opt(llr_ch, (B, 3, self.n), torch.float32, "llr_ch")
+        synd_llr_x = self._opt(synd_llr_x, (B, R, self.m_x), torch.float32, "synd_llr_x")
+        synd_llr_z = self._opt(synd_llr_z, (B, R, self.m_z), torch.float32, "synd_llr_z")
+        xh = self._new((B, R, self.n), torch.uint8)
+        zh = self._new((B, R, self.n), torch.uint8)
+        uxh = self._new((B, R, self.m_x), torch.uint8)
+        uzh = self._new((B, R, self.m_z), torch.uint8)
+        stats = self._new((B, 4), torch.int32)
+        check(_lib.lib().fgnn_stbp4_decode(self.handle, cn, len(factors), factors.ctypes.data, owns.ctypes.data, int(pre_iter),
+                                           int(attempt_iter), int(restart), R, _ptr(llr_ch), float(llr_const), _ptr(synd_x), _ptr(synd_z),
+                                           _ptr(prev_x), _ptr(prev_z), _ptr(synd_llr_x), float(gamma_x), float(gamma_last_x),
+                                           _ptr(synd_llr_z), float(gamma_z), float(gamma_last_z), B, _ptr(xh), _ptr(zh), _ptr(uxh),
+                                           _ptr(uzh), _ptr(stats), _stream(self.device)))
+        return xh, zh, uxh, uzh, stats
+
     @staticmethod
     def syndrome_noise_seeds(seed):
         """The two stream seeds of `syndrome_noise`: ``(seed + 0x9E3779B97F4A7C15) mod 2^64`` for the hx checks and ``(seed + 2 *

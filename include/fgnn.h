@@ -468,6 +468,62 @@ int fgnn_dsbp4_decode(const fgnn_graph* g, int cn_type, int num_attempts, const 
                       const float* synd_llr_x /* [B,m_x] or NULL */, float gamma_x, const float* synd_llr_z /* [B,m_z] or NULL */,
                       float gamma_z, int B, uint8_t* x_hat, uint8_t* z_hat, uint8_t* u_x_hat /* [B,m_x] */, uint8_t* u_z_hat /* [B,m_z] */,
                       int32_t* stats /* [B,4] */, void* stream);
+/* Space-time BP4: a window of `rounds` = R >= 1 repeated, noisy syndrome measurements decoded in one launch (the phenomenological
+ * noise model of fault-tolerant memory experiments), flooding schedule, with the attempt list of fgnn_mbp4_decode kept.  Before
+ * measurement t a fresh data error e_t occurs, and measurement t reports s_t = H (e_0 ^ .. ^ e_t) ^ u_t with u_t its own flips.  The
+ * differences of consecutive syndromes satisfy d_t = s_t ^ s_{t-1} = H e_t ^ u_t ^ u_{t-1}: R copies of the code's two Tanner graphs,
+ * coupled only by binary "time" variables u_{c,t} of degree two, between check c of round t and check c of round t + 1.  The time
+ * variable of the last round has degree one, which is exactly the extra input of fgnn_dsbp4_decode.
+ * Inputs.  synd_x [B,R,m_x] / synd_z [B,R,m_z]: the raw measured syndromes (NULL = all zero).  prev_x [B,m_x] / prev_z [B,m_z]: the
+ * syndrome a sliding window starts from (NULL = zero).  The differences are formed inside: d_{c,0} = s_{c,0} ^ prev_c and d_{c,t} =
+ * s_{c,t} ^ s_{c,t-1}.  llr_ch [B,3,n] or llr_const: one prior per qubit, the same in every round.  Syndrome LLRs per side: gamma_x /
+ * gamma_z for rounds 0 .. R-2 and gamma_last_x / gamma_last_z for round R-1 (+inf: the final perfect read-out; a window that is not
+ * the last one passes gamma here too); synd_llr_x [B,R,m_x] / synd_llr_z [B,R,m_z], where not NULL, replace both scalars of their side.
+ * Everything not mentioned here is fgnn_dsbp4_decode and fgnn_mbp4_decode to the float operation: the message layout of every round,
+ * the literal qubit update with own[a], factor[a], pre_iter / attempt_iter / restart, iteration counting, the four stats columns,
+ * B = 0 and the argument checks.
+ * Variables.  Qubit (v,t) is a quaternary variable on the checks of round t only, with BP4's qubit rule unchanged.  Time variable
+ * (c,t), t = 0 .. R-1, is binary with prior gamma_{c,t}; for t < R-1 it sits on check (c,t) and check (c,t+1), for t = R-1 on check
+ * (c,t) only.  u_{c,-1} is known to be 0 and is no variable.
+ * Check rule.  Check (c,t) with d edges (inputs nu_1 .. nu_d in ascending qubit order) and syndrome bit d_{c,t} evaluates the rule of
+ * cn_type on the inputs (nu_1, .., nu_d, b) for t = 0 and (nu_1, .., nu_d, a, b) for t >= 1, in that order, with the same float
+ * operations; a is the message from time variable (c,t-1), b the message from time variable (c,t).  Every extra input is treated as
+ * fgnn_dsbp4_decode treats its one extra input:
+ *   boxplus-phi: phi of the magnitude is added to T after the edges, in order (T = (((a_1 + ..) + a_d) + phi|a|) + phi|b|), and the
+ *                sign enters neg;  the output for an extra input x is with_sign(phi(T - phi|x|), neg ^ (x < 0)) * factor.
+ *   minsum:      the same +-20 clip;  minv, min2 and nsum run over all inputs in order;  an extra input's output takes min_e or minv by
+ *                the same d == 0 test.
+ *   boxplus:     tanh(x / 2) with 0 -> 1e-12 is multiplied in after the edges, in order, then the syndrome sign;  the output is
+ *                (2 * atanh(clip(rcp(t_x) * P))) * factor, with the same small-magnitude flush and clip.
+ * Outputs 1 .. d, times factor[a], are the new c->v messages.  The outputs for the extra inputs, times factor[a], are w_up_{c,t}
+ * (towards time variable (c,t-1), only for t >= 1) and w_dn_{c,t} (towards time variable (c,t)).
+ * Time variable rule, evaluated in the qubit phase together with the qubits, on the outputs of the check update before it:
+ *     Gamma_{c,t} = (gamma_{c,t} + w_dn_{c,t}) + w_up_{c,t+1}  for t < R-1;   Gamma_{c,t} = gamma_{c,t} + w_dn_{c,t}  for t = R-1
+ *     u_hat_{c,t} = Gamma_{c,t} < 0
+ *     to check (c,t+1):  a = gamma_{c,t} + w_dn_{c,t}
+ *     to check (c,t):    b = gamma_{c,t} + w_up_{c,t+1}  for t < R-1;   b = gamma_{c,t} itself, with no add, for t = R-1
+ * own[a] acts on qubits only: a time variable's messages are the plain extrinsic sums above.  Before the first check update, and at
+ * a restarting attempt, every w is 0 (the adds are still made).
+ * Joint test, after check update k, on the decisions and the u_hat formed from the new messages.  A window is solved iff for every
+ * round t, for every hx row c, parity(z_hat_t over c) ^ d_{c,t} ^ u_hat_{c,t} ^ u_hat_{c,t-1} == 0, and for every hz row c,
+ * parity(x_hat_t over c) ^ d_{c,t} ^ u_hat_{c,t} ^ u_hat_{c,t-1} == 0, with u_hat_{c,-1} = 0.
+ * Outputs of the last test made: x_hat, z_hat [B,R,n] = the error estimated for each round (not cumulative), u_x_hat [B,R,m_x],
+ * u_z_hat [B,R,m_z], stats [B,4] as fgnn_mbp4_decode (per window).  rounds < 1 or a NaN scalar gamma is FGNN_ERR_ARG; +inf and
+ * negative values are legal, as in fgnn_dsbp4_decode.  With rounds = 1, prev = NULL and gamma_last = gamma every output equals
+ * fgnn_dsbp4_decode's bit for bit.  The messages, a and b slots, decisions and u_hat bytes of a whole window stay in LDS for the whole
+ * launch, next to the two 64-float tables: per window 4 (R round4(E_x + E_z) + round4(R m) + round4((R-1) m)) bytes of floats plus
+ * R n and R m bytes, each byte area rounded up to 16 bytes.  A window that does not fit is refused (FGNN_ERR_ARG) with a message that
+ * names the bytes needed and the largest number of rounds that fits; there is no global-memory variant.  The launch is planned for
+ * the window (R n qubits, R m checks); fgnn_graph_set_launch is honoured, with "codeword" read as "window", and no result depends on
+ * the geometry. */
+int fgnn_stbp4_decode(const fgnn_graph* g, int cn_type, int num_attempts, const float* factor, const float* own, int pre_iter,
+                      int attempt_iter, int restart, int rounds, const float* llr_ch, float llr_const,
+                      const uint8_t* synd_x /* [B,R,m_x] or NULL */, const uint8_t* synd_z /* [B,R,m_z] or NULL */,
+                      const uint8_t* prev_x /* [B,m_x] or NULL */, const uint8_t* prev_z /* [B,m_z] or NULL */,
+                      const float* synd_llr_x /* [B,R,m_x] or NULL */, float gamma_x, float gamma_last_x,
+                      const float* synd_llr_z /* [B,R,m_z] or NULL */, float gamma_z, float gamma_last_z, int B,
+                      uint8_t* x_hat /* [B,R,n] */, uint8_t* z_hat /* [B,R,n] */, uint8_t* u_x_hat /* [B,R,m_x] */,
+                      uint8_t* u_z_hat /* [B,R,m_z] */, int32_t* stats /* [B,4] */, void* stream);
 /* Layers of the serial (layered) check schedule.  Checks are numbered 0..m_x-1 for hx and m_x..m_x+m_z-1 for hz; a layering is
  * layer_of[m_x+m_z] with values in [0, num_layers) such that every layer is non-empty and no two checks of a layer share a qubit —
  * across hx and hz too, since a qubit's update reads the messages of both sides.  All pointers are host pointers; fgnn_greedy_layers and
