@@ -25,6 +25,7 @@
 // operation count per codeword stays a constant, and every float that reaches a message is produced by the operations the oracle
 // executes for it (see first_closed / first_peeled in bp4_kernel).
 
+#include <cmath>
 #include <type_traits>
 
 #include "fgnn_internal.h"
@@ -79,6 +80,7 @@ struct BpArgs {
     float* tape_z;            //                          [num_iter+1, B, E_z] — the tape fgnn_bp4_backward reads
     int nt;                   // 4 / 5: first decoder with compile-time trips (kernel variant NT = nt), 0: the runtime loops
     int shared_lse;           // 1: the (a - b)-dependent part of the qubit update's log-sum-exp once per qubit and side (FGNN_OPT_BP4_SHARED_LSE)
+    int bounded;              // 1: the launch arguments keep the qubit update's arguments within FG_BOUNDED_MAX (kernel variant BND, nt or lreg set)
 };
 
 // Elementary-function policy of the kernel.  Mx<false> = fgnn_math.h: the float operations the CPU oracle executes, bit for bit
@@ -96,6 +98,15 @@ struct Mx {
     static __device__ __forceinline__ float lse2(float a, float b) { return fg_lse2_ranged(a, b); }
     static __device__ __forceinline__ float lse2_corr(float a, float b) { return fg_lse2_corr_ranged(a, b); }
     static __device__ __forceinline__ float phi(float x) { return fg_phi_med(x); }
+};
+// Mx<false> for a launch whose arguments bound every softplus argument and every log-sum-exp distance by FG_BOUNDED_MAX (plan_bp4
+// makes the proof; BND of bp4_kernel): the range guards of the two routines, which act beyond 87 only, are not issued — six v_min_f32
+// per qubit and iteration in the literal form, and a v_cmp + v_cndmask in each of the two softplus.  The same bits on the bounded
+// range (fgnn_math_ranged.h; tests/test_math_bounded.py, exhaustive).  phi is Mx<false>'s.
+struct MxBounded : Mx<false> {
+    static __device__ __forceinline__ float softplus(float t) { return fg_softplus_bounded(t); }
+    static __device__ __forceinline__ float lse2(float a, float b) { return fg_lse2_bounded(a, b); }
+    static __device__ __forceinline__ float lse2_corr(float a, float b) { return fg_lse2_corr_bounded(a, b); }
 };
 template <>
 struct Mx<true> {
@@ -377,14 +388,20 @@ __device__ __forceinline__ float softplus_saturated(float t)
 // unrolled at compile time: a qubit's slots are one per-thread LDS base plus an immediate offset, a check's row is a scalar base
 // plus one per-thread offset, and no counter, pointer or bounds test is carried through the iteration loop.  The NQ > 0 kernels run
 // their checks the same way with NQ trips, each guarded (their threads-per-codeword is a launch argument).
+// BND (the NT and NQ kernels of the (3,3,6) graphs, which is where the benchmark's sandwiches run): the launch arguments bound every
+// argument of the qubit update's softplus and log-sum-exp (a.bounded, proven in plan_bp4), so the qubit phase, the closed-form and
+// peeled iteration 0 and the epilogue's binary LLRs run on MxBounded — the routines without their range guards, the same bits.  The
+// check-node rule and everything else are the BND = false kernel's.
 template <int CN_TYPE, int DVX, int DVZ, int DC, bool OPT, bool HWT = false, int NQ = 0, bool TRACE = false, bool GMEM = false, int LSE = 2,
-          int NT = 0>
+          int NT = 0, bool BND = false>
 __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(NQ > 0 ? FGNN_BP4_WAVES - 1 : FGNN_BP4_WAVES)))
 bp4_kernel(GraphDev g, BpArgs a)
 {
     static_assert(!(HWT && OPT), "the hardware-transcendental variant is the fixed dataflow only: the exact shortcuts are proofs about fgnn_math.h");
     static_assert(!GMEM || (DVX == 0 && !OPT && !HWT && NQ == 0 && !TRACE), "the global-memory variant is the plain runtime-degree kernel");
-    using MX = Mx<HWT>;
+    static_assert(!BND || (DVX > 0 && CN_TYPE == FGNN_CN_BOXPLUS_PHI && !HWT && !TRACE && !GMEM && (NQ > 0 || NT > 0)),
+                  "bounded arguments: the regular phi kernels with compile-time trips, exact math");
+    using MX = std::conditional_t<BND, MxBounded, Mx<HWT>>;
     FG_LOG_TAB_SETUP();
     constexpr bool REGULAR = DVX > 0;
     constexpr bool LREG = NQ > 0;
@@ -977,8 +994,8 @@ using Bp4Kernel = void (*)(GraphDev, BpArgs);
 
 // The benchmark codes' kernels carry the form of the qubit update as a compile-time argument (LSE = 0 literal / 1 shared):
 // the (3,3,6) phi kernels indexed by [lreg 0 / 4 / 5][shortcut][LSE].
-template <int NQ, bool OPT, int LSE, int NT = 0>
-constexpr Bp4Kernel bp4_lse_kernel = bp4_kernel<FGNN_CN_BOXPLUS_PHI, 3, 3, 6, OPT, false, NQ, false, false, LSE, NT>;
+template <int NQ, bool OPT, int LSE, int NT = 0, bool BND = false>
+constexpr Bp4Kernel bp4_lse_kernel = bp4_kernel<FGNN_CN_BOXPLUS_PHI, 3, 3, 6, OPT, false, NQ, false, false, LSE, NT, BND>;
 constexpr Bp4Kernel bp4_lse_kernels[3][2][2] = {
     {{bp4_lse_kernel<0, false, 0>, bp4_lse_kernel<0, false, 1>}, {bp4_lse_kernel<0, true, 0>, bp4_lse_kernel<0, true, 1>}},
     {{bp4_lse_kernel<4, false, 0>, bp4_lse_kernel<4, false, 1>}, {bp4_lse_kernel<4, true, 0>, bp4_lse_kernel<4, true, 1>}},
@@ -988,6 +1005,16 @@ constexpr Bp4Kernel bp4_lse_kernels[3][2][2] = {
 constexpr Bp4Kernel bp4_nt_kernels[2][2][2] = {
     {{bp4_lse_kernel<0, false, 0, 4>, bp4_lse_kernel<0, false, 1, 4>}, {bp4_lse_kernel<0, true, 0, 4>, bp4_lse_kernel<0, true, 1, 4>}},
     {{bp4_lse_kernel<0, false, 0, 5>, bp4_lse_kernel<0, false, 1, 5>}, {bp4_lse_kernel<0, true, 0, 5>, bp4_lse_kernel<0, true, 1, 5>}}};
+
+// the same sixteen with bounded arguments (BND; a.bounded): [lreg 4 / 5][shortcut][LSE] and [nt 4 / 5][shortcut][LSE]
+template <int NQ, bool OPT, int LSE, int NT = 0>
+constexpr Bp4Kernel bp4_bnd_kernel = bp4_lse_kernel<NQ, OPT, LSE, NT, true>;
+constexpr Bp4Kernel bp4_lse_bnd_kernels[2][2][2] = {
+    {{bp4_bnd_kernel<4, false, 0>, bp4_bnd_kernel<4, false, 1>}, {bp4_bnd_kernel<4, true, 0>, bp4_bnd_kernel<4, true, 1>}},
+    {{bp4_bnd_kernel<5, false, 0>, bp4_bnd_kernel<5, false, 1>}, {bp4_bnd_kernel<5, true, 0>, bp4_bnd_kernel<5, true, 1>}}};
+constexpr Bp4Kernel bp4_nt_bnd_kernels[2][2][2] = {
+    {{bp4_bnd_kernel<0, false, 0, 4>, bp4_bnd_kernel<0, false, 1, 4>}, {bp4_bnd_kernel<0, true, 0, 4>, bp4_bnd_kernel<0, true, 1, 4>}},
+    {{bp4_bnd_kernel<0, false, 0, 5>, bp4_bnd_kernel<0, false, 1, 5>}, {bp4_bnd_kernel<0, true, 0, 5>, bp4_bnd_kernel<0, true, 1, 5>}}};
 
 template <int CN_TYPE, int DVX, int DVZ, int DC>
 int launch_bp4_k(const fgnn_graph* g, const BpArgs& a, const LaunchGeom& L, size_t lds_bytes, hipStream_t st)
@@ -1001,6 +1028,8 @@ int launch_bp4_k(const fgnn_graph* g, const BpArgs& a, const LaunchGeom& L, size
         if constexpr (DVX == 3 && DVZ == 3 && DC == 6) {
             if (!a.trace_x && !a.hwt) kern = bp4_lse_kernels[a.lreg ? a.lreg - 3 : 0][a.shortcut][a.shared_lse];
             if (!a.trace_x && !a.hwt && a.nt) kern = bp4_nt_kernels[a.nt - 4][a.shortcut][a.shared_lse];
+            if (!a.trace_x && !a.hwt && a.bounded && a.lreg) kern = bp4_lse_bnd_kernels[a.lreg - 4][a.shortcut][a.shared_lse];
+            if (!a.trace_x && !a.hwt && a.bounded && a.nt) kern = bp4_nt_bnd_kernels[a.nt - 4][a.shortcut][a.shared_lse];
             if (!a.trace_x && !a.hwt && (a.nt || a.lreg)) {
                 // these address their check slots as dynamic-LDS offset + BP4_STATIC_LDS (cn_phi_regular<..., LDSB>): hold the
                 // compiled kernel to it (a compiler that lays the static LDS out differently must not decode silently wrong)
@@ -1038,7 +1067,8 @@ int launch_bp4(const fgnn_graph* g, const BpArgs& a, const LaunchGeom& L, const 
 // Fills the layout and variant fields of `a` (lch_off, lreg, nt, trace_off, sig_off, early_exit, flag_off, lds_per_cw, shortcut, hwt,
 // shared_lse) from the graph, its options and the optional buffers set in `a`.  A codeword whose state does not fit a CU's LDS is
 // planned again with gmem = true: no LDS budget, one global-memory workspace row per codeword.
-Bp4Plan plan_bp4(const fgnn_graph* g, int cn_type, const LaunchGeom& L, BpArgs& a, bool gmem = false)
+// `llr_bound`: what the caller guarantees about a.llr_ch, |llr_ch[.]| <= llr_bound for every entry (+inf: nothing) — it decides a.bounded.
+Bp4Plan plan_bp4(const fgnn_graph* g, int cn_type, const LaunchGeom& L, BpArgs& a, float llr_bound, bool gmem = false)
 {
     const GraphDev& d = g->d;
     const int n = d.n;
@@ -1060,6 +1090,25 @@ Bp4Plan plan_bp4(const fgnn_graph* g, int cn_type, const LaunchGeom& L, BpArgs& 
     a.lreg = (a.llr_ch && fixed_trips && trips <= 5) ? (trips <= 4 ? 4 : 5) : 0;
     // one constant channel LLR, 256 threads, as many checks as qubits per thread and the last trip the only partial one
     a.nt = (!a.llr_ch && fixed_trips && L.tpc == 256 && per_thread == per_thread_c && (trips == 4 || trips == 5)) ? trips : 0;
+    // Bounded arguments (kernel variant BND, MxBounded): the NT / NQ kernels drop the range guards of the qubit update's softplus and
+    // log-sum-exp when the launch arguments prove that no argument reaches them.  In exact arithmetic, on a (3,3,6) graph:
+    //  - every check-to-qubit message is phi(.) * factor (or the shortcut's phi0 * factor), and phi <= phi0 = 16.6355324 on every float
+    //    (tests/test_math_bounded.py: exhaustive), so from zero start messages |Sx|, |Sz| <= M = 3 * phi0 * |factor| in every iteration;
+    //  - the channel LLRs are bounded by L_b: |llr_const| without llr_ch, else what the caller guarantees (the feedback GNN's output
+    //    bound from its weights; nothing for a caller's own llr_ch: +inf, never bounded);
+    //  - a softplus sees t = -X or -Z: |t| <= M + L_b.  A log-sum-exp sees d = |(A - mu) - (Y - mu)| (literal form, epilogue: mu = 0)
+    //    or |A - Y| (shared form) with A = X or Z: Y - X = Sx + l_y - l_x, Y - Z = Sz + l_y - l_z, so d <= M + 2 * L_b.
+    // In floats, the three-term sums Sz and Sx, the two additions of Y = (Sz + Sx) + l, the one of X and of Z, and the two subtractions
+    // of the edge's own message each round by at most half an ulp of a number below 128 (2^-17): fewer than ten such roundings, far below
+    // the 1 the second condition adds, and both conditions stop at FG_BOUNDED_MAX = 80 where the routines are good to 87.
+    // Evaluated in double; anything not proven (initial messages, a non-finite factor or bound) takes the guarded kernels.
+    {
+        const double phi0 = 16.6355324, M = 3.0 * phi0 * std::fabs((double)a.factor);
+        const double Lb = a.llr_ch ? (double)llr_bound : std::fabs((double)a.llr_const);
+        a.bounded = ((a.nt || a.lreg) && !a.msg_init_x && !a.msg_init_z && std::isfinite(M) && std::isfinite(Lb) && Lb >= 0.0 &&
+                     M + Lb <= (double)FG_BOUNDED_MAX && M + 2.0 * Lb + 1.0 <= (double)FG_BOUNDED_MAX)
+                        ? 1 : 0;
+    }
     int per = a.lch_off + ((a.llr_ch && !a.lreg) ? 3 * n : 0);
     a.trace_off = 0;
     if (trace) {  // 2n binary LLRs of the per-iteration soft syndromes, behind the messages and the channel LLRs
@@ -1093,7 +1142,7 @@ Bp4Plan plan_bp4(const fgnn_graph* g, int cn_type, const LaunchGeom& L, BpArgs& 
     }
     a.lds_per_cw = per;
     const size_t lds_bytes = ((size_t)per * L.cpb + tail) * sizeof(float);
-    if (lds_bytes > FGNN_LDS_BUDGET) return plan_bp4(g, cn_type, L, a, true);
+    if (lds_bytes > FGNN_LDS_BUDGET) return plan_bp4(g, cn_type, L, a, llr_bound, true);
     return {lds_bytes, false, 0};
 }
 
@@ -1103,7 +1152,7 @@ static int bp4_decode_core(const fgnn_graph* g, int cn_type, int num_iter, float
                            float llr_const, const uint8_t* synd_x, const uint8_t* synd_z, int B, const float* msg_init_x,
                            const float* msg_init_z, float* llr_out, uint8_t* x_hat, uint8_t* z_hat, float* x_logit,
                            float* z_logit, float* msg_out_x, float* msg_out_z, const int* index, uint8_t* flagged,
-                           float* trace_x, float* trace_z, float* tape_x, float* tape_z, void* stream)
+                           float* trace_x, float* trace_z, float* tape_x, float* tape_z, float llr_bound, void* stream)
 {
     if (!g) return fgnn_fail(FGNN_ERR_ARG, "graph is NULL");
     if (B < 0 || num_iter < 0) return fgnn_fail(FGNN_ERR_ARG, "B and num_iter must be >= 0");
@@ -1141,7 +1190,7 @@ static int bp4_decode_core(const fgnn_graph* g, int cn_type, int num_iter, float
     a.trace_z = trace_z;
     a.tape_x = tape_x;
     a.tape_z = tape_z;
-    const Bp4Plan p = plan_bp4(g, cn_type, L, a);
+    const Bp4Plan p = plan_bp4(g, cn_type, L, a, llr_bound);
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (p.gmem) {
         // The codeword's state does not fit a CU's LDS (about E + 3n > 40 000 floats): run the same runtime-degree kernel with that
@@ -1180,11 +1229,12 @@ static int bp4_decode_core(const fgnn_graph* g, int cn_type, int num_iter, float
 int fgnn_bp4_decode_impl(const fgnn_graph* g, int cn_type, int num_iter, float normalization_factor, const float* llr_ch,
                          float llr_const, const uint8_t* synd_x, const uint8_t* synd_z, int B, const float* msg_init_x,
                          const float* msg_init_z, float* llr_out, uint8_t* x_hat, uint8_t* z_hat, float* x_logit,
-                         float* z_logit, float* msg_out_x, float* msg_out_z, const int* index, uint8_t* flagged, void* stream)
+                         float* z_logit, float* msg_out_x, float* msg_out_z, const int* index, uint8_t* flagged, float llr_bound,
+                         void* stream)
 {
     return bp4_decode_core(g, cn_type, num_iter, normalization_factor, llr_ch, llr_const, synd_x, synd_z, B, msg_init_x, msg_init_z,
                            llr_out, x_hat, z_hat, x_logit, z_logit, msg_out_x, msg_out_z, index, flagged, nullptr, nullptr, nullptr,
-                           nullptr, stream);
+                           nullptr, llr_bound, stream);
 }
 
 extern "C" int fgnn_bp4_decode_trace(const fgnn_graph* g, int cn_type, int num_iter, float normalization_factor,
@@ -1200,7 +1250,7 @@ extern "C" int fgnn_bp4_decode_trace(const fgnn_graph* g, int cn_type, int num_i
         return fgnn_fail(FGNN_ERR_STATE, "logit row sets not installed (fgnn_graph_set_rows)");
     return bp4_decode_core(g, cn_type, num_iter, normalization_factor, llr_ch, llr_const, synd_x, synd_z, B, msg_init_x, msg_init_z,
                            llr_out, x_hat, z_hat, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, x_logit_trace,
-                           z_logit_trace, tape_x, tape_z, stream);
+                           z_logit_trace, tape_x, tape_z, INFINITY, stream);
 }
 
 extern "C" int fgnn_bp4_decode(const fgnn_graph* g, int cn_type, int num_iter, float normalization_factor,
@@ -1209,6 +1259,8 @@ extern "C" int fgnn_bp4_decode(const fgnn_graph* g, int cn_type, int num_iter, f
                                uint8_t* z_hat, float* x_logit, float* z_logit, float* msg_out_x, float* msg_out_z,
                                void* stream)
 {
+    // a caller's own llr_ch comes without a bound: the guarded kernels (a constant channel LLR is its own bound, see plan_bp4)
     return fgnn_bp4_decode_impl(g, cn_type, num_iter, normalization_factor, llr_ch, llr_const, synd_x, synd_z, B, msg_init_x,
-                                msg_init_z, llr_out, x_hat, z_hat, x_logit, z_logit, msg_out_x, msg_out_z, nullptr, nullptr, stream);
+                                msg_init_z, llr_out, x_hat, z_hat, x_logit, z_logit, msg_out_x, msg_out_z, nullptr, nullptr, INFINITY,
+                                stream);
 }

@@ -788,6 +788,22 @@ extern "C" int fgnn_weights_create(const float* const host_arrays[12], int devic
     w->d.msg_rows[1] = base + off_mr[1];
     w->d.emb_rows = base + off_er;
     w->d.emb_quads = base + off_eq;
+    // |out_i| = |sum_j h_j W_out[j][i] + b_out[i]| with |h_j| <= 1 (fg_tanh clamps its result, in gnn_kernel, the MFMA kernel and the
+    // streaming kernels alike): at most sum_j |W_out[j][i]| + |b_out[i]|.  In double, with 1e-5 for the float32 accumulation of the
+    // 40 terms in whatever order a kernel takes them (each rounding is within 2^-24 of a partial sum below the bound: 41 * 2^-24 =
+    // 2.5e-6), rounded up to float.  The weights are a launch argument that stays the same from call to call: computed once, here.
+    {
+        double worst = 0.0;
+        for (int i = 0; i < 3; ++i) {
+            double s = std::fabs((double)host_arrays[1][i]);
+            for (int j = 0; j < HID; ++j) s += std::fabs((double)host_arrays[0][j * 3 + i]);
+            worst = s > worst || !(s == s) ? s : worst;  // a NaN weight stays a NaN: no bound
+        }
+        worst *= 1.0 + 1e-5;
+        float f = (float)worst;
+        if ((double)f < worst) f = std::nextafterf(f, INFINITY);
+        w->llr_out_bound = std::isfinite(f) ? f : INFINITY;
+    }
     *out = w;
     return FGNN_OK;
 }

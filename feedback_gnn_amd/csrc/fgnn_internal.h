@@ -1,6 +1,7 @@
 // fgnn_internal.h — shared declarations of libfgnn_hip.so (not part of the C ABI).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 #include <string>
 #include <vector>
@@ -111,6 +112,10 @@ struct fgnn_weights {
     void* blob;
     bool general = false;
     GnnGeneralDev gen;
+    // host side: an upper bound of |out| over every input, max_i (sum_j |W_out[j][i]| + |b_out[i]|) rounded up — the last hidden layer
+    // of the shipped network ends in fg_tanh's clamp to [-1, 1] in both of its kernels.  +inf for the runtime-shaped network, whose
+    // last hidden activation need not be bounded.  The sandwich hands it to the decoder that reads the output (plan_bp4).
+    float llr_out_bound = INFINITY;
 };
 
 // What the GNN_BP4 tape forward and reverse pass (fgnn_gnnbp4_backward.hip) read of a weight handle made by
@@ -232,11 +237,14 @@ LaunchGeom fgnn_geom(const fgnn_graph* g, int B);
 int fgnn_graph_ensure_layers(const fgnn_graph* g);
 
 // internal entry points with an optional slot->sample indirection (compacted sandwich rounds); bp4: flagged[b] (optional) = the
-// decision's syndrome differs from the measured one — the sandwich's flag test fused into the decoder's epilogue
+// decision's syndrome differs from the measured one — the sandwich's flag test fused into the decoder's epilogue; llr_bound = what
+// the caller guarantees about llr_ch, |llr_ch[.]| <= llr_bound (INFINITY: nothing), from which the launch may prove its kernel's
+// arguments bounded (plan_bp4)
 int fgnn_bp4_decode_impl(const fgnn_graph* g, int cn_type, int num_iter, float normalization_factor, const float* llr_ch,
                          float llr_const, const uint8_t* synd_x, const uint8_t* synd_z, int B, const float* msg_init_x,
                          const float* msg_init_z, float* llr_out, uint8_t* x_hat, uint8_t* z_hat, float* x_logit,
-                         float* z_logit, float* msg_out_x, float* msg_out_z, const int* index, uint8_t* flagged, void* stream);
+                         float* z_logit, float* msg_out_x, float* msg_out_z, const int* index, uint8_t* flagged, float llr_bound,
+                         void* stream);
 int fgnn_feedback_gnn_impl(const fgnn_graph* g, const fgnn_weights* w, const float* llr, const float* logit_hx,
                            const float* logit_hz, const uint8_t* synd_x, const uint8_t* synd_z, int B, float* out,
                            const int* index, void* stream);

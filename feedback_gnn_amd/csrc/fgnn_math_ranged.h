@@ -90,4 +90,39 @@ FG_FN float fg_softplus_max(float t)
     return (t < -FG_SOFTPLUS_THRESH) ? small : m;
 }
 
+/* ---- arguments bounded by the launch --------------------------------------------------------------------------------------------
+ * Two guards of the routines above exist for arguments the launch of a BP4 decoder can prove never occur (plan_bp4 in fgnn_bp4.hip
+ * makes the proof from the launch arguments; a decode it cannot prove takes the routines above):
+ *   log-sum-exp : min(d, 20) keeps fg_exp inside its domain, which ends at -87.  For 20 < d <= 87 the exponential is evaluated at -d
+ *                 instead of -20 and y = fg_exp(-d) <= fg_exp(-20) = 2.06e-9 < 2^-24 either way: 1 + y == 1.0f, and the log of 1.0f is
+ *                 +0.  Below 20 the minimum is d itself.
+ *   softplus    : the lower bound of the clamp and the select on t < -87 act below -87 only.
+ * With |t| and d at most FG_BOUNDED_MAX the guarded and the bounded forms return the same bits (tests/test_math_bounded.py:
+ * exhaustive over the range).  The distance from 80 to the domain's edge at 87 is deliberate: the proof of the launch is made in exact
+ * arithmetic and the float sums it speaks of round. */
+#define FG_BOUNDED_MAX 80.0f
+
+/* fg_softplus_max(t) for |t| <= FG_BOUNDED_MAX: the same operations in the same order, the clamp's upper bound alone, no flush */
+FG_FN float fg_softplus_bounded(float t)
+{
+    float tc = FG_MIN(t, FG_SOFTPLUS_THRESH);
+    float y = fg_exp(tc);
+    float l = fg_log1p(y);
+    float m = FG_MAX(t, l);
+    return (t < -FG_SOFTPLUS_THRESH) ? y : m;
+}
+
+/* fg_lse2_corr_ranged / fg_lse2_ranged for |a - b| <= FG_BOUNDED_MAX: the exponential at -d itself */
+FG_FN float fg_lse2_corr_bounded(float a, float b)
+{
+    float d = FG_ABS(a - b);
+    float y = fg_exp(-d);
+    return fg_log_1to2(1.0f + y);
+}
+FG_FN float fg_lse2_bounded(float a, float b)
+{
+    float m = FG_MAX(a, b);
+    return fg_lse2_corr_bounded(a, b) + m;
+}
+
 #endif /* FGNN_MATH_RANGED_H */

@@ -125,7 +125,7 @@ extern "C" int fgnn_sandwich_decode(const fgnn_graph* g, int num_layers, const i
     const bool fuse = g->cpb == 1;
     rc = fgnn_bp4_decode_impl(g, cn_types[0], iters[0], factors[0], nullptr, llr_const, synd_x, synd_z, B, nullptr, nullptr,
                               ws.llr_a, x_hat, z_hat, only ? nullptr : ws.xlogit, only ? nullptr : ws.zlogit, nullptr, nullptr,
-                              nullptr, (fuse && !only) ? ws.errors : nullptr, stream);
+                              nullptr, (fuse && !only) ? ws.errors : nullptr, INFINITY, stream);
     if (rc) return rc;
     const int blk = (B + 255) / 256;
     if (num_layers > 1 && !fuse) rc = fgnn_launch(fill_u8, dim3(blk), dim3(256), 0, st, ws.errors, (uint8_t)1, B);  // (:322)
@@ -163,7 +163,8 @@ extern "C" int fgnn_sandwich_decode(const fgnn_graph* g, int num_layers, const i
         const bool last = i == num_layers - 1;
         rc = fgnn_bp4_decode_impl(g, cn_types[i], iters[i], factors[i], ws.llr_b, 0.0f, synd_x, synd_z, nact, nullptr, nullptr,
                                   ws.llr_a, ws.x_upd, ws.z_upd, last ? nullptr : ws.xlogit, last ? nullptr : ws.zlogit, nullptr,
-                                  nullptr, index, (fuse && !last) ? ws.fnext : nullptr, stream);  // (:336)
+                                  nullptr, index, (fuse && !last) ? ws.fnext : nullptr, weights[i - 1]->llr_out_bound,
+                                  stream);  // (:336; ws.llr_b is weights[i - 1]'s output: its bound goes with it)
         if (rc) return rc;
         rc = fgnn_merge_impl(ws.errors, ws.x_upd, ws.z_upd, nact, n, x_hat, z_hat, index, stream);  // (:339-340)
         if (rc) return rc;

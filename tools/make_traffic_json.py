@@ -90,10 +90,11 @@ for spec in sys.argv[2:]:
         # the FIRST decoder's launch (constant channel LLR: template argument NQ = 0) — the later decoders of a sandwich carry
         # their per-qubit channel LLRs in registers (NQ = 4 / 5) and are a different instantiation
         # (template tail: ..., NQ, TRACE, GMEM, LSE> — LSE appeared in round 6: 0 = literal, 1 = shared log-sum-exp (compile-time forms of
-        # the (3,3,6) phi kernels), 2 = chosen at run time; GMEM in round 5; the round-4 summaries end in NQ, TRACE>; NT follows LSE from round 8)
+        # the (3,3,6) phi kernels), 2 = chosen at run time; GMEM in round 5; the round-4 summaries end in NQ, TRACE>; NT follows LSE from round 8,
+        # BND — the bounded-argument variant — follows NT from round 11)
         want_lse = ("1", "2") if reassoc else ("0", "2")
         def is_first_decoder(nm):
-            m = re.search(r",\s*0,\s*false,\s*false,\s*([012])(?:,\s*\d+)?>$", nm)  # (round 8: a trailing NT, the compile-time trips)
+            m = re.search(r",\s*0,\s*false,\s*false,\s*([012])(?:,\s*\d+)?(?:,\s*(?:true|false))?>$", nm)  # (trailing NT, then BND)
             return m is not None and m.group(1) in want_lse
         bp = pick(rows, "bp4_kernel", is_first_decoder)
         if bp:
