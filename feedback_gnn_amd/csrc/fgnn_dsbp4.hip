@@ -5,8 +5,8 @@
 // and the decoder returns u_hat next to the data error.  A sample is solved when H e_hat == s ^ u_hat on both graphs.  The algorithm is
 // stated to the float operation at fgnn_dsbp4_decode in include/fgnn.h.  The kernel stands on the frame of the step-loop decoders
 // (fgnn_step.h): staged syndrome bits, a qubit's slots, a check's row and parity (started from s ^ u_hat), the output write; its
-// attempt walk, `tab` table and own-weight edge rule are mbp4_kernel's (fgnn_mbp4.hip).  Its own are the `uh` bytes, the soft check
-// rule and the addressing of its inputs (DsRows below, where the other four kernels use StepRows).
+// attempt walk, `tab` table and qubit phase are mbp4_kernel's and stbp4_kernel's too (fgnn_attempts.h, fgnn_step.h).  Its own are the
+// `uh` bytes, the soft check rule and its input addressing (DsRows; bp4gd, bp4fb, mbp4 and relay4 use StepRows, stbp4 its StIn).
 //
 // LDS of one codeword, in floats, each area rounded up to 4 floats:
 //   msg  [E_x + E_z]  c->v / v->c messages, bp4_kernel's layout
@@ -46,16 +46,13 @@ static_assert(FGNN_SOFT_BOXPLUS == FGNN_CN_BOXPLUS && FGNN_SOFT_BOXPLUS_PHI == F
 
 namespace {
 
-constexpr int DSBP4_MAX_ATTEMPTS = 64;
-
-struct DsArgs : StepArgs {
-    int pre_iter, attempt_iter, attempts, restart, u_off;
+struct DsArgs : AttemptArgs {
+    int u_off;
     float gamma_x, gamma_z;
     const float* synd_llr_x;  // [B,m_x] or null (gamma_x for every hx check)
     const float* synd_llr_z;  // [B,m_z] or null
     uint8_t* u_x_hat;         // [B,m_x]
     uint8_t* u_z_hat;         // [B,m_z]
-    float tab[2 * DSBP4_MAX_ATTEMPTS];  // factor[0..63], own[0..63]; entries from `attempts` on are 0 and never read
 };
 
 // This kernel's form of StepRows (fgnn_step.h): the inputs are addressed as the rows of the workgroup's first codeword, the same for
@@ -115,9 +112,6 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_
     float* msg = lds + (size_t)cwl * a.lds_per_cw;
     uint8_t* dec = reinterpret_cast<uint8_t*>(msg + a.d_off);
     uint8_t* uh = reinterpret_cast<uint8_t*>(msg + a.u_off);
-    float* tab = lds + (size_t)a.cpb * a.lds_per_cw;
-    int* stamp = reinterpret_cast<int*>(tab + 2 * DSBP4_MAX_ATTEMPTS);
-    int* ndone = stamp + a.cpb;
     const int n = g.n, m = g.m;
     const size_t b0 = (size_t)blockIdx.x * a.cpb;
     const float* gx0 = a.synd_llr_x ? a.synd_llr_x + b0 * g.m_x : nullptr;
@@ -125,8 +119,7 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_
     const float gamma_x = a.gamma_x, gamma_z = a.gamma_z;
 #define GAMMA_OF(c) gamma_at(gx0, gz0, gamma_x, gamma_z, cwl, g.m_x, g.m_z, (c))
 
-    for (int i = threadIdx.x; i < 2 * DSBP4_MAX_ATTEMPTS; i += blockDim.x) tab[i] = a.tab[i];
-    for (int i = threadIdx.x; i < a.cpb + 1; i += blockDim.x) stamp[i] = 0;  // stamp, ndone
+    const AttemptLds w = attempt_stage(lds, a);
     if (cw.active) {
         for (int e = lane; e < g.E; e += a.tpc) msg[e] = 0.0f;
         for (int v = lane; v < n; v += a.tpc) dec[v] = 0;
@@ -135,35 +128,24 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_
     const StepSynd synd(g, rows, cw, a.tpc);
     __syncthreads();
 
-    int r = 0, k = 0, its = 0;  // r < a.attempts <= 64 throughout: the last attempt ends the codeword
-    bool done = !cw.active;
+    AttemptCtl ctl(cw.active);
     for (int step = 1; step <= a.max_steps; ++step) {
-        const int T = (r == 0) ? a.pre_iter : a.attempt_iter;
+        const int T = ctl.T(a.sched), k = ctl.k;
         // ---- qubits: marginals after k check updates and their decision, messages to the checks ----
-        if (!done) {
-            const bool zero = a.restart && k == 0 && r > 0;  // a restarting attempt starts from zero messages
-            const float ow = tab[DSBP4_MAX_ATTEMPTS + r];
+        if (!ctl.done) {
+            const bool zero = ctl.zero(a.sched);
+            const float ow = w.tab[ATTEMPT_MAX + ctl.r];
             for (int v = lane; v < n; v += a.tpc) {
                 float lx, ly, lz;
                 rows.llrs(n, v, a.llr_const, lx, ly, lz);
-                QubitSlots<DV> q(g, msg, v);
-                if (zero) q.clear();
-                float Sz, Sx;
-                q.fetch(Sz, Sx);
-                float X, Y, Z;
-                vn_totals(Sz, Sx, lx, ly, lz, X, Y, Z);
-                if (k > 0) {  // the test's decision; an attempt's last test sends no messages
-                    dec[v] = (uint8_t)vn_decide(X, Y, Z);
-                    if (k == T) continue;
-                }
-                q.store(X, Y, Z, [&](float num, float A, float Ye, float mu) { return vn_edge_own<VnMath>(num, A, Ye, mu, ow); });
+                attempt_qubit<DV>(g, msg, v, lx, ly, lz, k, T, zero, ow, dec + v);
             }
         }
         __syncthreads();
-        if (*ndone == cw.nact) break;  // the same word for every thread, last written before the barrier above
+        if (*w.ndone == cw.nact) break;  // the same word for every thread, last written before the barrier above
         // ---- checks of both graphs: parity of the decisions against s ^ u_hat (k > 0), then the soft check update (k < T) ----
-        if (!done) {
-            const float fac = tab[r];
+        if (!ctl.done) {
+            const float fac = w.tab[ctl.r];
             // one check: c, its index i among the lane's checks, its syndrome LLR
             auto one_check = [&](const int c, const int i, const float gm) __attribute__((always_inline)) {
                 const unsigned sy = synd.at(g, rows, i, c);
@@ -182,20 +164,19 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_
                     if (k < T) un = soft_u_hat(gm, cn_soft_update<CN_TYPE, PhiSoft>(msg, g.cslot + c0, deg, sy, gm, fac));
                 }
                 uh[c] = (uint8_t)(un | (ut << 1));
-                if (odd) stamp[cwl] = step;
+                if (odd) w.stamp[cwl] = step;
             };
             int i = 0;
             for (int c = lane; c < m; c += a.tpc, ++i) one_check(c, i, k < T ? GAMMA_OF(c) : 0.0f);
         }
         __syncthreads();
         // ---- per codeword: solution found, attempt over, decoder finished ----
-        if (!done) {
+        if (!ctl.done) {
             if (k == 0) {
-                k = 1;
-                ++its;
+                ctl.more();  // an attempt's first step tests nothing
             } else {
-                const bool sat = stamp[cwl] != step;
-                if (sat || (k == T && r == a.attempts - 1)) {
+                const bool sat = w.stamp[cwl] != step;
+                if (sat || ctl.last(a.sched, T)) {
                     // the output rows are addressed from a laundered copy of b: formed here, once per codeword, instead of living in
                     // per-lane 64-bit registers through every step
                     int bo = cw.b;
@@ -207,14 +188,12 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_
                         if (c < g.m_x) a.u_x_hat[ob * g.m_x + c] = u;
                         else a.u_z_hat[ob * g.m_z + (c - g.m_x)] = u;
                     }
-                    if (lane == 0) step_finish(a, ob, sat, r, its, k, ndone);
-                    done = true;
+                    if (lane == 0) step_finish(a, ob, sat, ctl.r, ctl.its, k, w.ndone);
+                    ctl.done = true;
                 } else if (k == T) {
-                    ++r;
-                    k = 0;
+                    ctl.again();
                 } else {
-                    ++k;
-                    ++its;
+                    ctl.more();
                 }
             }
         }
@@ -231,40 +210,27 @@ extern "C" int fgnn_dsbp4_decode(const fgnn_graph* g, int cn_type, int num_attem
                                  int B, uint8_t* x_hat, uint8_t* z_hat, uint8_t* u_x_hat, uint8_t* u_z_hat, int32_t* stats, void* stream)
 {
     if (int err = step_check_args(g, cn_type, B)) return err;
-    if (num_attempts < 1 || num_attempts > DSBP4_MAX_ATTEMPTS) return fgnn_fail(FGNN_ERR_ARG, "num_attempts must be in 1 .. 64");
-    if (pre_iter < 1 || attempt_iter < 1) return fgnn_fail(FGNN_ERR_ARG, "pre_iter and attempt_iter must be >= 1");
-    if (restart != 0 && restart != 1) return fgnn_fail(FGNN_ERR_ARG, "restart must be 0 or 1");
-    if (!factor || !own) return fgnn_fail(FGNN_ERR_ARG, "factor and own must hold num_attempts floats each");
-    for (int i = 0; i < num_attempts; ++i) {
-        if (!std::isfinite(factor[i]) || !(factor[i] > 0.0f)) return fgnn_fail(FGNN_ERR_ARG, "every factor must be finite and > 0");
-        if (!std::isfinite(own[i]) || own[i] < 0.0f) return fgnn_fail(FGNN_ERR_ARG, "every own weight must be finite and >= 0");
-    }
+    if (int err = attempt_check_sched(num_attempts, pre_iter, attempt_iter, restart)) return err;
+    if (int err = attempt_check_tables(num_attempts, factor, own)) return err;
     if (std::isnan(gamma_x) || std::isnan(gamma_z)) return fgnn_fail(FGNN_ERR_ARG, "gamma_x and gamma_z must not be NaN");
     if (B == 0) return FGNN_OK;  // an empty batch needs no buffers
     if (!x_hat || !z_hat || !u_x_hat || !u_z_hat || !stats) return fgnn_fail(FGNN_ERR_ARG, "no output buffer");
     FGNN_DEVICE_GUARD(g->device);
     const LaunchGeom L = fgnn_geom(g, B);
     DsArgs a;
-    step_args_fill(a, L, B, pre_iter, num_attempts - 1, attempt_iter, llr_ch, llr_const, synd_x, synd_z, x_hat, z_hat, stats);
-    a.pre_iter = pre_iter;
-    a.attempt_iter = attempt_iter;
-    a.attempts = num_attempts;
-    a.restart = restart;
+    attempt_args_fill(a, L, B, num_attempts, factor, own, pre_iter, attempt_iter, restart, llr_ch, llr_const, synd_x, synd_z, x_hat, z_hat,
+                      stats);
     a.gamma_x = gamma_x;
     a.gamma_z = gamma_z;
     a.synd_llr_x = synd_llr_x;
     a.synd_llr_z = synd_llr_z;
     a.u_x_hat = u_x_hat;
     a.u_z_hat = u_z_hat;
-    for (int i = 0; i < DSBP4_MAX_ATTEMPTS; ++i) {
-        a.tab[i] = i < num_attempts ? factor[i] : 0.0f;
-        a.tab[DSBP4_MAX_ATTEMPTS + i] = i < num_attempts ? own[i] : 0.0f;
-    }
     // per codeword: E messages, n decision bytes and m u_hat bytes; per workgroup: the two 64-float tables, a stamp per codeword and
     // ndone
     const size_t d_off = lds_round4(g->d.E), u_off = d_off + lds_bytes_as_floats(g->d.n);
     size_t lds_bytes;
-    if (int err = step_lds_bytes(a, "soft-syndrome BP4", u_off + lds_bytes_as_floats(g->d.m), 2 * DSBP4_MAX_ATTEMPTS, L.cpb + 1, &lds_bytes))
+    if (int err = step_lds_bytes(a, "soft-syndrome BP4", u_off + lds_bytes_as_floats(g->d.m), 2 * ATTEMPT_MAX, L.cpb + 1, &lds_bytes))
         return err;
     a.d_off = (int)d_off;
     a.u_off = (int)u_off;

@@ -4,10 +4,10 @@
 // "time" variables u_{c,t} between check c of round t and check c of round t + 1; the time variable of the last round has degree one,
 // which is soft-syndrome BP4's extra input, so R = 1 is fgnn_dsbp4_decode bit for bit.  The algorithm is stated to the float operation
 // at fgnn_stbp4_decode in include/fgnn.h.  The kernel is a sibling of dsbp4_kernel (fgnn_dsbp4.hip) on the frame of the step-loop
-// decoders (fgnn_step.h): a qubit's slots, the parity of a check's row, the stats words; its attempt walk, `tab` table and own-weight
-// edge rule are mbp4_kernel's (fgnn_mbp4.hip).  Its own are the window, the time variables and the check rule with one or two
-// time-like inputs (fgnn_cn_st.h).  Instantiations and dispatch as dsbp4_kernel: the runtime-degree loop for each check rule, and
-// min-sum on the packed rows of a (3,3,6)-regular graph, whose BYTE offsets are taken from the round's message area.
+// decoders (fgnn_step.h): the parity of a check's row, the stats words; its attempt walk, `tab` table and the qubit phase of a round's
+// qubit are the ones mbp4_kernel and dsbp4_kernel run (fgnn_attempts.h, fgnn_step.h).  Its own are the window, the time variables and
+// the check rule with one or two time-like inputs (fgnn_cn_st.h).  Instantiations and dispatch as dsbp4_kernel: the runtime-degree loop
+// for each check rule, and min-sum on the packed rows of a (3,3,6)-regular graph, whose BYTE offsets are taken from the round's area.
 //
 // LDS of one window, in floats, each area rounded up to 4 floats:
 //   msg  R x [E_x + E_z]   c->v / v->c messages of round t at msg + t * area, bp4_kernel's slot layout
@@ -52,10 +52,8 @@ static_assert(FGNN_SOFT_BOXPLUS == FGNN_CN_BOXPLUS && FGNN_SOFT_BOXPLUS_PHI == F
 
 namespace {
 
-constexpr int STBP4_MAX_ATTEMPTS = 64;
-
-struct StArgs : StepArgs {  // synd_x [B,R,m_x], synd_z [B,R,m_z], x_hat and z_hat [B,R,n]
-    int pre_iter, attempt_iter, attempts, restart, rounds;
+struct StArgs : AttemptArgs {  // synd_x [B,R,m_x], synd_z [B,R,m_z], x_hat and z_hat [B,R,n]
+    int rounds;
     int area, b_off, a_off, u_off;  // floats: a round's message area; the b, a and uh areas from the window's start (dec: d_off)
     float gamma_x, gamma_z, gamma_last_x, gamma_last_z;
     const float* synd_llr_x;  // [B,R,m_x] or null
@@ -64,7 +62,6 @@ struct StArgs : StepArgs {  // synd_x [B,R,m_x], synd_z [B,R,m_z], x_hat and z_h
     const uint8_t* prev_z;    // [B,m_z] or null
     uint8_t* u_x_hat;         // [B,R,m_x]
     uint8_t* u_z_hat;         // [B,R,m_z]
-    float tab[2 * STBP4_MAX_ATTEMPTS];  // factor[0..63], own[0..63]; entries from `attempts` on are 0 and never read
 };
 
 // What the lanes read of the arguments beside the frame's, copied out once by value: a select between a field of the argument struct
@@ -144,17 +141,13 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_
     float* asl = win + a.a_off;
     uint8_t* dec = reinterpret_cast<uint8_t*>(win + a.d_off);
     uint8_t* uh = reinterpret_cast<uint8_t*>(win + a.u_off);
-    float* tab = lds + (size_t)a.cpb * a.lds_per_cw;
-    int* stamp = reinterpret_cast<int*>(tab + 2 * STBP4_MAX_ATTEMPTS);
-    int* ndone = stamp + a.cpb;
     const int n = g.n, m = g.m, R = a.rounds, NQ = R * n, NC = R * m;
     const size_t row = cw.active ? (size_t)cw.b : 0;
     const StIn in(a);
     const float llr_const = a.llr_const;  // by value: lch ? lch[v] : a.llr_const would select between two addresses
     const float* lch = a.llr_ch ? a.llr_ch + row * 3 * n : nullptr;
 
-    for (int i = threadIdx.x; i < 2 * STBP4_MAX_ATTEMPTS; i += blockDim.x) tab[i] = a.tab[i];
-    for (int i = threadIdx.x; i < a.cpb + 1; i += blockDim.x) stamp[i] = 0;  // stamp, ndone
+    const AttemptLds w = attempt_stage(lds, a);
     if (cw.active) {
         for (int e = lane; e < a.d_off; e += a.tpc) win[e] = 0.0f;  // the messages of every round, b and a
         for (int i = lane; i < NQ; i += a.tpc) dec[i] = 0;
@@ -163,30 +156,19 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_
     const StSynd synd(g, in, cw, row, a.tpc);
     __syncthreads();
 
-    int r = 0, k = 0, its = 0;  // r < a.attempts <= 64 throughout: the last attempt ends the window
-    bool done = !cw.active;
+    AttemptCtl ctl(cw.active);
     for (int step = 1; step <= a.max_steps; ++step) {
-        const int T = (r == 0) ? a.pre_iter : a.attempt_iter;
+        const int T = ctl.T(a.sched), k = ctl.k;
         // ---- qubits of every round, then the time variables: marginals after k check updates, their decisions, messages to the checks ----
-        if (!done) {
-            const bool zero = a.restart && k == 0 && r > 0;  // a restarting attempt starts from zero messages
-            const float ow = tab[STBP4_MAX_ATTEMPTS + r];
+        if (!ctl.done) {
+            const bool zero = ctl.zero(a.sched);
+            const float ow = w.tab[ATTEMPT_MAX + ctl.r];
             for (int i = lane, v = lane, t = 0; i < NQ; i += a.tpc, v += a.tpc) {
                 while (v >= n) { v -= n; ++t; }
                 const float lx = lch ? lch[v] : llr_const;
                 const float ly = lch ? lch[n + v] : llr_const;
                 const float lz = lch ? lch[2 * n + v] : llr_const;
-                QubitSlots<DV> q(g, win + t * a.area, v);
-                if (zero) q.clear();
-                float Sz, Sx;
-                q.fetch(Sz, Sx);
-                float X, Y, Z;
-                vn_totals(Sz, Sx, lx, ly, lz, X, Y, Z);
-                if (k > 0) {  // the test's decision; an attempt's last test sends no messages
-                    dec[i] = (uint8_t)vn_decide(X, Y, Z);
-                    if (k == T) continue;
-                }
-                q.store(X, Y, Z, [&](float num, float A, float Ye, float mu) { return vn_edge_own<VnMath>(num, A, Ye, mu, ow); });
+                attempt_qubit<DV>(g, win + t * a.area, v, lx, ly, lz, k, T, zero, ow, dec + i);
             }
             for (int j = lane, c = lane, t = 0; j < NC; j += a.tpc, c += a.tpc) {
                 while (c >= m) { c -= m; ++t; }
@@ -209,10 +191,10 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_
             }
         }
         __syncthreads();
-        if (*ndone == cw.nact) break;  // the same word for every thread, last written before the barrier above
+        if (*w.ndone == cw.nact) break;  // the same word for every thread, last written before the barrier above
         // ---- checks of both graphs in every round: parity of the decisions against d ^ u_hat_t ^ u_hat_{t-1} (k > 0), update (k < T) ----
-        if (!done) {
-            const float fac = tab[r];
+        if (!ctl.done) {
+            const float fac = w.tab[ctl.r];
             int idx = 0;
             for (int j = lane, c = lane, t = 0; j < NC; j += a.tpc, c += a.tpc, ++idx) {
                 while (c >= m) { c -= m; ++t; }
@@ -226,7 +208,7 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_
                 if constexpr (REGULAR) {
                     unsigned off[DC];
                     row_unpack(g, c, off);
-                    if (k > 0 && parity_regular<DV>(g, dec + t * n, off, c < g.m_x, par) != 0u) stamp[cwl] = step;
+                    if (k > 0 && parity_regular<DV>(g, dec + t * n, off, c < g.m_x, par) != 0u) w.stamp[cwl] = step;
                     if (k < T) {
                         if (t == 0) {
                             float x[1] = {bsl[j]};
@@ -241,7 +223,7 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_
                     }
                 } else {
                     const int c0 = g.cptr[c], deg = g.cptr[c + 1] - c0;
-                    if (k > 0 && parity_csr(g, dec + t * n, c0, deg, c < g.m_x, par) != 0u) stamp[cwl] = step;
+                    if (k > 0 && parity_csr(g, dec + t * n, c0, deg, c < g.m_x, par) != 0u) w.stamp[cwl] = step;
                     if (k < T) {
                         if (t == 0) {
                             float x[1] = {bsl[j]};
@@ -259,31 +241,24 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_
         }
         __syncthreads();
         // ---- per window: solution found, attempt over, decoder finished ----
-        if (!done) {
+        if (!ctl.done) {
             if (k == 0) {
-                k = 1;
-                ++its;
+                ctl.more();  // an attempt's first step tests nothing
             } else {
-                const bool sat = stamp[cwl] != step;
-                if (sat || (k == T && r == a.attempts - 1)) {
-                    for (int i = lane; i < NQ; i += a.tpc) {
-                        const unsigned d = dec[i];
-                        a.x_hat[row * NQ + i] = (uint8_t)(d & 1u);
-                        a.z_hat[row * NQ + i] = (uint8_t)(d >> 1);
-                    }
+                const bool sat = w.stamp[cwl] != step;
+                if (sat || ctl.last(a.sched, T)) {
+                    step_write_decisions(a, dec, row, NQ, lane);  // the window's R rows of n as one row of R n
                     for (int j = lane, c = lane, t = 0; j < NC; j += a.tpc, c += a.tpc) {
                         while (c >= m) { c -= m; ++t; }
                         if (c < g.m_x) a.u_x_hat[(row * R + t) * g.m_x + c] = uh[j];
                         else a.u_z_hat[(row * R + t) * g.m_z + (c - g.m_x)] = uh[j];
                     }
-                    if (lane == 0) step_finish(a, row, sat, r, its, k, ndone);
-                    done = true;
+                    if (lane == 0) step_finish(a, row, sat, ctl.r, ctl.its, k, w.ndone);
+                    ctl.done = true;
                 } else if (k == T) {
-                    ++r;
-                    k = 0;
+                    ctl.again();
                 } else {
-                    ++k;
-                    ++its;
+                    ctl.more();
                 }
             }
         }
@@ -307,7 +282,7 @@ struct StLayout {
 // per window: the layout above; per workgroup: the two 64-float tables, a stamp per window and ndone
 size_t st_lds_bytes(const GraphDev& d, int R, int cpb)
 {
-    return StLayout(d, R).per_win * sizeof(float) * (size_t)cpb + 2 * STBP4_MAX_ATTEMPTS * sizeof(float) + lds_round4((size_t)cpb + 1) * sizeof(int);
+    return StLayout(d, R).per_win * sizeof(float) * (size_t)cpb + 2 * ATTEMPT_MAX * sizeof(float) + lds_round4((size_t)cpb + 1) * sizeof(int);
 }
 
 // The launch of a window: R n qubits and R m checks per "codeword".  A caller's fgnn_graph_set_launch is taken as it is; else the
@@ -349,15 +324,9 @@ extern "C" int fgnn_stbp4_decode(const fgnn_graph* g, int cn_type, int num_attem
                                  uint8_t* z_hat, uint8_t* u_x_hat, uint8_t* u_z_hat, int32_t* stats, void* stream)
 {
     if (int err = step_check_args(g, cn_type, B)) return err;
-    if (num_attempts < 1 || num_attempts > STBP4_MAX_ATTEMPTS) return fgnn_fail(FGNN_ERR_ARG, "num_attempts must be in 1 .. 64");
-    if (pre_iter < 1 || attempt_iter < 1) return fgnn_fail(FGNN_ERR_ARG, "pre_iter and attempt_iter must be >= 1");
-    if (restart != 0 && restart != 1) return fgnn_fail(FGNN_ERR_ARG, "restart must be 0 or 1");
+    if (int err = attempt_check_sched(num_attempts, pre_iter, attempt_iter, restart)) return err;
     if (rounds < 1) return fgnn_fail(FGNN_ERR_ARG, "rounds must be >= 1");
-    if (!factor || !own) return fgnn_fail(FGNN_ERR_ARG, "factor and own must hold num_attempts floats each");
-    for (int i = 0; i < num_attempts; ++i) {
-        if (!std::isfinite(factor[i]) || !(factor[i] > 0.0f)) return fgnn_fail(FGNN_ERR_ARG, "every factor must be finite and > 0");
-        if (!std::isfinite(own[i]) || own[i] < 0.0f) return fgnn_fail(FGNN_ERR_ARG, "every own weight must be finite and >= 0");
-    }
+    if (int err = attempt_check_tables(num_attempts, factor, own)) return err;
     if (std::isnan(gamma_x) || std::isnan(gamma_z) || std::isnan(gamma_last_x) || std::isnan(gamma_last_z))
         return fgnn_fail(FGNN_ERR_ARG, "gamma_x, gamma_z, gamma_last_x and gamma_last_z must not be NaN");
     // the window must fit the LDS, whatever the batch: one window per workgroup is the least a launch can ask for
@@ -374,11 +343,8 @@ extern "C" int fgnn_stbp4_decode(const fgnn_graph* g, int cn_type, int num_attem
     FGNN_DEVICE_GUARD(g->device);
     const LaunchGeom L = st_geom(g, B, rounds);
     StArgs a;
-    step_args_fill(a, L, B, pre_iter, num_attempts - 1, attempt_iter, llr_ch, llr_const, synd_x, synd_z, x_hat, z_hat, stats);
-    a.pre_iter = pre_iter;
-    a.attempt_iter = attempt_iter;
-    a.attempts = num_attempts;
-    a.restart = restart;
+    attempt_args_fill(a, L, B, num_attempts, factor, own, pre_iter, attempt_iter, restart, llr_ch, llr_const, synd_x, synd_z, x_hat, z_hat,
+                      stats);
     a.rounds = rounds;
     a.gamma_x = gamma_x;
     a.gamma_z = gamma_z;
@@ -390,10 +356,6 @@ extern "C" int fgnn_stbp4_decode(const fgnn_graph* g, int cn_type, int num_attem
     a.prev_z = prev_z;
     a.u_x_hat = u_x_hat;
     a.u_z_hat = u_z_hat;
-    for (int i = 0; i < STBP4_MAX_ATTEMPTS; ++i) {
-        a.tab[i] = i < num_attempts ? factor[i] : 0.0f;
-        a.tab[STBP4_MAX_ATTEMPTS + i] = i < num_attempts ? own[i] : 0.0f;
-    }
     const StLayout lay(g->d, rounds);
     a.area = (int)lay.area;
     a.b_off = (int)lay.b_off;

@@ -1,25 +1,32 @@
 // fgnn_step.h — the frame of the step-loop BP4 decoders: bp4gd_kernel (fgnn_bp4gd.hip), bp4fb_kernel (fgnn_bp4fb.hip), mbp4_kernel
-// (fgnn_mbp4.hip), dsbp4_kernel (fgnn_dsbp4.hip) and relay4_kernel (fgnn_relay4.hip).
+// (fgnn_mbp4.hip), dsbp4_kernel (fgnn_dsbp4.hip), stbp4_kernel (fgnn_stbp4.hip) and relay4_kernel (fgnn_relay4.hip).
 //
-// The five kernels keep several codewords in the LDS of a workgroup and walk each through workgroup steps of one qubit phase, one
+// The six kernels keep several codewords in the LDS of a workgroup and walk each through workgroup steps of one qubit phase, one
 // check phase and a control section.  What is the same in all of them has its one statement here:
 //   StepCw / StepRows / StepSynd   which codeword a thread works on, the codeword's input rows, its syndrome bits staged in a register
 //   QubitSlots<DV>                 a qubit's message slots: pre-clear, fetch with the sums Sz and Sx, store through the kernel's edge rule
 //   row_unpack / parity_*          a check's packed row, and the parity of the decisions over a check's qubits
 //   step_write_decisions / step_finish   dec -> x_hat | z_hat, the four stats words and ndone
 // and on the host StepArgs (the head of every kernel's argument struct), the LDS arithmetic, the LDS refusal and the dispatch over
-// (check rule, regular 3-3-6).  Each kernel keeps its own step loop, barriers, control section, LDS order, waves-per-SIMD value and
-// whatever makes it that decoder.  Every float operation stays where it was: the sums run hz before hx, each ascending from 0.
+// (check rule, regular 3-3-6).  Each kernel keeps its own step loop, barriers, LDS order, waves-per-SIMD value and whatever makes it
+// that decoder.  bp4gd_kernel, bp4fb_kernel and relay4_kernel have a control section each.  mbp4_kernel, dsbp4_kernel and
+// stbp4_kernel share one, the attempt schedule of fgnn_attempts.h (AttemptSched, AttemptCtl, the step bound), and with it
+//   AttemptArgs, attempt_check_* / attempt_args_fill   the schedule in the argument struct, its argument checks and its fill
+//   attempt_stage                  tab, stamp and ndone staged into LDS behind the codewords
+//   attempt_qubit<DV>              the qubit phase of one qubit: decision after k updates, messages with own[r]
+// Every float operation stays where it was: the sums run hz before hx, each ascending from 0.
 #ifndef FGNN_STEP_H
 #define FGNN_STEP_H
 
 #include <algorithm>
 #include <climits>
+#include <cmath>
 #include <type_traits>
 
 #include "fgnn_internal.h"
 #include "fgnn_math.h"
 #include "fgnn_vn.h"
+#include "fgnn_attempts.h"
 
 // ---------------------------------------------------------------------------------------------
 // Host side
@@ -37,16 +44,15 @@ struct StepArgs {
     int32_t* stats;          // [B,4]
 };
 
-// a codeword takes T + 1 steps per run (round, attempt, leg) of T check updates: the first run of pre_iter, `later` more of `iter`;
-// one more step lets the workgroup see its last codeword finished
+// the first run (round, attempt, leg) of a codeword has pre_iter check updates, `later` more have `iter`: max_steps is
+// attempt_step_bound (fgnn_attempts.h)
 inline void step_args_fill(StepArgs& a, const LaunchGeom& L, int B, int pre_iter, long long later, int iter, const float* llr_ch,
                            float llr_const, const uint8_t* synd_x, const uint8_t* synd_z, uint8_t* x_hat, uint8_t* z_hat, int32_t* stats)
 {
-    const long long steps = (long long)pre_iter + 1 + later * ((long long)iter + 1) + 1;
     a.B = B;
     a.tpc = L.tpc;
     a.cpb = L.cpb;
-    a.max_steps = (int)std::min<long long>(steps, INT_MAX - 1);
+    a.max_steps = attempt_step_bound(pre_iter, later, iter);
     a.llr_const = llr_const;
     a.llr_ch = llr_ch;
     a.synd_x = synd_x;
@@ -80,6 +86,46 @@ inline int step_check_args(const fgnn_graph* g, int cn_type, int B)
     if (cn_type < 0 || cn_type > 2) return fgnn_fail(FGNN_ERR_ARG, "Unknown node type.");  // decoding_q.py:107
     if (B < 0) return fgnn_fail(FGNN_ERR_ARG, "B must be >= 0");
     return FGNN_OK;
+}
+
+// what a kernel on the attempt schedule is told; MbArgs, DsArgs and StArgs derive from it
+struct AttemptArgs : StepArgs {
+    AttemptSched sched;
+};
+
+// the checks of the schedule that follow step_check_args, in two parts: a decoder may test arguments of its own between the numbers
+// and the tables (fgnn_stbp4_decode: rounds) and after the tables (the gammas)
+inline int attempt_check_sched(int num_attempts, int pre_iter, int attempt_iter, int restart)
+{
+    if (num_attempts < 1 || num_attempts > ATTEMPT_MAX) return fgnn_fail(FGNN_ERR_ARG, "num_attempts must be in 1 .. 64");
+    if (pre_iter < 1 || attempt_iter < 1) return fgnn_fail(FGNN_ERR_ARG, "pre_iter and attempt_iter must be >= 1");
+    if (restart != 0 && restart != 1) return fgnn_fail(FGNN_ERR_ARG, "restart must be 0 or 1");
+    return FGNN_OK;
+}
+inline int attempt_check_tables(int num_attempts, const float* factor, const float* own)
+{
+    if (!factor || !own) return fgnn_fail(FGNN_ERR_ARG, "factor and own must hold num_attempts floats each");
+    for (int i = 0; i < num_attempts; ++i) {
+        if (!std::isfinite(factor[i]) || !(factor[i] > 0.0f)) return fgnn_fail(FGNN_ERR_ARG, "every factor must be finite and > 0");
+        if (!std::isfinite(own[i]) || own[i] < 0.0f) return fgnn_fail(FGNN_ERR_ARG, "every own weight must be finite and >= 0");
+    }
+    return FGNN_OK;
+}
+
+// step_args_fill and the schedule of a checked call
+inline void attempt_args_fill(AttemptArgs& a, const LaunchGeom& L, int B, int num_attempts, const float* factor, const float* own, int pre_iter,
+                              int attempt_iter, int restart, const float* llr_ch, float llr_const, const uint8_t* synd_x,
+                              const uint8_t* synd_z, uint8_t* x_hat, uint8_t* z_hat, int32_t* stats)
+{
+    step_args_fill(a, L, B, pre_iter, num_attempts - 1, attempt_iter, llr_ch, llr_const, synd_x, synd_z, x_hat, z_hat, stats);
+    a.sched.pre_iter = pre_iter;
+    a.sched.attempt_iter = attempt_iter;
+    a.sched.attempts = num_attempts;
+    a.sched.restart = restart;
+    for (int i = 0; i < ATTEMPT_MAX; ++i) {
+        a.sched.tab[i] = i < num_attempts ? factor[i] : 0.0f;
+        a.sched.tab[ATTEMPT_MAX + i] = i < num_attempts ? own[i] : 0.0f;
+    }
 }
 
 // the graphs the (3,3,6) instantiations run: (3,3,6)-regular with packed check rows, unless the tests force the loop
@@ -243,6 +289,44 @@ struct QubitSlots {
         }
     }
 };
+
+// The per-workgroup words of a kernel on the attempt schedule, behind the cpb codewords: tab[128] = factor[0..63], own[0..63] (the
+// codewords of a workgroup sit at different attempts, so the two are indexed per lane), stamp[cpb] = the number of the last
+// workgroup step in which a check of the codeword saw odd parity, ndone = finished codewords.  Staged by the whole workgroup,
+// before the kernel's first barrier
+struct AttemptLds {
+    float* tab;
+    int* stamp;
+    int* ndone;
+};
+__device__ __forceinline__ AttemptLds attempt_stage(float* lds, const AttemptArgs& a)
+{
+    float* tab = lds + (size_t)a.cpb * a.lds_per_cw;
+    int* stamp = reinterpret_cast<int*>(tab + 2 * ATTEMPT_MAX);
+    for (int i = threadIdx.x; i < 2 * ATTEMPT_MAX; i += blockDim.x) tab[i] = a.sched.tab[i];
+    for (int i = threadIdx.x; i < a.cpb + 1; i += blockDim.x) stamp[i] = 0;  // stamp, ndone
+    return {tab, stamp, stamp + a.cpb};
+}
+
+// The qubit phase of qubit v at step k of an attempt of T check updates, on the slots of `msg` and the channel LLRs lx, ly, lz:
+// the marginals after k updates, for k > 0 the test's decision into *d, for k < T the messages to the checks with the own weight ow
+// (an attempt's last test sends none); zero: a restarting attempt's first step, the owner zeroes the qubit's slots first
+template <int DV>
+__device__ __forceinline__ void attempt_qubit(const GraphDev& g, float* msg, const int v, const float lx, const float ly, const float lz,
+                                              const int k, const int T, const bool zero, const float ow, uint8_t* d)
+{
+    QubitSlots<DV> q(g, msg, v);
+    if (zero) q.clear();
+    float Sz, Sx;
+    q.fetch(Sz, Sx);
+    float X, Y, Z;
+    vn_totals(Sz, Sx, lx, ly, lz, X, Y, Z);
+    if (k > 0) {
+        *d = (uint8_t)vn_decide(X, Y, Z);
+        if (k == T) return;
+    }
+    q.store(X, Y, Z, [&](float num, float A, float Ye, float mu) { return vn_edge_own<VnMath>(num, A, Ye, mu, ow); });
+}
 
 // the BYTE offsets of check c's slots from its packed row of g.cslot16
 template <int DC>
