@@ -31,6 +31,9 @@ def __getattr__(name):
     if name in ("OSD0_Decoder", "OSD_Decoder", "BP4_OSD_Model", "BP2_OSD_Model"):
         from . import bp_osd as _o
         return getattr(_o, name)
+    if name in ("LSD_Decoder", "BP4_LSD_Model", "BP2_LSD_Model"):
+        from . import lsd as _l
+        return getattr(_l, name)
     if name in ("RelayBPDecoder", "BP2_Relay_Model", "RelayBP4Decoder", "BP4_Relay_Model"):
         from . import relay as _r
         return getattr(_r, name)

@@ -137,6 +137,9 @@ _SIGNATURES = {
     "fgnn_osd_ws": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "fgnn_compact": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fgnn_lsd_max_pivots": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "fgnn_lsd": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                           C.c_void_p, C.c_void_p, C.c_void_p]),
     "fgnn_gnnbp4_weights_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "fgnn_gnnbp4_weights_destroy": (None, [C.c_void_p]),
     "fgnn_gnnbp4_weights_create_general": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),

@@ -797,6 +797,24 @@ class TannerGraph:
                                      int(nact), _ptr(e_hat), _ptr(chosen), _ptr(workspace), workspace.numel(), _stream(self.device)))
         return e_hat
 
+    # ---- cluster post-processing (fgnn_lsd) ------------------------------------------------------------------------
+    def lsd_max_pivots(self, side):
+        """The largest `max_pivots` `lsd` takes for side 0 (hx) / 1 (hz): min(m_side, n, what the LDS holds)."""
+        cap = C.c_int()
+        check(_lib.lib().fgnn_lsd_max_pivots(self.handle, int(side), C.byref(cap)))
+        return int(cap.value)
+
+    def lsd(self, side, synd, e_hat, marg=None, llr_bin=None, index=None, nact=0, max_pivots=0, max_rounds=0, stats=None):
+        """Overwrite e_hat[b] (uint8 [B,n]) for the listed samples with the LSD-0 solution of side 0 (hx) / 1 (hz) on the full matrix
+        (`fgnn_lsd`; no row basis).  `max_pivots` = 0: `lsd_max_pivots(side)`; `max_rounds` = 0: no limit.  Returns `(e_hat, stats)`,
+        stats int32 [B,4] = (found, rounds, columns appended, pivots) of every processed sample (the rows of the others are left as
+        they were: uninitialised when `stats` is not handed in)."""
+        B, synd, e_hat, marg, llr_bin, index, _ = self._osd_in(side, synd, e_hat, marg, llr_bin, index)
+        stats = self._new((B, 4), torch.int32) if stats is None else self._chk_out(stats, (B, 4), torch.int32, "stats")
+        check(_lib.lib().fgnn_lsd(self.handle, int(side), _ptr(marg), _ptr(llr_bin), _ptr(synd), B, _ptr(index), int(nact),
+                                  int(max_pivots), int(max_rounds), _ptr(e_hat), _ptr(stats), _stream(self.device)))
+        return e_hat, stats
+
     def residual_rows(self, rows_x, rows_z, ex, ez, x_hat, z_hat):
         B, ex, ez, x_hat, z_hat = self._residual_in(ex, ez, x_hat, z_hat)
         ls_hat = self._new((B, self._row_count(rows_x) + self._row_count(rows_z)), torch.uint8)

@@ -624,6 +624,44 @@ int fgnn_osd_ws(const fgnn_graph* g, int side, int method, int order, const floa
  * zero on entry; ids of one 256-sample block are ascending, blocks arrive in any order. */
 int fgnn_compact(const uint8_t* mask, int bit, int B, int32_t* index, int32_t* count, void* stream);
 
+/* Localized statistics decoding, LSD-0 with synchronous growth (Hillmann, Berent, Quintavalle, Eisert, Wille, Roffe 2024; BpLsdDecoder
+ * of ldpc v2): cluster-based post-processing of BP failures.  It needs no row basis (fgnn_graph_set_basis is not used) and takes
+ * dependent rows as they are.  One side of the graph is a binary matrix H of m checks by n bits (side 0 = hx, solves z_hat; side 1 =
+ * hz, solves x_hat, as fgnn_osd0); every listed sample of that side is solved on its own.
+ * Inputs: the full syndrome s [m] (synd [B,m_side]); the reliabilities r of fgnn_osd0 (from marg [B,3,n] or llr_bin [B,n], exactly
+ * one of them, then r + 0.0f); key(v) = (sortable(r[v]) << 32) | v with fgnn_osd's order-preserving float -> uint32 map: the smallest
+ * key is the most likely error, ties go to the lower bit index.
+ * State: t = the reduced syndrome over the m checks, initially s; lab[c] = the cluster label of check c, -1 outside every cluster, else
+ * the smallest check index of its cluster; inB[v] = bit v is in a cluster; isPivot[c] = check c is a pivot row; pivots k = 0 .. P-1,
+ * each a check piv[k], a bit col[k] and an m-bit vector L[k].
+ * Start: every check with s[c] = 1 is a cluster of its own (a zero syndrome: e = 0, found = 1, 0 rounds).  A cluster is invalid while
+ * some non-pivot check of it has t[c] = 1.  Rounds run while an invalid cluster that is not dead exists, no cap has been hit, and
+ * max_rounds is 0 or fewer than max_rounds rounds have run.  A round:
+ *   1. select, on the state at the start of the round: every invalid live cluster picks the bit of smallest key among the bits not in
+ *      inB that touch one of its checks; a cluster with no such bit is dead (a whole connected component whose syndrome is not in the
+ *      image of H): it stays invalid and is never grown again.  S = the distinct bits selected.
+ *   2. append the bits v of S in ascending key order, one after the other: set inB[v]; all checks of v join one cluster together with
+ *      every cluster they belonged to (label = the smallest check index of the union); x = column v of H; for k = 0 .. P-1 in order:
+ *      if x[piv[k]] is set, x ^= L[k] with its own piv[k] bit left out (x[piv[k]] stays set); if x is zero on every non-pivot check
+ *      the column is dependent and nothing more happens; otherwise, if P == max_pivots the sample ends here (found = 0); otherwise
+ *      p = the lowest non-pivot check set in x, piv[P] = p, col[P] = v, L[P] = x, p becomes a pivot, if t[p] is set t ^= x with bit p
+ *      left out, and P += 1.
+ * These are Gauss-Jordan row operations kept as a list: every pivot column is a unit vector, so e[col[k]] = t[piv[k]] and every other
+ * bit is 0, without back-substitution.
+ * Outputs, for every processed sample b (others untouched): e_hat[b,:] zeroed and then written (with found = 0: the read-out of the
+ * pivots there are); stats[b] = (found, rounds, columns appended, pivots) (device int32 [B,4], may be NULL).  A round in which a
+ * cluster dies counts as a round; the column that hits the pivot cap counts as a column; found = 1 iff no cluster is invalid at the
+ * end.  With no caps H e_hat = s holds whenever s is the syndrome of some error.  Selection is an integer minimum per cluster and the
+ * append is sequential in key order: nothing depends on arrival order or launch geometry.
+ * All state lives in LDS.  fgnn_lsd_max_pivots: *cap = min(m_side, n, the largest pivot count whose LDS fits); a side with more than
+ * 8192 checks, or one whose state does not fit with one pivot, is refused by both calls.  max_pivots = 0 means that cap; max_rounds =
+ * 0 means no limit.  Refused with FGNN_ERR_ARG before anything is launched or written: a NULL graph, synd or e_hat; both or neither
+ * of marg / llr_bin; max_pivots above the cap (the message names the largest count that fits); a negative max_pivots or max_rounds.
+ * index / nact select the samples as in fgnn_osd0. */
+int fgnn_lsd_max_pivots(const fgnn_graph* g, int side, int* cap);
+int fgnn_lsd(const fgnn_graph* g, int side, const float* marg, const float* llr_bin, const uint8_t* synd, int B, const int32_t* index,
+             int nact, int max_pivots, int max_rounds, uint8_t* e_hat, int32_t* stats, void* stream);
+
 /* GNN_BP4 (the syndrome-only "full GNN" decoder), sionna/fec/ldpc/gnn.py:71-423 with UpdateCNEmbeddings (:426-610)
  * and UpdateVNEmbeddings (:612-751): num_mlp_layers=2, tanh, mean, use_bias, num_embed_dims=20, num_hidden_units=40.
  * Weights: 30 host arrays — cn_msg_x, cn_msg_z, cn_embed_x, cn_embed_z, vn_msg_x, vn_msg_z, vn_embed, each
