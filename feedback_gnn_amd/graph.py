@@ -473,31 +473,37 @@ class TannerGraph:
         return dict(tape_x=tx, tape_z=tz, x_logit=xl, z_logit=zl, x_hat=out["x_hat"], z_hat=out["z_hat"], llr=out["llr"])
 
     def bp4_backward(self, llr_ch, synd_x, synd_z, tape_x, tape_z, grad_x_logit, grad_z_logit, factor=1.0):
-        """d loss / d llr_ch [B,3,n] from d loss / d soft syndromes [T+1,B,rows] (fgnn_bp4_backward)."""
+        """d loss / d llr_ch [B,3,n] from d loss / d soft syndromes [T+1,B,rows] (fgnn_bp4_backward); a side whose gradient is None
+        contributes nothing (the library's NULL)."""
         T, B = int(tape_x.shape[0]) - 1, int(llr_ch.shape[0])
         llr_ch = self._chk(llr_ch, (B, 3, self.n), torch.float32, "llr_ch")
         synd_x = self._chk(synd_x, (B, self.m_x), torch.uint8, "synd_x")
         synd_z = self._chk(synd_z, (B, self.m_z), torch.uint8, "synd_z")
         tape_x = self._chk(tape_x, (T + 1, B, self.E_x), torch.float32, "tape_x")
         tape_z = self._chk(tape_z, (T + 1, B, self.E_z), torch.float32, "tape_z")
-        gx = self._chk(grad_x_logit, (T + 1, B, self.rows_xp), torch.float32, "grad_x_logit")
-        gz = self._chk(grad_z_logit, (T + 1, B, self.rows_zp), torch.float32, "grad_z_logit")
-        has = ((gx != 0).flatten(1).any(1) | (gz != 0).flatten(1).any(1)).to(torch.uint8).contiguous()
+        gx = self._opt(grad_x_logit, (T + 1, B, self.rows_xp), torch.float32, "grad_x_logit")
+        gz = self._opt(grad_z_logit, (T + 1, B, self.rows_zp), torch.float32, "grad_z_logit")
+        flags = [(t != 0).flatten(1).any(1) for t in (gx, gz) if t is not None]
+        if flags:
+            has = (flags[0] | flags[-1]).to(torch.uint8).contiguous()
+        else:
+            has = self._new((T + 1,), torch.uint8).zero_()
         out = self._new((B, 3, self.n), torch.float32)
         check(_lib.lib().fgnn_bp4_backward(self.handle, T, float(factor), _ptr(llr_ch), _ptr(synd_x), _ptr(synd_z), B,
                                            _ptr(tape_x), _ptr(tape_z), _ptr(gx), _ptr(gz), _ptr(has), _ptr(out),
                                            _stream(self.device)))
         return out
 
-    def feedback_gnn_backward(self, weights, llr, logit_hx, logit_hz, synd_x, synd_z, grad_out):
-        """Weight gradients (12 tensors, Keras order) of sum(grad_out * Feedback_GNN(...)): the HIP kernel leaves the
-        (activation, delta) pairs of the four Dense layers in HBM, the reductions over batch x edges are library GEMMs."""
+    def feedback_gnn_backward_pairs(self, weights, llr, logit_hx, logit_hz, synd_x, synd_z, grad_out):
+        """The reverse kernels' own outputs: one (input activations [rows, K], pre-activation deltas [rows, J]) pair per Dense layer
+        in execution order — hx message MLP, hz message MLP (rows = B * E_s, the edges in the order of `edges(s)`), embed MLP,
+        _llr_inv_embed (rows = B * n).  The one place their buffers are sized and handed to the library.  Shipped configuration
+        (fgnn_feedback_gnn_backward): (e_feat, e_d1), (e_h1, e_dm) per side, (node_in, node_d2) with node_in 44 wide (column 43 is
+        padding), (node_h2, grad_out as rows); any other (fgnn_feedback_gnn_backward_general): acts[li], deltas[li]."""
         B, llr, logit_hx, logit_hz, synd_x, synd_z = self._gnn_in(llr, logit_hx, logit_hz, synd_x, synd_z)
         grad_out = self._chk(grad_out, (B, 3, self.n), torch.float32, "grad_out")
         if weights.general:
-            # any constructor setting (fgnn_feedback_gnn_backward_general): one (input activations, pre-activation delta) pair per Dense
-            # layer in execution order; the gradients come back in the order of get_weights() (_llr_inv_embed first)
-            D, H, L, _, _, bias = weights.config
+            D, H, L, _, _, _ = weights.config
             shapes = [(4 if l == 0 else H, D if l == L - 1 else H) for _ in range(2) for l in range(L)]
             shapes += [(2 * D + 3 if l == 0 else H, H) for l in range(L - 1)]
             shapes += [(H if L > 1 else 2 * D + 3, 3)]
@@ -509,13 +515,7 @@ class TannerGraph:
             check(_lib.lib().fgnn_feedback_gnn_backward_general(self.handle, weights.handle, _ptr(llr), _ptr(logit_hx), _ptr(logit_hz),
                                                                 _ptr(synd_x), _ptr(synd_z), B, _ptr(grad_out), pa, pd, len(acts),
                                                                 _stream(self.device)))
-            grads = []
-            for f in range(3 * L):
-                li = 3 * L - 1 if f == 0 else f - 1
-                grads.append(acts[li].t() @ deltas[li])
-                if bias:
-                    grads.append(deltas[li].sum(0))
-            return grads
+            return list(zip(acts, deltas))
         node_in = self._new((B * self.n, 44), torch.float32)
         node_h2 = self._new((B * self.n, 40), torch.float32)
         node_d2 = self._new((B * self.n, 40), torch.float32)
@@ -530,10 +530,21 @@ class TannerGraph:
                                                     _ptr(node_h2), _ptr(node_d2), pp(feat), pp(h1), pp(d1), pp(dm),
                                                     _stream(self.device)))
         G = grad_out.permute(0, 2, 1).reshape(B * self.n, 3)
-        grads = [node_h2.t() @ G, G.sum(0)]
-        for s in range(2):
-            grads += [feat[s].t() @ d1[s], d1[s].sum(0), h1[s].t() @ dm[s], dm[s].sum(0)]
-        grads += [node_in[:, :43].t() @ node_d2, node_d2.sum(0)]
+        return [(feat[0], d1[0]), (h1[0], dm[0]), (feat[1], d1[1]), (h1[1], dm[1]), (node_in, node_d2), (node_h2, G)]
+
+    def feedback_gnn_backward(self, weights, llr, logit_hx, logit_hz, synd_x, synd_z, grad_out):
+        """Weight gradients (Keras order, _llr_inv_embed first) of sum(grad_out * Feedback_GNN(...)): the HIP kernel leaves the
+        (activation, delta) pairs of the Dense layers in HBM (`feedback_gnn_backward_pairs`), the reductions over batch x edges are
+        library GEMMs: kernel gradient = activations^T deltas, bias gradient = column sums of the deltas."""
+        pairs = self.feedback_gnn_backward_pairs(weights, llr, logit_hx, logit_hz, synd_x, synd_z, grad_out)
+        D, H, L, _, _, bias = weights.config
+        kernels = gnn_weight_shapes(D, H, L, use_bias=False)
+        grads = []
+        for f in range(3 * L):
+            a, d = pairs[3 * L - 1 if f == 0 else f - 1]  # get_weights() lists _llr_inv_embed first, the kernels run it last
+            grads.append(a[:, :kernels[f][0]].t() @ d)  # (the slice drops node_in's padding column and nothing else)
+            if bias:
+                grads.append(d.sum(0))
         return grads
 
     # ---- channel / syndromes / flags / residual ---------------------------------------------------------
