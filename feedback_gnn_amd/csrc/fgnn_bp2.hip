@@ -11,8 +11,7 @@
 // Bit-identical to oracle/fgnn_oracle.c: og_bp2_decode.
 #include <cstdlib>
 
-#include "fgnn_internal.h"
-#include "fgnn_math.h"
+#include "fgnn_step.h"
 #include "fgnn_cn.h"
 #include "fgnn_rng.h"
 
@@ -124,72 +123,39 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_
     FG_LOG_TAB_SETUP();
     constexpr bool REGULAR = DV > 0;
     extern __shared__ float lds[];
-    const int cwl = threadIdx.x / a.tpc;
-    const int lane = threadIdx.x - cwl * a.tpc;
-    const int b = blockIdx.x * a.cpb + cwl;
-    const bool active = b < a.B;
-    float* msg = lds + (size_t)cwl * a.lds_per_cw;
+    const StepCw cw(a.B, a.tpc, a.cpb);
+    const int lane = cw.lane;
+    const BitRows rows(g, a.llr_ch, a.llr_const, a.synd, cw);
+    float* msg = lds + (size_t)cw.cwl * a.lds_per_cw;
     const int n = g.n, m = g.m_x;
-    if (active)
+    if (cw.active)
         for (int e = lane; e < g.E_x; e += a.tpc) msg[e] = 0.0f;
-    // the syndrome bits of the checks lane, lane + tpc, ... this thread owns, one register for all iterations
-    const bool synd_in_reg = (m + a.tpc - 1) / a.tpc <= 32;
-    unsigned synd_bits = 0;
-    if (active && a.synd && synd_in_reg) {
-        int k = 0;
-        for (int c = lane; c < m; c += a.tpc, ++k) synd_bits |= (unsigned)(a.synd[(size_t)b * m + c] & 1u) << k;
-    }
+    const StepSynd synd(g, rows, cw, a.tpc, m, a.synd != nullptr);  // the syndrome bits of the lane's checks, one register for all iterations
     const bool f1 = a.factor == 1.0f;
     __syncthreads();
     for (int it = 0; it <= a.num_iter; ++it) {
-        if (active)
+        if (cw.active)
             for (int v = lane; v < n; v += a.tpc) {
-                float lc = a.llr_ch ? a.llr_ch[(size_t)b * n + v] : a.llr_const;
-                lc = FG_MIN(FG_MAX(lc, -20.0f), 20.0f);
-                const float L = -1.0f * lc;
-                if constexpr (REGULAR) {
-                    float* mv = msg + v * DV;
-                    float mi[DV];
-#pragma unroll
-                    for (int k = 0; k < DV; ++k) mi[k] = mv[k];
-                    float S = 0.0f;
-#pragma unroll
-                    for (int k = 0; k < DV; ++k) S = S + mi[k];
-                    if (it == a.num_iter) {
-                        const float o = -1.0f * (L + S);
-                        if (a.soft_out) a.soft_out[(size_t)b * n + v] = o;
-                        if (a.hard_out) a.hard_out[(size_t)b * n + v] = (uint8_t)(0.0f < o);
-                        continue;
-                    }
-                    const float x = S + L;
-#pragma unroll
-                    for (int k = 0; k < DV; ++k) mv[k] = x - mi[k];
-                } else {
-                    const int e0 = g.vptr_x[v], e1 = g.vptr_x[v + 1];
-                    float S = 0.0f;
-                    for (int e = e0; e < e1; ++e) S = S + msg[e];
-                    if (it == a.num_iter) {
-                        const float o = -1.0f * (L + S);
-                        if (a.soft_out) a.soft_out[(size_t)b * n + v] = o;
-                        if (a.hard_out) a.hard_out[(size_t)b * n + v] = (uint8_t)(0.0f < o);
-                        continue;
-                    }
-                    const float x = S + L;
-                    for (int e = e0; e < e1; ++e) msg[e] = x - msg[e];
+                const float L = rows.prior(v);
+                BitSlots<DV> q(g, msg, v);
+                const float S = q.fetch();
+                if (it == a.num_iter) {
+                    const float o = -1.0f * (L + S);
+                    if (a.soft_out) a.soft_out[rows.at(v)] = o;
+                    if (a.hard_out) a.hard_out[rows.at(v)] = (uint8_t)(0.0f < o);
+                    continue;
                 }
+                q.store(S + L);
             }
         if (it == a.num_iter) break;
         __syncthreads();
-        if (active) {
-            int k = 0;
-            for (int c = lane; c < m; c += a.tpc, ++k) {
-                const unsigned sy = !a.synd ? 0u : synd_in_reg ? ((synd_bits >> k) & 1u) : (a.synd[(size_t)b * m + c] & 1u);
+        if (cw.active) {
+            int i = 0;
+            for (int c = lane; c < m; c += a.tpc, ++i) {
+                const unsigned sy = synd.at(g, rows, i, c);
                 if constexpr (REGULAR) {
-                    const uint4 pk = reinterpret_cast<const uint4*>(g.cslot16)[c];
-                    const unsigned w[4] = {pk.x, pk.y, pk.z, pk.w};
                     unsigned off[DC];
-#pragma unroll
-                    for (int j = 0; j < DC; ++j) off[j] = (w[j >> 1] >> ((j & 1) * 16)) & 0xffffu;
+                    row_unpack(g, c, off);
                     if constexpr (CN_TYPE == FGNN_CN_MINSUM) cn_minsum_regular<DC>(msg, off, DC, sy, a.factor);
                     else cn2_phi_regular<DC>(msg, off, sy, a.factor, f1);
                 } else if constexpr (DC > 0 && CN_TYPE == FGNN_CN_MINSUM) {
@@ -223,12 +189,6 @@ __global__ void __launch_bounds__(256) bsc_kernel(uint64_t seed, float p, uint64
         if (blk * 4 + k < n) noise[(size_t)b * n + blk * 4 + k] = (uint8_t)(u[k] < p);
 }
 
-template <int CN_TYPE, int DV = 0, int DC = 0>
-int launch(const fgnn_graph* g, const Bp2Args& a, const LaunchGeom& L, size_t lds_bytes, hipStream_t st)
-{
-    return fgnn_launch(bp2_kernel<CN_TYPE, DV, DC>, dim3(L.blocks), dim3(L.threads), lds_bytes, st, g->d, a);
-}
-
 }  // namespace
 
 extern "C" int fgnn_bp2_decode(const fgnn_graph* g, int cn_type, int num_iter, float normalization_factor, const float* llr_ch,
@@ -252,30 +212,16 @@ extern "C" int fgnn_bp2_decode(const fgnn_graph* g, int cn_type, int num_iter, f
     a.synd = synd;
     a.soft_out = soft_out;
     a.hard_out = hard_out;
-    a.lds_per_cw = (g->d.E_x + 3) & ~3;
+    a.lds_per_cw = (int)lds_round4(g->d.E_x);
     const size_t lds_bytes = (size_t)a.lds_per_cw * sizeof(float) * (size_t)L.cpb;
     if (lds_bytes > FGNN_LDS_BUDGET) return fgnn_fail(FGNN_ERR_ARG, "code too large for the LDS-resident kernel");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    // the register-resident check update for (3,6)- and (4,8)-regular hx graphs (the GHP and GB families; cslot16 exists for check degrees up to 8;
-    // slots of side 0 come first in the combined numbering, so its byte offsets index this kernel's message area directly)
-    const bool regular = g->d.cslot16 && !g->force_generic;
-    const bool r36 = regular && g->d.dvx == 3 && g->d.dc == 6, r48 = regular && g->d.dvx == 4 && g->d.dc == 8;  // GHP / GB families
-    if (r36 && cn_type == FGNN_CN_BOXPLUS_PHI) return launch<FGNN_CN_BOXPLUS_PHI, 3, 6>(g, a, L, lds_bytes, st);
-    if (r36 && cn_type == FGNN_CN_MINSUM) return launch<FGNN_CN_MINSUM, 3, 6>(g, a, L, lds_bytes, st);
-    if (r48 && cn_type == FGNN_CN_BOXPLUS_PHI) return launch<FGNN_CN_BOXPLUS_PHI, 4, 8>(g, a, L, lds_bytes, st);
-    if (r48 && cn_type == FGNN_CN_MINSUM) return launch<FGNN_CN_MINSUM, 4, 8>(g, a, L, lds_bytes, st);
-    // runtime-degree graphs whose hx checks have at most 8 / 16 edges, min-sum rule: the predicated register-resident update (its
-    // compare/select work is cheap, what the loop over the slot list pays for is latency: 17.7 -> 13.0 ms on [[882,24]], 202 -> 153 ms on
-    // the 1000-row over-complete GB matrix, per 65 536 x 64).  The phi rule stays on the loop: masked-out edges would still cost a phi
-    // (measured: 26.2 against 20.8 ms).
-    const int md = (g->force_generic && getenv("FGNN_BP2_NO_PRED")) ? 1 << 30 : g->d.max_cdeg_x;
-    if (md <= 8 && cn_type == FGNN_CN_MINSUM) return launch<FGNN_CN_MINSUM, 0, 8>(g, a, L, lds_bytes, st);
-    if (md <= 16 && cn_type == FGNN_CN_MINSUM) return launch<FGNN_CN_MINSUM, 0, 16>(g, a, L, lds_bytes, st);
-    switch (cn_type) {
-    case FGNN_CN_BOXPLUS_PHI: return launch<FGNN_CN_BOXPLUS_PHI>(g, a, L, lds_bytes, st);
-    case FGNN_CN_MINSUM: return launch<FGNN_CN_MINSUM>(g, a, L, lds_bytes, st);
-    default: return launch<FGNN_CN_BOXPLUS>(g, a, L, lds_bytes, st);
-    }
+    // FGNN_BP2_NO_PRED (tests): a graph forced onto the generic kernels runs min-sum on the loop too
+    const bool predicated = !(g->force_generic && getenv("FGNN_BP2_NO_PRED"));
+    return bit_dispatch(g, cn_type, predicated, [&](auto cn, auto dv, auto dc) {
+        return fgnn_launch(bp2_kernel<decltype(cn)::value, decltype(dv)::value, decltype(dc)::value>, dim3(L.blocks), dim3(L.threads),
+                           lds_bytes, st, g->d, a);
+    });
 }
 
 extern "C" int fgnn_bsc_noise(uint64_t seed, float p, uint64_t first_sample, int B, int n, uint8_t* noise, void* stream)

@@ -3,10 +3,10 @@
 // Relay-BP's memory term (Mueller et al., "Improved belief propagation is sufficient for real-time decoding of quantum memories", 2025)
 // applied to each of a qubit's three LLRs, in the form include/fgnn.h states at fgnn_relay4_decode.  The qubit update is the literal
 // form of fgnn_vn.h (one log-sum-exp per edge, fgnn_math.h) with the memory-weighted LLRs Lam in place of the channel LLRs,
-// the check update is the shared min-sum rule of fgnn_cn.h, the leg / stop / weight control is relay_kernel's (fgnn_relay.hip).  The
-// kernel stands on the frame of the step-loop decoders (fgnn_step.h): codeword rows, staged syndrome bits, a qubit's slots (counted as
-// zeros before a leg's first check update), a check's row and parity, the write of the decisions; its own are the leg walk below, the
-// posteriors M, the weights and the late stats write.  No
+// the check update is the shared min-sum rule of fgnn_cn.h, the leg / stop / weight control is the shared one of fgnn_legs.h (LegCtl).
+// The kernel stands on the frame of the step-loop decoders (fgnn_step.h): codeword rows, staged syndrome bits, a qubit's slots (counted
+// as zeros before a leg's first check update), a check's row and parity, the write of the decisions, the staging of the control's LDS
+// words; its own are the memory term on the posteriors M and the weight of a decision.  No
 // saturation shortcuts, no register-resident channel LLRs, no hardware transcendentals: the channel LLRs are re-read from global
 // memory (L2) by the thread that owns the qubit, every float operation is the one bp4_kernel and cn_update execute, in their order.
 //
@@ -14,10 +14,7 @@
 //   msg [E_x + E_z]  c->v / v->c messages, slot e in [0,E_x) = hx edges, [E_x,E) = hz edges, sorted by (qubit, check): bp4_kernel's layout
 //   M   [3n]         posteriors M^X [0,n), M^Y [n,2n), M^Z [2n,3n): the memory term reads them, the next leg starts from them
 //   dec [n] bytes    decisions d_v = x_v | z_v << 1 of the last test: the parity test gathers them in the same sweep as the check update
-// and per workgroup stamp[cpb], wacc[cpb], ndone (ints), as relay_kernel:
-//   stamp[cw]  the number of the last workgroup step in which a check of the codeword saw odd parity (no reset needed)
-//   wacc[cw]   running total of the weights of the decisions weighed so far (integer atomics; a thread keeps the previous total)
-//   ndone      finished codewords; read by all threads in the same interval, so leaving the loop is a uniform decision
+// and per workgroup the ints of the leg control, stamp[cpb], wacc[cpb], ndone (leg_lds_words of fgnn_legs.h, laid out by leg_stage).
 // [[882,24]]: 5292 + 2648 + 224 floats = 32 656 bytes per codeword; [[1270,28]]: 7620 + 3812 + 320 floats = 47 008 bytes.
 //
 // Codewords of one workgroup stop at different steps: leg, step of the leg, solutions found and best weight are registers every thread of
@@ -25,7 +22,7 @@
 //
 // Occupancy.  With 256 threads (4 waves) per codeword the LDS above admits 4 workgroups of [[882,24]] on a CU (5 x (32 672 + the 256
 // bytes of the log table) exceed 160 KiB) and 3 of [[1270,28]]: 4 waves per SIMD at the most, whatever the registers allow.  The kernels
-// are therefore compiled for 4 waves per SIMD (a budget of 128 VGPRs): the (3,3,6) instantiation takes 88 VGPRs and the loop 68, no
+// are therefore compiled for 4 waves per SIMD (a budget of 128 VGPRs): the (3,3,6) instantiation takes 89 VGPRs and the loop 69, no
 // spills, no scratch.  Asking for more waves would only squeeze the allocation of a kernel whose residency LDS decides.
 #include "fgnn_step.h"
 #include "fgnn_cn.h"
@@ -37,7 +34,8 @@
 namespace {
 
 struct Relay4Args : StepArgs {
-    int pre_iter, num_legs, leg_iter, stop_nconv, m_off;
+    LegSched legs;
+    int m_off;
     float factor;
     const float* gamma;      // [num_legs,n]
 };
@@ -62,12 +60,9 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_
     float* msg = lds + (size_t)cwl * a.lds_per_cw;
     float* M = msg + a.m_off;
     uint8_t* dec = reinterpret_cast<uint8_t*>(msg + a.d_off);
-    int* stamp = reinterpret_cast<int*>(lds + (size_t)a.cpb * a.lds_per_cw);
-    int* wacc = stamp + a.cpb;
-    int* ndone = wacc + a.cpb;
     const int n = g.n, m = g.m;
 
-    for (int i = threadIdx.x; i < 2 * a.cpb + 1; i += blockDim.x) stamp[i] = 0;
+    const LegLds ws = leg_stage(lds, a.cpb, a.lds_per_cw);
     if (cw.active)
         for (int v = lane; v < n; v += a.tpc) {
             rows.llrs(n, v, a.llr_const, M[v], M[n + v], M[2 * n + v]);
@@ -76,12 +71,11 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_
     const StepSynd synd(g, rows, cw, a.tpc);
     __syncthreads();
 
-    int r = 0, k = 0, found = 0, best_w = 0, best_r = 0, best_k = 0, wprev = 0, pend_r = 0, pend_k = 0;
-    bool done = !cw.active, written = !cw.active, pending = false;
+    LegCtl ctl(cw.active);
     for (int step = 1; step <= a.max_steps; ++step) {
-        const int T = (r == 0) ? a.pre_iter : a.leg_iter;
+        const int T = ctl.T(a.legs), r = ctl.r, k = ctl.k;
         // ---- qubits: marginals after k check updates and their decision, memory term, messages to the checks ----
-        if (!done) {
+        if (!ctl.done) {
             const float* gam = a.gamma + (size_t)r * n;
             for (int v = lane; v < n; v += a.tpc) {
                 float lx, ly, lz;
@@ -108,31 +102,11 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_
         }
         __syncthreads();
         // ---- the decision weighed in the previous step: its weight is complete now, dec still holds it ----
-        if (pending) {
-            const int total = wacc[cwl];
-            const int w = total - wprev;
-            wprev = total;
-            if (found <= 1 || w < best_w) {
-                best_w = w;
-                best_r = pend_r;
-                best_k = pend_k;
-                step_write_decisions(a, dec, rows.bb, n, lane);
-            }
-            pending = false;
-        }
-        if (done && !written) {
-            if (lane == 0) {
-                int32_t* st = a.stats + (size_t)cw.b * 4;
-                st[0] = found;
-                st[1] = best_w;
-                st[2] = best_r;
-                st[3] = best_k;
-            }
-            written = true;
-        }
-        if (*ndone == cw.nact) break;  // the same word for every thread, last written before the barrier above
+        if (ctl.pending) ctl.settle(ws.wacc[cwl], [&] { step_write_decisions(a, dec, rows.bb, n, lane); });
+        if (ctl.stats_due() && lane == 0) ctl.stats(a.stats + (size_t)cw.b * 4);
+        if (*ws.ndone == cw.nact) break;  // the same word for every thread, last written before the barrier above
         // ---- checks of both graphs: parity of the decisions (k > 0), then the min-sum update (k < T) ----
-        if (!done) {
+        if (!ctl.done) {
             int i = 0;
             for (int c = lane; c < m; c += a.tpc, ++i) {
                 const unsigned sy = synd.at(g, rows, i, c);
@@ -140,26 +114,23 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_
                 if constexpr (REGULAR) {
                     unsigned off[DC];
                     row_unpack(g, c, off);
-                    if (k > 0 && parity_regular<DV>(g, dec, off, is_x, sy)) stamp[cwl] = step;
+                    if (k > 0 && parity_regular<DV>(g, dec, off, is_x, sy)) ws.stamp[cwl] = step;
                     if (k < T) cn_minsum_regular<DC>(msg, off, DC, sy, a.factor);
                 } else {
                     const int c0 = g.cptr[c], deg = g.cptr[c + 1] - c0;
-                    if (k > 0 && parity_csr(g, dec, c0, deg, is_x, sy)) stamp[cwl] = step;
+                    if (k > 0 && parity_csr(g, dec, c0, deg, is_x, sy)) ws.stamp[cwl] = step;
                     if (k < T) cn_update<FGNN_CN_MINSUM, PhiGnn>(msg, g.cslot + c0, deg, sy, a.factor);
                 }
             }
         }
         __syncthreads();
-        // ---- per codeword: solution found, leg over, decoder finished ----
-        if (!done) {
+        // ---- per codeword: solution found, leg over, decoder finished (fgnn_legs.h) ----
+        if (!ctl.done) {
             if (k == 0) {
-                k = 1;
+                ctl.more();
             } else {
-                const bool sat = stamp[cwl] != step;
-                const bool leg_end = sat || k == T;
-                if (sat) ++found;
-                const bool fin = leg_end && (r == a.num_legs - 1 || found == a.stop_nconv);
-                if (sat || (fin && found == 0)) {  // weigh this decision: a solution, or the last test of a decoder that found none
+                const LegTest t = ctl.test(a.legs, T, ws.stamp[cwl] != step);
+                if (t.weigh) {
                     int part = 0;
                     for (int v = lane; v < n; v += a.tpc) {
                         const int d = dec[v];
@@ -169,19 +140,16 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_
                             part += relay4_weight(d, lx, ly, lz);
                         }
                     }
-                    if (part) atomicAdd(&wacc[cwl], part);
-                    pending = true;
-                    pend_r = r;
-                    pend_k = k;
+                    if (part) atomicAdd(&ws.wacc[cwl], part);
+                    ctl.weighed();
                 }
-                if (fin) {
-                    done = true;
-                    if (lane == 0) atomicAdd(ndone, 1);
-                } else if (leg_end) {
-                    ++r;
-                    k = 0;
+                if (t.fin) {
+                    ctl.finish();
+                    if (lane == 0) atomicAdd(ws.ndone, 1);
+                } else if (t.leg_end) {
+                    ctl.next_leg();
                 } else {
-                    ++k;
+                    ctl.more();
                 }
             }
         }
@@ -207,16 +175,13 @@ extern "C" int fgnn_relay4_decode(const fgnn_graph* g, int cn_type, float normal
     Relay4Args a;
     // the step after a codeword's last weighs its last decision
     step_args_fill(a, L, B, pre_iter, num_legs - 1, leg_iter, llr_ch, llr_const, synd_x, synd_z, x_hat, z_hat, stats);
-    a.pre_iter = pre_iter;
-    a.num_legs = num_legs;
-    a.leg_iter = leg_iter;
-    a.stop_nconv = stop_nconv;
+    a.legs = {pre_iter, num_legs, leg_iter, stop_nconv};
     a.factor = normalization_factor;
     a.gamma = gamma;
     // per codeword: E messages, 3n posteriors and n decision bytes; per workgroup: stamp and wacc per codeword, ndone
     const size_t m_off = lds_round4(g->d.E), d_off = m_off + lds_round4((size_t)3 * g->d.n);
     size_t lds_bytes;
-    if (int err = step_lds_bytes(a, "Relay-BP4", d_off + lds_bytes_as_floats(g->d.n), 0, 2 * L.cpb + 1, &lds_bytes)) return err;
+    if (int err = step_lds_bytes(a, "Relay-BP4", d_off + lds_bytes_as_floats(g->d.n), 0, leg_lds_words(L.cpb), &lds_bytes)) return err;
     a.m_off = (int)m_off;
     a.d_off = (int)d_off;
     const auto kernel = step_regular_336(g) ? relay4_kernel<3, 6> : relay4_kernel<0, 0>;

@@ -9,12 +9,20 @@
 //   step_write_decisions / step_finish   dec -> x_hat | z_hat, the four stats words and ndone
 // and on the host StepArgs (the head of every kernel's argument struct), the LDS arithmetic, the LDS refusal and the dispatch over
 // (check rule, regular 3-3-6).  Each kernel keeps its own step loop, barriers, LDS order, waves-per-SIMD value and whatever makes it
-// that decoder.  bp4gd_kernel, bp4fb_kernel and relay4_kernel have a control section each.  mbp4_kernel, dsbp4_kernel and
-// stbp4_kernel share one, the attempt schedule of fgnn_attempts.h (AttemptSched, AttemptCtl, the step bound), and with it
+// that decoder.  bp4gd_kernel and bp4fb_kernel have a control section each.  mbp4_kernel, dsbp4_kernel and stbp4_kernel share
+// one, the attempt schedule of fgnn_attempts.h (AttemptSched, AttemptCtl, the step bound), and with it
 //   AttemptArgs, attempt_check_* / attempt_args_fill   the schedule in the argument struct, its argument checks and its fill
 //   attempt_stage                  tab, stamp and ndone staged into LDS behind the codewords
 //   attempt_qubit<DV>              the qubit phase of one qubit: decision after k updates, messages with own[r]
+// relay4_kernel shares its control with the binary relay_kernel (fgnn_relay.hip): the leg control of fgnn_legs.h (LegSched, LegCtl),
+// whose LDS words leg_stage lays out here.
 // Every float operation stays where it was: the sums run hz before hx, each ascending from 0.
+//
+// The two binary decoders on side 0 (hx), bp2_kernel (fgnn_bp2.hip) and relay_kernel, take StepCw (from B, tpc, cpb: their argument
+// structs are their own), StepSynd (over the m_x checks of hx) and row_unpack from the frame, and have their own part at the end:
+//   BitRows                        the llr_ch / output row and the syndrome row of a codeword, synd_of, the prior
+//   BitSlots<DV>                   a bit's message slots: fetch with the ascending sum (or zeros), store x - m_j; QubitSlots' binary sibling
+// and on the host bit_dispatch over (check rule, regular (3,6) / (4,8), predicated runtime degrees up to 8 / 16, loop).
 #ifndef FGNN_STEP_H
 #define FGNN_STEP_H
 
@@ -27,6 +35,7 @@
 #include "fgnn_math.h"
 #include "fgnn_vn.h"
 #include "fgnn_attempts.h"
+#include "fgnn_legs.h"
 
 // ---------------------------------------------------------------------------------------------
 // Host side
@@ -150,6 +159,35 @@ int step_dispatch(const fgnn_graph* g, int cn_type, LAUNCH launch)
     return launch(integral_constant<int, FGNN_CN_MINSUM>(), loop, loop);
 }
 
+// kernel<CN_TYPE, DV, DC> of a launch of the binary decoders on side 0 (hx): boxplus-phi and min-sum run the register-resident
+// check update on (3,6)- and (4,8)-regular hx with packed check rows (the GHP and GB families; cslot16 exists for check degrees up
+// to 8, and the slots of side 0 come first in the combined numbering, so its byte offsets index a binary kernel's message area
+// directly), unless the tests force the loop.  On other graphs min-sum runs the predicated update for runtime degrees up to 8 / 16
+// where `predicated` allows it (its compare/select work is cheap, what the loop over the slot list pays for is latency: 17.7 ->
+// 13.0 ms on [[882,24]], 202 -> 153 ms on the 1000-row over-complete GB matrix, per 65 536 x 64).  The phi rule stays on the loop:
+// masked-out edges would still cost a phi (measured: 26.2 against 20.8 ms); so does boxplus.  `launch` as for step_dispatch
+template <typename LAUNCH>
+int bit_dispatch(const fgnn_graph* g, int cn_type, bool predicated, LAUNCH launch)
+{
+    using std::integral_constant;
+    const integral_constant<int, 0> loop;
+    const bool regular = g->d.cslot16 && !g->force_generic;
+    const bool r36 = regular && g->d.dvx == 3 && g->d.dc == 6, r48 = regular && g->d.dvx == 4 && g->d.dc == 8;
+    const bool phi = cn_type == FGNN_CN_BOXPLUS_PHI, minsum = cn_type == FGNN_CN_MINSUM;
+    const integral_constant<int, FGNN_CN_BOXPLUS_PHI> PHI;
+    const integral_constant<int, FGNN_CN_MINSUM> MINSUM;
+    if (r36 && phi) return launch(PHI, integral_constant<int, 3>(), integral_constant<int, 6>());
+    if (r36 && minsum) return launch(MINSUM, integral_constant<int, 3>(), integral_constant<int, 6>());
+    if (r48 && phi) return launch(PHI, integral_constant<int, 4>(), integral_constant<int, 8>());
+    if (r48 && minsum) return launch(MINSUM, integral_constant<int, 4>(), integral_constant<int, 8>());
+    const int md = predicated ? g->d.max_cdeg_x : 1 << 30;
+    if (minsum && md <= 8) return launch(MINSUM, loop, integral_constant<int, 8>());
+    if (minsum && md <= 16) return launch(MINSUM, loop, integral_constant<int, 16>());
+    if (phi) return launch(PHI, loop, loop);
+    if (minsum) return launch(MINSUM, loop, loop);
+    return launch(integral_constant<int, FGNN_CN_BOXPLUS>(), loop, loop);
+}
+
 // ---------------------------------------------------------------------------------------------
 // Device side
 // ---------------------------------------------------------------------------------------------
@@ -159,14 +197,15 @@ int step_dispatch(const fgnn_graph* g, int cn_type, LAUNCH launch)
 struct StepCw {
     int cwl, lane, b, nact;
     bool active;
-    __device__ __forceinline__ StepCw(const StepArgs& a)
+    __device__ __forceinline__ StepCw(const int B, const int tpc, const int cpb)
     {
-        cwl = threadIdx.x / a.tpc;
-        lane = threadIdx.x - cwl * a.tpc;
-        b = blockIdx.x * a.cpb + cwl;
-        active = b < a.B;
-        nact = min(a.cpb, a.B - (int)blockIdx.x * a.cpb);
+        cwl = threadIdx.x / tpc;
+        lane = threadIdx.x - cwl * tpc;
+        b = blockIdx.x * cpb + cwl;
+        active = b < B;
+        nact = min(cpb, B - (int)blockIdx.x * cpb);
     }
+    __device__ __forceinline__ StepCw(const StepArgs& a) : StepCw(a.B, a.tpc, a.cpb) {}
 };
 
 // the input rows of a thread's codeword (row 0 for an inactive one, which reads nothing), one pointer each
@@ -198,25 +237,32 @@ struct StepRows {
 };
 
 // the syndrome bits of a lane's checks c = lane, lane + tpc, ..: bit i of a register where a lane has 32 checks at the most, else
-// read again from the rows.  ROWS: StepRows, or a kernel's own rows with the same synd_of
+// read again from the rows.  ROWS: StepRows, or a kernel's own rows with the same synd_of; m: the checks of the codeword, g.m
+// unless the kernel says otherwise (the binary decoders: g.m_x).  any = false: the syndrome is null, that is all-zero; no bit is
+// staged and none is asked of the rows (the binary decoders again; StepRows answers 0 for a null side by itself)
 struct StepSynd {
-    bool in_reg;
+    bool any, in_reg;
     unsigned bits;
     template <typename ROWS>
-    __device__ __forceinline__ StepSynd(const GraphDev& g, const ROWS& rows, const StepCw& cw, const int tpc)
+    __device__ __forceinline__ StepSynd(const GraphDev& g, const ROWS& rows, const StepCw& cw, const int tpc, const int m, const bool any_ = true)
+        : any(any_)
     {
-        in_reg = (g.m + tpc - 1) / tpc <= 32;
+        in_reg = (m + tpc - 1) / tpc <= 32;
         bits = 0;
-        if (cw.active && in_reg) {
+        if (cw.active && any && in_reg) {
             int i = 0;
-            for (int c = cw.lane; c < g.m; c += tpc, ++i) bits |= rows.synd_of(g, c) << i;
+            for (int c = cw.lane; c < m; c += tpc, ++i) bits |= rows.synd_of(g, c) << i;
         }
+    }
+    template <typename ROWS>
+    __device__ __forceinline__ StepSynd(const GraphDev& g, const ROWS& rows, const StepCw& cw, const int tpc) : StepSynd(g, rows, cw, tpc, g.m)
+    {
     }
     // of the lane's i-th check, which is c
     template <typename ROWS>
     __device__ __forceinline__ unsigned at(const GraphDev& g, const ROWS& rows, const int i, const int c) const
     {
-        return in_reg ? ((bits >> i) & 1u) : rows.synd_of(g, c);
+        return !any ? 0u : in_reg ? ((bits >> i) & 1u) : rows.synd_of(g, c);
     }
 };
 
@@ -224,7 +270,7 @@ struct StepSynd {
 // (DV,DV,.)-regular graph, the messages are fetched into registers once; DV = 0: runtime degrees, they are read where they are used.
 // Only the fetch and the store differ between the two.  The runs are kept by their ends, as vn_sums takes them, and the two pointers
 // are formed once: with degrees kept instead, or the pointers formed again in the store, bp4gd_kernel's boxplus-phi loop takes 75
-// VGPRs instead of 72 and relay4_kernel<3,6> 89 instead of 88.
+// VGPRs instead of 72 (and relay4_kernel<3,6> took one more, measured before it moved onto the leg control of fgnn_legs.h).
 template <int DV>
 struct QubitSlots {
     static constexpr bool REGULAR = DV > 0;
@@ -308,6 +354,20 @@ __device__ __forceinline__ AttemptLds attempt_stage(float* lds, const AttemptArg
     return {tab, stamp, stamp + a.cpb};
 }
 
+// The per-workgroup words of a kernel on the leg control (fgnn_legs.h), behind the cpb codewords of lds_per_cw floats each:
+// stamp[cpb], wacc[cpb], ndone, leg_lds_words(cpb) ints.  Zeroed by the whole workgroup, before the kernel's first barrier
+struct LegLds {
+    int* stamp;
+    int* wacc;
+    int* ndone;
+};
+__device__ __forceinline__ LegLds leg_stage(float* lds, const int cpb, const int lds_per_cw)
+{
+    int* stamp = reinterpret_cast<int*>(lds + (size_t)cpb * lds_per_cw);
+    for (int i = threadIdx.x; i < leg_lds_words(cpb); i += blockDim.x) stamp[i] = 0;
+    return {stamp, stamp + cpb, stamp + 2 * cpb};
+}
+
 // The qubit phase of qubit v at step k of an attempt of T check updates, on the slots of `msg` and the channel LLRs lx, ly, lz:
 // the marginals after k updates, for k > 0 the test's decision into *d, for k < T the messages to the checks with the own weight ow
 // (an attempt's last test sends none); zero: a restarting attempt's first step, the owner zeroes the qubit's slots first
@@ -384,5 +444,94 @@ __device__ __forceinline__ void step_finish(const StepArgs& a, const size_t row,
     st[3] = k;
     atomicAdd(ndone, 1);
 }
+
+// ---------------------------------------------------------------------------------------------
+// The binary decoders on side 0 (hx): bp2_kernel (fgnn_bp2.hip) and relay_kernel (fgnn_relay.hip)
+// ---------------------------------------------------------------------------------------------
+
+// the rows of a thread's codeword b: element v of its llr_ch and output rows is at(v), its syndrome bits are synd_of; the pointers are
+// the launch's.  The products are formed where they are used, as an index and not a pointer (an inactive codeword's lie beyond the
+// arrays, and it reads and writes nothing): kept as a row pointer per lane, or formed once ahead of the loops, bp2_kernel's min-sum
+// instantiations measured 0.4 to 0.7 % slower
+struct BitRows {
+    int b, n, m;
+    const float* llr_ch;   // [B,n] logits or null
+    const uint8_t* synd;   // [B,m_x] or null
+    float llr_const;
+    __device__ __forceinline__ BitRows(const GraphDev& g, const float* llr_ch_, const float llr_const_, const uint8_t* synd_, const StepCw& cw)
+        : b(cw.b), n(g.n), m(g.m_x), llr_ch(llr_ch_), synd(synd_), llr_const(llr_const_)
+    {
+    }
+    __device__ __forceinline__ size_t at(const int v) const { return (size_t)b * n + v; }
+    // of a syndrome that is not null: StepSynd is told of a null one (any = false) and then asks for no bit
+    __device__ __forceinline__ unsigned synd_of(const GraphDev&, const int c) const { return synd[(size_t)b * m + c] & 1u; }
+    // the prior of bit v: the channel logit clamped to +-20, as an LLR
+    __device__ __forceinline__ float prior(const int v) const
+    {
+        float lc = llr_ch ? llr_ch[at(v)] : llr_const;
+        lc = FG_MIN(FG_MAX(lc, -20.0f), 20.0f);
+        return -1.0f * lc;
+    }
+};
+
+// The message slots [e0, e1) of bit v in the codeword's msg, the binary sibling of QubitSlots: DV > 0: a (DV,.)-regular hx, the
+// messages are fetched into registers once; DV = 0: runtime degrees through g.vptr_x, they are read where they are used
+template <int DV>
+struct BitSlots {
+    static constexpr bool REGULAR = DV > 0;
+    float* msg;
+    int e0, e1;
+    float mi[REGULAR ? DV : 1];
+
+    __device__ __forceinline__ BitSlots(const GraphDev& g, float* msg_, const int v) : msg(msg_)
+    {
+        e0 = REGULAR ? v * DV : g.vptr_x[v];
+        e1 = REGULAR ? e0 + DV : g.vptr_x[v + 1];
+    }
+    // the sum of the bit's c->v messages, ascending from 0
+    __device__ __forceinline__ float fetch()
+    {
+        float S = 0.0f;
+        if constexpr (REGULAR) {
+            float* mv = msg + e0;
+#pragma unroll
+            for (int j = 0; j < DV; ++j) mi[j] = mv[j];
+#pragma unroll
+            for (int j = 0; j < DV; ++j) S = S + mi[j];
+        } else {
+            for (int e = e0; e < e1; ++e) S = S + msg[e];
+        }
+        return S;
+    }
+    // in place of fetch() where no check update has written the slots yet: the messages count as zeros, whatever the slots hold,
+    // and their sum is 0.  The caller branches between the two (relay_kernel, on k > 0): folded into fetch(live), the regular bit
+    // loop compiled to two exec regions where the branch gives one
+    __device__ __forceinline__ void zeros()
+    {
+        if constexpr (REGULAR) {
+#pragma unroll
+            for (int j = 0; j < DV; ++j) mi[j] = 0.0f;
+        }
+    }
+    // the v->c messages from the total x: x minus the edge's own c->v message, as fetched, or after zeros() as zero
+    __device__ __forceinline__ void store(const float x)
+    {
+        if constexpr (REGULAR) {
+            float* mv = msg + e0;
+#pragma unroll
+            for (int j = 0; j < DV; ++j) mv[j] = x - mi[j];
+        } else {
+            for (int e = e0; e < e1; ++e) msg[e] = x - msg[e];
+        }
+    }
+    __device__ __forceinline__ void store_zeros(const float x)
+    {
+        if constexpr (REGULAR) {
+            store(x);
+        } else {
+            for (int e = e0; e < e1; ++e) msg[e] = x - 0.0f;
+        }
+    }
+};
 
 #endif
