@@ -49,7 +49,7 @@ def __getattr__(name):
     if name in ("SoftSyndromeBP4Decoder", "BP4_SoftSyndrome_Model"):
         from . import soft_syndrome as _ss
         return getattr(_ss, name)
-    if name in ("SpaceTimeBP4Decoder", "BP4_Phenomenological_Model"):
+    if name in ("SpaceTimeBP4Decoder", "BP4_Phenomenological_Model", "SpaceTimePostDecoder", "window_matrix"):
         from . import space_time as _st
         return getattr(_st, name)
     if name in ("GNN_BP4", "MLP"):

@@ -36,8 +36,12 @@
 //   control  solved / out of attempts: outputs, done;  k = T: the next attempt
 // No float atomics; no result depends on the order in which threads arrive, nor on the launch geometry.
 //
+// Soft outputs.  fgnn_stbp4_decode_soft launches the same kernel with the compile-time flag SOFT: where a window's outputs are
+// written, the totals of its qubits and the Gamma of its time variables are formed again from the LDS (st_soft_out below says why
+// that is exact for an unsolved window) and written next to them; no LDS is added and the plain instantiations keep their code.
+//
 // Registers.  Compiled for FGNN_STBP4_WAVES waves per SIMD, the most at which no instantiation needs scratch (DESIGN.md section 4,
-// "Repeated measurements", lists what each instantiation takes).
+// "Repeated measurements" and "Window post-processing", lists what each instantiation takes).
 #include <cmath>
 
 #include "fgnn_step.h"
@@ -62,6 +66,14 @@ struct StArgs : AttemptArgs {  // synd_x [B,R,m_x], synd_z [B,R,m_z], x_hat and 
     const uint8_t* prev_z;    // [B,m_z] or null
     uint8_t* u_x_hat;         // [B,R,m_x]
     uint8_t* u_z_hat;         // [B,R,m_z]
+};
+
+// fgnn_stbp4_decode_soft: StArgs and the three soft outputs.  A struct of its own, so that the plain instantiations keep their
+// kernel arguments and with them their code
+struct StSoftArgs : StArgs {
+    float* marg;   // [B,R,3,n]
+    float* gam_x;  // [B,R,m_x]
+    float* gam_z;  // [B,R,m_z]
 };
 
 // What the lanes read of the arguments beside the frame's, copied out once by value: a select between a field of the argument struct
@@ -126,9 +138,63 @@ __device__ __forceinline__ float st_gamma(const GraphDev& g, const StIn& in, con
     return is_x ? (last ? in.gxl : in.gx) : (last ? in.gzl : in.gz);
 }
 
+// The soft outputs of a finished window, from its LDS (SOFT instantiations, control section).  An unsolved window ends at k = T of its
+// last attempt: that step's qubit phase sent no messages (attempt_qubit returns after the decision, the time variables `continue`
+// before they write a / b) and its check phase made no update, so the edge slots still hold the c->v messages of update T and the
+// b / a slots w_dn / w_up.  The totals and Gamma are formed again from them, by the routines and in the order of the qubit phase:
+// the values the decisions and u_hat of the last test were taken from.  A window solved at k < T has had its slots overwritten by
+// update k + 1: the rows of every solved window are +0.0f
+template <int DV>
+__device__ __forceinline__ void st_soft_out(const GraphDev& g, const StSoftArgs& a, const StIn& in, float* win, const float* bsl,
+                                            const float* asl, const float* lch, const float llr_const, const size_t row, const int lane,
+                                            const bool unsolved)
+{
+    const int n = g.n, m = g.m, R = a.rounds, NQ = R * n, NC = R * m;
+    float* const marg = a.marg;
+    float* const gam_x = a.gam_x;
+    float* const gam_z = a.gam_z;
+    // the four scalar gammas as values the compiler takes for new here: left to it, the selects among them in this second place
+    // that reads them become an indexed read of a four-float table in scratch
+    float gx = in.gx, gz = in.gz, gxl = in.gxl, gzl = in.gzl;
+    asm volatile("" : "+s"(gx), "+s"(gz), "+s"(gxl), "+s"(gzl));
+    for (int i = lane, v = lane, t = 0; i < NQ; i += a.tpc, v += a.tpc) {
+        while (v >= n) { v -= n; ++t; }
+        float X = 0.0f, Y = 0.0f, Z = 0.0f;
+        if (unsolved) {
+            const float lx = lch ? lch[v] : llr_const;
+            const float ly = lch ? lch[n + v] : llr_const;
+            const float lz = lch ? lch[2 * n + v] : llr_const;
+            QubitSlots<DV> q(g, win + t * a.area, v);
+            float Sz, Sx;
+            q.fetch(Sz, Sx);
+            vn_totals(Sz, Sx, lx, ly, lz, X, Y, Z);
+        }
+        float* mg = marg + (row * R + t) * 3 * n + v;
+        mg[0] = X;
+        mg[n] = Y;
+        mg[2 * (size_t)n] = Z;
+    }
+    for (int j = lane, c = lane, t = 0; j < NC; j += a.tpc, c += a.tpc) {
+        while (c >= m) { c -= m; ++t; }
+        float G = 0.0f;
+        if (unsolved) {
+            const bool is_x = c < g.m_x, last = t == R - 1;
+            const float* gl = is_x ? in.glx : in.glz;  // st_gamma on the values above
+            float gm = is_x ? (last ? gxl : gx) : (last ? gzl : gz);
+            if (gl) gm = gl[(row * R + t) * (size_t)(is_x ? g.m_x : g.m_z) + (size_t)(is_x ? c : c - g.m_x)];
+            const float s1 = gm + bsl[j];
+            G = last ? s1 : s1 + asl[j];
+        }
+        if (c < g.m_x) gam_x[(row * R + t) * g.m_x + c] = G;
+        else gam_z[(row * R + t) * g.m_z + (c - g.m_x)] = G;
+    }
+}
+
 // DV/DC > 0: (DV,DV,DC)-regular graphs with the packed slot rows of g.cslot16 (min-sum); DV = DC = 0: runtime degrees, the loop.
-template <int CN_TYPE, int DV, int DC>
-__global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_STBP4_WAVES))) stbp4_kernel(GraphDev g, StArgs a)
+// SOFT: fgnn_stbp4_decode_soft, the same steps, and st_soft_out where a window's outputs are written.
+template <int CN_TYPE, int DV, int DC, bool SOFT = false>
+__global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_STBP4_WAVES)))
+stbp4_kernel(GraphDev g, std::conditional_t<SOFT, StSoftArgs, StArgs> a)
 {
     FG_LOG_TAB_SETUP();
     constexpr bool REGULAR = DV > 0;
@@ -253,6 +319,7 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_
                         if (c < g.m_x) a.u_x_hat[(row * R + t) * g.m_x + c] = uh[j];
                         else a.u_z_hat[(row * R + t) * g.m_z + (c - g.m_x)] = uh[j];
                     }
+                    if constexpr (SOFT) st_soft_out<DV>(g, a, in, win, bsl, asl, lch, llr_const, row, lane, !sat);
                     if (lane == 0) step_finish(a, row, sat, ctl.r, ctl.its, k, w.ndone);
                     ctl.done = true;
                 } else if (k == T) {
@@ -315,13 +382,12 @@ LaunchGeom st_geom(const fgnn_graph* g, int B, int R)
     return L;
 }
 
-}  // namespace
-
-extern "C" int fgnn_stbp4_decode(const fgnn_graph* g, int cn_type, int num_attempts, const float* factor, const float* own, int pre_iter,
-                                 int attempt_iter, int restart, int rounds, const float* llr_ch, float llr_const, const uint8_t* synd_x,
-                                 const uint8_t* synd_z, const uint8_t* prev_x, const uint8_t* prev_z, const float* synd_llr_x, float gamma_x,
-                                 float gamma_last_x, const float* synd_llr_z, float gamma_z, float gamma_last_z, int B, uint8_t* x_hat,
-                                 uint8_t* z_hat, uint8_t* u_x_hat, uint8_t* u_z_hat, int32_t* stats, void* stream)
+// fgnn_stbp4_decode and fgnn_stbp4_decode_soft: one set of checks and one launch; soft: the three soft arrays are asked for
+int st_decode(const bool soft, const fgnn_graph* g, int cn_type, int num_attempts, const float* factor, const float* own, int pre_iter,
+              int attempt_iter, int restart, int rounds, const float* llr_ch, float llr_const, const uint8_t* synd_x, const uint8_t* synd_z,
+              const uint8_t* prev_x, const uint8_t* prev_z, const float* synd_llr_x, float gamma_x, float gamma_last_x,
+              const float* synd_llr_z, float gamma_z, float gamma_last_z, int B, uint8_t* x_hat, uint8_t* z_hat, uint8_t* u_x_hat,
+              uint8_t* u_z_hat, int32_t* stats, float* marg, float* gam_x, float* gam_z, void* stream)
 {
     if (int err = step_check_args(g, cn_type, B)) return err;
     if (int err = attempt_check_sched(num_attempts, pre_iter, attempt_iter, restart)) return err;
@@ -340,9 +406,10 @@ extern "C" int fgnn_stbp4_decode(const fgnn_graph* g, int cn_type, int num_attem
     }
     if (B == 0) return FGNN_OK;  // an empty batch needs no buffers
     if (!x_hat || !z_hat || !u_x_hat || !u_z_hat || !stats) return fgnn_fail(FGNN_ERR_ARG, "no output buffer");
+    if (soft && (!marg || !gam_x || !gam_z)) return fgnn_fail(FGNN_ERR_ARG, "no soft output buffer");
     FGNN_DEVICE_GUARD(g->device);
     const LaunchGeom L = st_geom(g, B, rounds);
-    StArgs a;
+    StSoftArgs a;
     attempt_args_fill(a, L, B, num_attempts, factor, own, pre_iter, attempt_iter, restart, llr_ch, llr_const, synd_x, synd_z, x_hat, z_hat,
                       stats);
     a.rounds = rounds;
@@ -363,9 +430,39 @@ extern "C" int fgnn_stbp4_decode(const fgnn_graph* g, int cn_type, int num_attem
     a.d_off = (int)lay.d_off;
     a.u_off = (int)lay.u_off;
     a.lds_per_cw = (int)lay.per_win;
+    a.marg = marg;
+    a.gam_x = gam_x;
+    a.gam_z = gam_z;
     const size_t lds_bytes = st_lds_bytes(g->d, rounds, L.cpb);
+    const hipStream_t st = static_cast<hipStream_t>(stream);
     return step_dispatch(g, cn_type, [&](auto cn, auto dv, auto dc) {
-        return fgnn_launch(stbp4_kernel<decltype(cn)::value, decltype(dv)::value, decltype(dc)::value>, dim3(L.blocks), dim3(L.threads),
-                           lds_bytes, static_cast<hipStream_t>(stream), g->d, a);
+        constexpr int CN = decltype(cn)::value, DV = decltype(dv)::value, DC = decltype(dc)::value;
+        if (soft) return fgnn_launch(stbp4_kernel<CN, DV, DC, true>, dim3(L.blocks), dim3(L.threads), lds_bytes, st, g->d, a);
+        return fgnn_launch(stbp4_kernel<CN, DV, DC, false>, dim3(L.blocks), dim3(L.threads), lds_bytes, st, g->d, StArgs(a));
     });
+}
+
+}  // namespace
+
+extern "C" int fgnn_stbp4_decode(const fgnn_graph* g, int cn_type, int num_attempts, const float* factor, const float* own, int pre_iter,
+                                 int attempt_iter, int restart, int rounds, const float* llr_ch, float llr_const, const uint8_t* synd_x,
+                                 const uint8_t* synd_z, const uint8_t* prev_x, const uint8_t* prev_z, const float* synd_llr_x, float gamma_x,
+                                 float gamma_last_x, const float* synd_llr_z, float gamma_z, float gamma_last_z, int B, uint8_t* x_hat,
+                                 uint8_t* z_hat, uint8_t* u_x_hat, uint8_t* u_z_hat, int32_t* stats, void* stream)
+{
+    return st_decode(false, g, cn_type, num_attempts, factor, own, pre_iter, attempt_iter, restart, rounds, llr_ch, llr_const, synd_x, synd_z,
+                     prev_x, prev_z, synd_llr_x, gamma_x, gamma_last_x, synd_llr_z, gamma_z, gamma_last_z, B, x_hat, z_hat, u_x_hat, u_z_hat,
+                     stats, nullptr, nullptr, nullptr, stream);
+}
+
+extern "C" int fgnn_stbp4_decode_soft(const fgnn_graph* g, int cn_type, int num_attempts, const float* factor, const float* own, int pre_iter,
+                                      int attempt_iter, int restart, int rounds, const float* llr_ch, float llr_const,
+                                      const uint8_t* synd_x, const uint8_t* synd_z, const uint8_t* prev_x, const uint8_t* prev_z,
+                                      const float* synd_llr_x, float gamma_x, float gamma_last_x, const float* synd_llr_z, float gamma_z,
+                                      float gamma_last_z, int B, uint8_t* x_hat, uint8_t* z_hat, uint8_t* u_x_hat, uint8_t* u_z_hat,
+                                      int32_t* stats, float* marg, float* gam_x, float* gam_z, void* stream)
+{
+    return st_decode(true, g, cn_type, num_attempts, factor, own, pre_iter, attempt_iter, restart, rounds, llr_ch, llr_const, synd_x, synd_z,
+                     prev_x, prev_z, synd_llr_x, gamma_x, gamma_last_x, synd_llr_z, gamma_z, gamma_last_z, B, x_hat, z_hat, u_x_hat, u_z_hat,
+                     stats, marg, gam_x, gam_z, stream);
 }

@@ -970,6 +970,22 @@ class TannerGraph:
         cumulative, `u_x_hat [B,R,m_x], u_z_hat [B,R,m_z]` uint8, `stats [B,4]` int32 = found, the attempt of the last test,
         iterations, k of the last test)`, per window.  A window that does not fit the LDS is refused with a ValueError that names the
         largest number of rounds that fits."""
+        return self._stbp4_run(False, synd_x, synd_z, factors, owns, pre_iter, attempt_iter, cn_type, restart, rounds, prev_x, prev_z, llr_ch,
+                               llr_const, synd_llr_x, synd_llr_z, gamma_x, gamma_z, gamma_last_x, gamma_last_z, B)
+
+    def stbp4_decode_soft(self, synd_x, synd_z, factors, owns, pre_iter, attempt_iter, cn_type="minsum", restart=True, rounds=None,
+                          prev_x=None, prev_z=None, llr_ch=None, llr_const=0.0, synd_llr_x=None, synd_llr_z=None, gamma_x=float("inf"),
+                          gamma_z=float("inf"), gamma_last_x=float("inf"), gamma_last_z=float("inf"), B=None):
+        """`stbp4_decode` with the soft values of the last test (`fgnn_stbp4_decode_soft`): the same arguments, and the same five
+        outputs bit for bit, followed by `marg [B,R,3,n]`, `gam_x [B,R,m_x]` and `gam_z [B,R,m_z]` (float32).  For a window that was
+        not solved they hold the totals X, Y, Z of every qubit and round and the Gamma of every time variable, the values the
+        decisions and u_hat were taken from; the rows of a solved window are zero."""
+        return self._stbp4_run(True, synd_x, synd_z, factors, owns, pre_iter, attempt_iter, cn_type, restart, rounds, prev_x, prev_z, llr_ch,
+                               llr_const, synd_llr_x, synd_llr_z, gamma_x, gamma_z, gamma_last_x, gamma_last_z, B)
+
+    def _stbp4_run(self, soft, synd_x, synd_z, factors, owns, pre_iter, attempt_iter, cn_type, restart, rounds, prev_x, prev_z, llr_ch,
+                   llr_const, synd_llr_x, synd_llr_z, gamma_x, gamma_z, gamma_last_x, gamma_last_z, B):
+        """The checks, allocations and call of `stbp4_decode` and `stbp4_decode_soft`."""
         cn = self._cn(cn_type)
         factors, owns = self._tables_in(factors, owns)
         windows = (synd_x, synd_z, synd_llr_x, synd_llr_z)
@@ -997,12 +1013,82 @@ class TannerGraph:
         uxh = self._new((B, R, self.m_x), torch.uint8)
         uzh = self._new((B, R, self.m_z), torch.uint8)
         stats = self._new((B, 4), torch.int32)
-        check(_lib.lib().fgnn_stbp4_decode(self.handle, cn, len(factors), factors.ctypes.data, owns.ctypes.data, int(pre_iter),
-                                           int(attempt_iter), int(restart), R, _ptr(llr_ch), float(llr_const), _ptr(synd_x), _ptr(synd_z),
-                                           _ptr(prev_x), _ptr(prev_z), _ptr(synd_llr_x), float(gamma_x), float(gamma_last_x),
-                                           _ptr(synd_llr_z), float(gamma_z), float(gamma_last_z), B, _ptr(xh), _ptr(zh), _ptr(uxh),
-                                           _ptr(uzh), _ptr(stats), _stream(self.device)))
-        return xh, zh, uxh, uzh, stats
+        args = (self.handle, cn, len(factors), factors.ctypes.data, owns.ctypes.data, int(pre_iter), int(attempt_iter), int(restart), R,
+                _ptr(llr_ch), float(llr_const), _ptr(synd_x), _ptr(synd_z), _ptr(prev_x), _ptr(prev_z), _ptr(synd_llr_x), float(gamma_x),
+                float(gamma_last_x), _ptr(synd_llr_z), float(gamma_z), float(gamma_last_z), B, _ptr(xh), _ptr(zh), _ptr(uxh), _ptr(uzh),
+                _ptr(stats))
+        if not soft:
+            check(_lib.lib().fgnn_stbp4_decode(*args, _stream(self.device)))
+            return xh, zh, uxh, uzh, stats
+        marg = self._new((B, R, 3, self.n), torch.float32)
+        gam_x = self._new((B, R, self.m_x), torch.float32)
+        gam_z = self._new((B, R, self.m_z), torch.float32)
+        check(_lib.lib().fgnn_stbp4_decode_soft(*args, _ptr(marg), _ptr(gam_x), _ptr(gam_z), _stream(self.device)))
+        return xh, zh, uxh, uzh, stats, marg, gam_x, gam_z
+
+    # ---- one side of a window as a binary problem (fgnn_st_window_problem / fgnn_st_window_apply) -----------------------------------
+    def _st_side(self, side):
+        if side not in (0, 1):
+            raise ValueError("side must be 0 or 1")
+        return self.m_x if side == 0 else self.m_z
+
+    def _st_index_in(self, index, nact):
+        """(index, nact) of a window list: int32 on the device, at least `nact` entries (None: windows 0 .. nact-1)."""
+        nact = int(nact)
+        if nact < 0:
+            raise ValueError("nact must be >= 0")
+        if index is not None:
+            index = self._opt_any(index, torch.int32, "index")
+            if index.numel() < nact:
+                raise ValueError(f"index holds {index.numel()} entries, nact is {nact}")
+        return index, nact
+
+    def st_window_problem(self, side, marg, gam, synd=None, prev=None, index=None, nact=None, rounds=None):
+        """One side of the listed windows as the binary problem ``H_st [e ; u] = d`` (`fgnn_st_window_problem`): `marg [B,R,3,n]` and
+        `gam [B,R,m_side]` are the soft outputs of `stbp4_decode_soft` for side 0 (hx: `gam_x`) or 1 (hz: `gam_z`), `synd [B,R,m_side]`
+        / `prev [B,m_side]` the raw syndromes the decoder was given (None: zero).  `index` (int32, device) lists the windows and `nact`
+        says how many of them count (`compact`); index None: windows 0 .. nact-1, nact None: all B.  Returns `(d [nact, R m_side]`
+        uint8, `llr [nact, R (n + m_side)]` float32)`, row i for window index[i], in the row and column order of
+        `space_time.window_matrix`: what `lsd` and `osd0` take as `synd` and `llr_bin` on that matrix's graph."""
+        m = self._st_side(side)
+        if marg.dim() != 4:
+            raise ValueError("marg must have shape [B, R, 3, n]")
+        B, R = int(marg.shape[0]), int(marg.shape[1]) if rounds is None else int(rounds)
+        if R < 1:
+            raise ValueError("rounds must be >= 1")
+        marg = self._chk(marg, (B, R, 3, self.n), torch.float32, "marg")
+        gam = self._chk(gam, (B, R, m), torch.float32, "gam")
+        synd = self._opt(synd, (B, R, m), torch.uint8, "synd")
+        prev = self._opt(prev, (B, m), torch.uint8, "prev")
+        index, nact = self._st_index_in(index, B if nact is None else nact)
+        if index is None and nact > B:
+            raise ValueError(f"nact is {nact}, the batch holds {B} windows")
+        d = self._new((nact, R * m), torch.uint8)
+        llr = self._new((nact, R * (self.n + m)), torch.float32)
+        check(_lib.lib().fgnn_st_window_problem(self.handle, int(side), R, _ptr(synd), _ptr(prev), _ptr(marg), _ptr(gam), _ptr(index), nact,
+                                                _ptr(d), _ptr(llr), _stream(self.device)))
+        return d, llr
+
+    def st_window_apply(self, side, e, hat, u_hat, index=None, nact=None):
+        """Write the solutions `e [nact, R (n + m_side)]` (uint8, the column order of `space_time.window_matrix`) of the listed
+        windows into the decoder's outputs in place (`fgnn_st_window_apply`): side 0 takes `hat = z_hat [B,R,n]` and `u_hat = u_x_hat
+        [B,R,m_x]`, side 1 `x_hat` and `u_z_hat`.  `index` / `nact` as `st_window_problem` (nact None: the rows of `e`); the rows of
+        windows that are not listed are left as they are.  Returns `(hat, u_hat)`."""
+        m = self._st_side(side)
+        if hat.dim() != 3:
+            raise ValueError("hat must have shape [B, R, n]")
+        B, R = int(hat.shape[0]), int(hat.shape[1])
+        hat = self._chk_out(hat, (B, R, self.n), torch.uint8, "hat")
+        u_hat = self._chk_out(u_hat, (B, R, m), torch.uint8, "u_hat")
+        index, nact = self._st_index_in(index, int(e.shape[0]) if nact is None else nact)
+        if index is None and nact > B:
+            raise ValueError(f"nact is {nact}, the batch holds {B} windows")
+        if int(e.shape[0]) < nact:
+            raise ValueError(f"e holds {int(e.shape[0])} rows, nact is {nact}")
+        e = self._chk(e, (int(e.shape[0]), R * (self.n + m)), torch.uint8, "e")
+        check(_lib.lib().fgnn_st_window_apply(self.handle, int(side), R, _ptr(e), _ptr(index), nact, _ptr(hat), _ptr(u_hat),
+                                              _stream(self.device)))
+        return hat, u_hat
 
     @staticmethod
     def syndrome_noise_seeds(seed):

@@ -67,7 +67,8 @@ class SpaceTimeBP4Decoder(CodeDecoder):
         self.last_correction_x, self.last_correction_z = _xor_rounds(x_hat), _xor_rounds(z_hat)
         return x_hat, z_hat, u_x_hat, u_z_hat, stats
 
-    def __call__(self, inputs):
+    def _window_in(self, inputs):
+        """``(synd_x [bs,R,m_x], synd_z [bs,R,m_z], llr_ch [bs,3,n])`` of a ``(llr_ch, syndrome_x, syndrome_z)`` call."""
         device = self.graph.device
         llr_ch, syndrome_x, syndrome_z = inputs
         llr_ch = llr_ch_in(llr_ch, self._num_vns, device)
@@ -82,7 +83,156 @@ class SpaceTimeBP4Decoder(CodeDecoder):
             synd.append((s.to(torch.int64) & 1).to(torch.uint8).permute(2, 0, 1).contiguous())
         if synd[0].shape[1] != synd[1].shape[1]:
             raise ValueError("the two syndromes must hold the same number of rounds")
-        self.decode(synd[0], synd[1], gamma=self.gamma, gamma_last=self.gamma_last, llr_ch=llr_ch)
+        return synd[0], synd[1], llr_ch
+
+    def __call__(self, inputs):
+        synd_x, synd_z, llr_ch = self._window_in(inputs)
+        self.decode(synd_x, synd_z, gamma=self.gamma, gamma_last=self.gamma_last, llr_ch=llr_ch)
+        return self.last_correction_x.to(torch.int64), self.last_correction_z.to(torch.float64)
+
+    call = __call__
+
+
+def window_matrix(h, rounds):
+    """One side of a window of ``rounds`` measurements as the binary matrix ``H_st`` (uint8, host) of ``H_st [e ; u] = d``: check
+    (c,t) is row ``t m + c``, data bit (v,t) column ``t n + v`` and time bit (c,t) column ``R n + t m + c``, with ``h [m,n]`` on the
+    block diagonal and ones at time bits (c,t) and (c,t-1) of row (c,t).  The time columns are unit lower-bidiagonal, so the rank is
+    ``R m``; ``rounds = 1`` gives ``[h | I]``.  The layout is that of `fgnn_st_window_problem` (include/fgnn.h)."""
+    h = (np.asarray(h) != 0).astype(np.uint8)
+    if not isinstance(rounds, (int, np.integer)) or rounds < 1:
+        raise ValueError("rounds must be a positive integer")
+    R, (m, n) = int(rounds), h.shape
+    H = np.zeros((R * m, R * (n + m)), np.uint8)
+    eye = np.arange(m)
+    for t in range(R):
+        H[t * m:(t + 1) * m, t * n:(t + 1) * n] = h
+        H[t * m + eye, R * n + t * m + eye] = 1
+        if t > 0:
+            H[t * m + eye, R * n + (t - 1) * m + eye] = 1
+    return H
+
+
+LSD_MAX_CHECKS = 8192   # fgnn_lsd: checks per side
+OSD_MAX_BITS = 16384    # fgnn_osd_ws: columns
+POST_METHODS = ("lsd", "osd0")
+
+
+class SpaceTimePostDecoder:
+    """``SpaceTimePostDecoder(decoder, method="lsd", max_pivots=None, max_rounds=None, fallback="osd0")``: a `SpaceTimeBP4Decoder`
+    with a post-processor behind it.  ``decode(...)`` takes the arguments of `SpaceTimeBP4Decoder.decode` and returns the same five
+    outputs; ``rounds``, ``graph``, the call with ``(llr_ch, syndrome_x, syndrome_z)`` and the ``last_*`` attributes are the
+    decoder's too, so `BP4_Phenomenological_Model` takes it in the decoder's place, sliding windows included.
+
+    The window is decoded by `TannerGraph.stbp4_decode_soft`.  The windows it leaves unsolved are compacted, and each of their two
+    sides is solved as the binary problem ``H_st [e ; u] = d`` (`window_matrix`, `TannerGraph.st_window_problem`) on the binary
+    LLRs of the qubits' last marginals and the Gamma of the time variables: by LSD (``method="lsd"``: `fgnn_lsd` with ``max_pivots``
+    / ``max_rounds`` as `LSD_Decoder`), by OSD-0 on the basis of all rows (``method="osd0"``), or by LSD and then OSD-0 for the
+    windows LSD returns with found = 0 on either side (``fallback="osd0"``; ``fallback=None`` leaves them as LSD's read-out), as
+    `BP4_LSD_Model`.  The solutions replace the estimates of those windows (`TannerGraph.st_window_apply`) and ``stats[:,0]``
+    becomes 1 where both sides came back found: the estimate then satisfies the window's checks, and with them the hand-over ``s ^
+    u_hat`` to the next window does.  Solved windows are returned exactly as `SpaceTimeBP4Decoder` returns them.
+
+    After a call ``last_num_post`` counts the windows post-processed, ``last_num_fallback`` those handed on to OSD-0, and
+    ``last_post_stats`` [2, B, 4] int32 holds `fgnn_lsd`'s stats (found, rounds, columns, pivots) of side 0 (hx) and 1 (hz), the
+    rows of untouched windows (and every row under ``method="osd0"``) reading "found, nothing done".  A window whose side has more
+    than 8192 checks is beyond `fgnn_lsd`, one with more than 16384 columns beyond OSD-0: both are refused with a ValueError."""
+
+    def __init__(self, decoder, method="lsd", max_pivots=None, max_rounds=None, fallback="osd0"):
+        if method not in POST_METHODS:
+            raise ValueError(f"method must be one of {POST_METHODS}")
+        if fallback not in ("osd0", None):
+            raise ValueError("fallback must be 'osd0' or None")
+        self.decoder, self.method, self.fallback = decoder, method, fallback
+        self.max_pivots = 0 if max_pivots is None else int(max_pivots)
+        self.max_rounds = 0 if max_rounds is None else int(max_rounds)
+        if self.max_pivots < 0 or self.max_rounds < 0:
+            raise ValueError("max_pivots and max_rounds must be >= 0")
+        self.rounds, self.graph, self.code = decoder.rounds, decoder.graph, decoder.code
+        self.gamma = self.gamma_last = INF
+        self._graphs = {}  # (side, R) -> the binary graph of window_matrix(h_side, R)
+        from .bp_osd import _OsdWorkspace
+        self._ws = _OsdWorkspace()  # OSD-0 on a window graph the LDS-resident kernel refuses
+        self.last_stats = self.last_u_x_hat = self.last_u_z_hat = self.last_correction_x = self.last_correction_z = None
+        self.last_post_stats = None
+        self.last_num_post = self.last_num_fallback = 0
+
+    @property
+    def _osd_reachable(self):
+        return self.method == "osd0" or self.fallback == "osd0"
+
+    def window_graph(self, side, rounds):
+        """The binary `TannerGraph` of ``window_matrix(hx or hz, rounds)`` (cached per side and rounds), with the basis of all rows
+        installed when OSD-0 can be reached."""
+        key = (int(side), int(rounds))
+        if key not in self._graphs:
+            from .decoding import _binary_graph
+            h = np.asarray(self.code.hx if side == 0 else self.code.hz)
+            m, n = h.shape
+            R = int(rounds)
+            if self.method == "lsd" and R * m > LSD_MAX_CHECKS:
+                raise ValueError(f"a window of {R} rounds has {R * m} checks on side {side}, fgnn_lsd takes at most {LSD_MAX_CHECKS}: "
+                                 "use method='osd0' or a shorter window")
+            if self._osd_reachable and R * (n + m) > OSD_MAX_BITS:
+                raise ValueError(f"a window of {R} rounds has {R * (n + m)} columns on side {side}, OSD-0 takes at most {OSD_MAX_BITS}: "
+                                 "use a shorter window" + (" or fallback=None" if self.method == "lsd" else ""))
+            wg = _binary_graph(window_matrix(h, R), None, self.graph.device)
+            if self._osd_reachable:
+                wg.set_basis(0, np.arange(R * m, dtype=np.int32))
+            self._graphs[key] = wg
+        return self._graphs[key]
+
+    def decode(self, synd_x, synd_z, prev_x=None, prev_z=None, synd_llr_x=None, synd_llr_z=None, gamma=INF, gamma_last=INF, llr_ch=None,
+               llr_const=0.0, rounds=None):
+        """`SpaceTimeBP4Decoder.decode` followed by the post-processing of the unsolved windows."""
+        from .bp_osd import _run_osd0
+        from .lsd import _fresh_stats, _missed
+        d, g = self.decoder, self.graph
+        given = next((t for t in (synd_x, synd_z, synd_llr_x, synd_llr_z) if t is not None), None)
+        R = int(rounds) if rounds is not None else (int(given.shape[1]) if given is not None and given.dim() == 3 else self.rounds)
+        if R > self.rounds:
+            raise ValueError(f"a window holds at most {self.rounds} rounds, got {R}")
+        x_hat, z_hat, u_x_hat, u_z_hat, stats, marg, gam_x, gam_z = g.stbp4_decode_soft(
+            synd_x, synd_z, d.factors, d.owns, d.num_iter, d.num_iter, d.cn_type, restart=d.restart, rounds=R, prev_x=prev_x, prev_z=prev_z,
+            llr_ch=llr_ch, llr_const=llr_const, synd_llr_x=synd_llr_x, synd_llr_z=synd_llr_z, gamma_x=gamma, gamma_z=gamma,
+            gamma_last_x=gamma_last, gamma_last_z=gamma_last)
+        B = int(stats.shape[0])
+        index, nact = g.compact((stats[:, 0] == 0).to(torch.uint8), 1)
+        self.last_num_post, self.last_num_fallback = nact, 0
+        self.last_post_stats = post = _fresh_stats(g, B, 2)
+        if nact:
+            sides = ((synd_x, prev_x, gam_x, z_hat, u_x_hat), (synd_z, prev_z, gam_z, x_hat, u_z_hat))
+            wgs = [self.window_graph(side, R) for side in (0, 1)]
+            lsd_stats = _fresh_stats(g, nact, 2)  # of the compact rows
+            work = []
+            for side, (synd, prev, gam, _, _) in enumerate(sides):
+                wg = wgs[side]
+                dd, llr = g.st_window_problem(side, marg, gam, synd=synd, prev=prev, index=index, nact=nact)
+                e = torch.zeros((nact, wg.n), dtype=torch.uint8, device=g.device)
+                if self.method == "lsd":
+                    wg.lsd(0, dd, e, llr_bin=llr, max_pivots=self.max_pivots, max_rounds=self.max_rounds, stats=lsd_stats[side])
+                else:
+                    _run_osd0(wg, self._ws, 0, dd, e, llr_bin=llr)
+                work.append((dd, llr, e))
+            found = (lsd_stats[:, :, 0] != 0).all(0)
+            if self.method == "lsd" and self.fallback == "osd0":
+                index2, nact2 = _missed(g, lsd_stats)
+                self.last_num_fallback = nact2
+                if nact2:
+                    for side, (dd, llr, e) in enumerate(work):
+                        _run_osd0(wgs[side], self._ws, 0, dd, e, llr_bin=llr, index=index2, nact=nact2)
+                    found = torch.ones_like(found)
+            for side, (_, _, _, hat, u_hat) in enumerate(sides):
+                g.st_window_apply(side, work[side][2], hat, u_hat, index=index, nact=nact)
+            rows = index[:nact].long()
+            post[:, rows] = lsd_stats
+            stats[rows, 0] = found.to(stats.dtype)
+        self.last_stats, self.last_u_x_hat, self.last_u_z_hat = stats, u_x_hat, u_z_hat
+        self.last_correction_x, self.last_correction_z = _xor_rounds(x_hat), _xor_rounds(z_hat)
+        return x_hat, z_hat, u_x_hat, u_z_hat, stats
+
+    def __call__(self, inputs):
+        synd_x, synd_z, llr_ch = self.decoder._window_in(inputs)
+        self.decode(synd_x, synd_z, gamma=self.gamma, gamma_last=self.gamma_last, llr_ch=llr_ch)
         return self.last_correction_x.to(torch.int64), self.last_correction_z.to(torch.float64)
 
     call = __call__

@@ -524,6 +524,55 @@ int fgnn_stbp4_decode(const fgnn_graph* g, int cn_type, int num_attempts, const 
                       const float* synd_llr_z /* [B,R,m_z] or NULL */, float gamma_z, float gamma_last_z, int B,
                       uint8_t* x_hat /* [B,R,n] */, uint8_t* z_hat /* [B,R,n] */, uint8_t* u_x_hat /* [B,R,m_x] */,
                       uint8_t* u_z_hat /* [B,R,m_z] */, int32_t* stats /* [B,4] */, void* stream);
+/* fgnn_stbp4_decode with the soft values of the last test, for a post-processor of the unsolved windows.  The arguments are those of
+ * fgnn_stbp4_decode followed by marg [B,R,3,n], gam_x [B,R,m_x] and gam_z [B,R,m_z] (device float32).
+ * Hard outputs: x_hat, z_hat, u_x_hat, u_z_hat and stats equal fgnn_stbp4_decode's bit for bit, for every input.
+ * Unsolved window (stats[b,0] == 0): marg[b,t,0..2,v] = the totals X, Y, Z (Y = (Sz + Sx) + ly, X = Sz + lx, Z = Sx + lz, the sums
+ * over the qubit's hz and hx messages each ascending from 0, as fgnn_mbp4_decode forms them) of qubit (v,t) in the last test, the
+ * values its decision was taken from; gam_*[b,t,c] = Gamma_{c,t} of that test as defined above, (gamma + w_dn) + w_up for t < R-1 and
+ * gamma + w_dn for t = R-1, the value u_hat_{c,t} was taken from.  Same float operations in the same order as the decoder's own: an
+ * unsolved window ends at the last test of its last attempt, after which no message is sent and no check is updated, so the LDS
+ * still holds the c->v messages, w_dn and w_up of that test and the values are formed again from them.  +inf is a legal Gamma.
+ * Solved window (stats[b,0] == 1): every element of its rows of marg, gam_x and gam_z is +0.0f (a window solved before the end of an
+ * attempt has had its messages overwritten by the next update, so no marginals are defined for it).  No element of any output is
+ * left unwritten.
+ * Argument checks as fgnn_stbp4_decode, in its order; then a NULL marg, gam_x or gam_z is FGNN_ERR_ARG.  B = 0 needs no buffers.  The
+ * soft outputs take no LDS: a window fits here iff it fits fgnn_stbp4_decode, and is refused with the same message. */
+int fgnn_stbp4_decode_soft(const fgnn_graph* g, int cn_type, int num_attempts, const float* factor, const float* own, int pre_iter,
+                           int attempt_iter, int restart, int rounds, const float* llr_ch, float llr_const,
+                           const uint8_t* synd_x /* [B,R,m_x] or NULL */, const uint8_t* synd_z /* [B,R,m_z] or NULL */,
+                           const uint8_t* prev_x /* [B,m_x] or NULL */, const uint8_t* prev_z /* [B,m_z] or NULL */,
+                           const float* synd_llr_x /* [B,R,m_x] or NULL */, float gamma_x, float gamma_last_x,
+                           const float* synd_llr_z /* [B,R,m_z] or NULL */, float gamma_z, float gamma_last_z, int B,
+                           uint8_t* x_hat /* [B,R,n] */, uint8_t* z_hat /* [B,R,n] */, uint8_t* u_x_hat /* [B,R,m_x] */,
+                           uint8_t* u_z_hat /* [B,R,m_z] */, int32_t* stats /* [B,4] */, float* marg /* [B,R,3,n] */,
+                           float* gam_x /* [B,R,m_x] */, float* gam_z /* [B,R,m_z] */, void* stream);
+/* One side of a window as a binary problem, and its solution put back.  For side 0 (hx: the Z components z_hat and the flips u_x) or
+ * side 1 (hz: x_hat and u_z), with h = that side's matrix, m = m_side and R = rounds, a window is H_st [e ; u] = d over GF(2):
+ *   row     t m + c          check (c,t):      (h e_t)_c ^ u_{c,t} ^ u_{c,t-1} = d_{c,t}   (u_{c,-1} = 0)
+ *   column  t n + v          data bit (v,t),   t = 0 .. R-1
+ *   column  R n + t m + c    time bit (c,t),   t = 0 .. R-1
+ * R m rows and R (n + m) columns.  The time columns form a unit lower-bidiagonal block, so H_st has full row rank R m; R = 1 is [h | I].
+ * A binary graph of H_st (side 0 of a graph created from it) is what fgnn_lsd, fgnn_osd0 and fgnn_osd_ws solve it on, with llr_bin.
+ * Both calls run over the list index[0..nact) of windows (device int32, distinct entries; NULL = windows 0 .. nact-1), one workgroup
+ * per listed window; row i of the compact arrays belongs to window index[i], and the window's own rows are read or written in place.
+ * fgnn_st_window_problem: d_out[i, t m + c] = d_{c,t} exactly as fgnn_stbp4_decode forms it from synd [B,R,m] (NULL = all zero) and
+ * prev [B,m] (NULL = zero): s_{c,0} ^ prev_c, s_{c,t} ^ s_{c,t-1}, on bit 0 of each byte.  llr_out[i, t n + v] = the binary LLR of
+ * the totals (X, Y, Z) = marg[b,t,0..2,v] of fgnn_stbp4_decode_soft: softplus(-X) - lse2(-Z, -Y) for side 0, softplus(-Z) -
+ * lse2(-X, -Y) for side 1, the reliabilities fgnn_osd0 and fgnn_lsd form from BP4 marginals, by the same routines.  llr_out[i, R n +
+ * t m + c] = gam[b,t,c] unchanged (+inf is legal: that flip is the last column any solver takes).
+ * fgnn_st_window_apply: for a solution e [nact, R (n + m)] (uint8) in that column order, hat[b,t,v] = e[i, t n + v] and
+ * u_hat[b,t,c] = e[i, R n + t m + c] for b = index[i]: side 0 is handed z_hat and u_x_hat, side 1 x_hat and u_z_hat.  The rows of
+ * windows that are not listed are not touched.
+ * Plain loads and stores, every element written by one thread: no atomics, nothing depends on the launch geometry.  Refused with
+ * FGNN_ERR_ARG before any launch: a NULL graph, side outside 0..1, rounds < 1, nact < 0, R (n + m) beyond 31 bits, and, for nact > 0,
+ * a NULL marg, gam, d_out, llr_out, e, hat or u_hat.  nact = 0 needs no buffers. */
+int fgnn_st_window_problem(const fgnn_graph* g, int side, int rounds, const uint8_t* synd /* [B,R,m_side] or NULL */,
+                           const uint8_t* prev /* [B,m_side] or NULL */, const float* marg /* [B,R,3,n] */,
+                           const float* gam /* [B,R,m_side] */, const int32_t* index, int nact, uint8_t* d_out /* [nact,R m_side] */,
+                           float* llr_out /* [nact,R (n+m_side)] */, void* stream);
+int fgnn_st_window_apply(const fgnn_graph* g, int side, int rounds, const uint8_t* e /* [nact,R (n+m_side)] */, const int32_t* index,
+                         int nact, uint8_t* hat /* [B,R,n] */, uint8_t* u_hat /* [B,R,m_side] */, void* stream);
 /* Layers of the serial (layered) check schedule.  Checks are numbered 0..m_x-1 for hx and m_x..m_x+m_z-1 for hz; a layering is
  * layer_of[m_x+m_z] with values in [0, num_layers) such that every layer is non-empty and no two checks of a layer share a qubit —
  * across hx and hz too, since a qubit's update reads the messages of both sides.  All pointers are host pointers; fgnn_greedy_layers and
