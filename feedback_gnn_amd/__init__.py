@@ -43,6 +43,9 @@ def __getattr__(name):
     if name in ("BP4FeedbackDecoder", "BP4_Feedback_Model"):
         from . import prior_feedback as _pf
         return getattr(_pf, name)
+    if name in ("BP4AugmentedDecoder", "BP4_Augmented_Model"):
+        from . import augmentation as _au
+        return getattr(_au, name)
     if name in ("AMBP4Decoder", "BP4_AMBP_Model"):
         from . import mbp as _mb
         return getattr(_mb, name)

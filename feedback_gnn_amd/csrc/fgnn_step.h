@@ -1,15 +1,17 @@
-// fgnn_step.h — the frame of the step-loop BP4 decoders: bp4gd_kernel (fgnn_bp4gd.hip), bp4fb_kernel (fgnn_bp4fb.hip), mbp4_kernel
-// (fgnn_mbp4.hip), dsbp4_kernel (fgnn_dsbp4.hip), stbp4_kernel (fgnn_stbp4.hip) and relay4_kernel (fgnn_relay4.hip).
+// fgnn_step.h — the frame of the step-loop BP4 decoders: bp4gd_kernel (fgnn_bp4gd.hip), bp4fb_kernel (fgnn_bp4fb.hip), bp4aug_kernel
+// (fgnn_bp4aug.hip), mbp4_kernel (fgnn_mbp4.hip), dsbp4_kernel (fgnn_dsbp4.hip), stbp4_kernel (fgnn_stbp4.hip) and relay4_kernel
+// (fgnn_relay4.hip).
 //
-// The six kernels keep several codewords in the LDS of a workgroup and walk each through workgroup steps of one qubit phase, one
+// The seven kernels keep several codewords in the LDS of a workgroup and walk each through workgroup steps of one qubit phase, one
 // check phase and a control section.  What is the same in all of them has its one statement here:
 //   StepCw / StepRows / StepSynd   which codeword a thread works on, the codeword's input rows, its syndrome bits staged in a register
-//   QubitSlots<DV>                 a qubit's message slots: pre-clear, fetch with the sums Sz and Sx, store through the kernel's edge rule
+//   QubitSlots<DV>                 a qubit's message slots: pre-clear, fetch with the sums Sz and Sx (or, for bp4aug_kernel, the sums
+//                                  with duplicated checks), store through the kernel's edge rule
 //   row_unpack / parity_*          a check's packed row, and the parity of the decisions over a check's qubits
 //   step_write_decisions / step_finish   dec -> x_hat | z_hat, the four stats words and ndone
 // and on the host StepArgs (the head of every kernel's argument struct), the LDS arithmetic, the LDS refusal and the dispatch over
 // (check rule, regular 3-3-6).  Each kernel keeps its own step loop, barriers, LDS order, waves-per-SIMD value and whatever makes it
-// that decoder.  bp4gd_kernel and bp4fb_kernel have a control section each.  mbp4_kernel, dsbp4_kernel and stbp4_kernel share
+// that decoder.  bp4gd_kernel, bp4fb_kernel and bp4aug_kernel have a control section each.  mbp4_kernel, dsbp4_kernel and stbp4_kernel share
 // one, the attempt schedule of fgnn_attempts.h (AttemptSched, AttemptCtl, the step bound), and with it
 //   AttemptArgs, attempt_check_* / attempt_args_fill   the schedule in the argument struct, its argument checks and its fill
 //   attempt_stage                  tab, stamp and ndone staged into LDS behind the codewords
@@ -314,6 +316,30 @@ struct QubitSlots {
             }
         } else if (live) {
             vn_sums(msg, z0, z1, x0, x1, Sz, Sx);
+        }
+    }
+    // the fetch on the code with duplicated check rows (vn_sums_dup of fgnn_vn.h): a marked slot's message is added twice in a row.
+    // DV > 0: bit j of `bits` marks hx slot j, bit DV + j hz slot j; DV = 0: dup[e] marks slot e of msg.  With no mark set the sums
+    // are those of fetch(), bit for bit
+    __device__ __forceinline__ void fetch_dup(float& Sz, float& Sx, const unsigned bits, const uint8_t* dup)
+    {
+        if constexpr (REGULAR) {
+            Sz = 0.0f;
+            Sx = 0.0f;
+#pragma unroll
+            for (int j = 0; j < DV; ++j) {
+                mz[j] = pz[j];
+                Sz = Sz + mz[j];
+                if ((bits >> (DV + j)) & 1u) Sz = Sz + mz[j];
+            }
+#pragma unroll
+            for (int j = 0; j < DV; ++j) {
+                mx[j] = px[j];
+                Sx = Sx + mx[j];
+                if ((bits >> j) & 1u) Sx = Sx + mx[j];
+            }
+        } else {
+            vn_sums_dup(msg, dup, z0, z1, x0, x1, Sz, Sx);
         }
     }
     // the v->c messages from the totals X, Y, Z: edge(num, A, Y, mu) is the kernel's edge rule (vn_edge, vn_edge_own of fgnn_vn.h),

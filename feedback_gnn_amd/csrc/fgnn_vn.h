@@ -26,6 +26,23 @@ FG_FN void vn_sums(const float* msg, int z0, int z1, int x0, int x1, float& Sz, 
     for (int e = x0; e < x1; ++e) Sx = Sx + msg[e];
 }
 
+// the same sums on the code with some check rows written a second time, each copy directly after its original (augmented BP4,
+// fgnn_bp4aug.hip): in flooding BP from zero messages a copy's message equals its original's bit for bit, so slot e with dup[e] != 0
+// adds msg[e] twice in a row, the second a separate add.  dup is indexed as msg is.  With no mark set this is vn_sums
+FG_FN void vn_sums_dup(const float* msg, const uint8_t* dup, int z0, int z1, int x0, int x1, float& Sz, float& Sx)
+{
+    Sz = 0.0f;
+    Sx = 0.0f;
+    for (int e = z0; e < z1; ++e) {
+        Sz = Sz + msg[e];
+        if (dup[e]) Sz = Sz + msg[e];
+    }
+    for (int e = x0; e < x1; ++e) {
+        Sx = Sx + msg[e];
+        if (dup[e]) Sx = Sx + msg[e];
+    }
+}
+
 // totals (:244-248): hz messages carry X-or-Y evidence, hx messages Z-or-Y; Y = (Sz + Sx) + ly in this association
 FG_FN void vn_totals(float Sz, float Sx, float lx, float ly, float lz, float& X, float& Y, float& Z)
 {

@@ -912,6 +912,24 @@ class TannerGraph:
                                            _ptr(zh), _ptr(stats), _stream(self.device)))
         return xh, zh, stats
 
+    def bp4aug_decode(self, synd_x, synd_z, pre_iter, attempt_iter, max_attempts, density, cn_type="minsum", factor=1.0, restart=True,
+                      seed=0x5EED, first_sample=0, llr_ch=None, llr_const=0.0, B=None):
+        """Augmented BP4 on both graphs (`fgnn_bp4aug_decode`): up to `pre_iter` iterations, then up to `max_attempts` times every
+        check row is written a second time with probability `density` and BP4 runs up to `attempt_iter` iterations on that code, from
+        zero messages with `restart`, else from the messages it has.  The marks are drawn from the Philox stream of `seed` at the
+        global sample indices `first_sample` .. `first_sample + B - 1`; `llr_ch` [B, 3, n] or one `llr_const` for all three LLRs of
+        every qubit; a syndrome that is None is all-zero.  Returns `(x_hat [B,n] uint8, z_hat [B,n] uint8, stats [B,4] int32 = found,
+        draws made, iterations, k of the last test)`."""
+        cn = self._cn(cn_type)
+        B, synd_x, synd_z, llr_ch = self._quaternary_in(synd_x, synd_z, llr_ch, B)
+        if not 0 <= int(seed) < 1 << 64 or not 0 <= int(first_sample) < 1 << 64:
+            raise ValueError("seed and first_sample must fit 64 unsigned bits")
+        xh, zh, stats = self._new_xzs(B)
+        check(_lib.lib().fgnn_bp4aug_decode(self.handle, cn, float(factor), int(pre_iter), int(attempt_iter), int(max_attempts),
+                                            float(density), int(restart), int(seed), int(first_sample), _ptr(llr_ch), float(llr_const),
+                                            _ptr(synd_x), _ptr(synd_z), B, _ptr(xh), _ptr(zh), _ptr(stats), _stream(self.device)))
+        return xh, zh, stats
+
     def mbp4_decode(self, synd_x, synd_z, factors, owns, pre_iter, attempt_iter, cn_type="minsum", restart=True, llr_ch=None,
                     llr_const=0.0, B=None):
         """BP4 with message-strength control on both graphs (`fgnn_mbp4_decode`): attempt a (up to `pre_iter` iterations for a = 0,

@@ -397,6 +397,46 @@ int fgnn_bp4fb_decode(const fgnn_graph* g, int rule, int cn_type, float normaliz
                       int max_attempts, float strength, int restart, uint64_t seed, uint64_t first_sample, const float* llr_ch,
                       float llr_const, const uint8_t* synd_x, const uint8_t* synd_z, int B, uint8_t* x_hat, uint8_t* z_hat,
                       int32_t* stats, void* stream);
+/* Augmented BP4 (Rigby, Olivier, Jarvis, "Modified belief propagation decoders for quantum low-density parity-check codes", Phys. Rev.
+ * A 100, 012330, 2019): when BP4 has run its iterations without a solution, a random fraction of the check rows is written into the
+ * matrix a second time and BP4 runs again, with fresh draws until an estimate reproduces both syndromes.  llr_ch [B,3,n] (X, Y, Z) or
+ * NULL (= llr_const for all three), synd_x [B,m_x] / synd_z [B,m_z] (NULL = all-zero), all three cn_types and stats as
+ * fgnn_bp4fb_decode.  All arithmetic is float32 in the order written.  Checks are numbered 0..m_x-1 (hx) and m_x..m_x+m_z-1 (hz).  Per
+ * codeword b, with i = first_sample + b, lam the channel LLRs (never changed) and A = max_attempts:
+ *     dup_c = 0 for every check;  mu = 0 on every edge;  its = 0
+ *     for a in 0 .. A:                                   (a = number of draws made so far)
+ *         T = pre_iter if a == 0 else attempt_iter
+ *         if a > 0: dup_c = unit(w(c, a, 5)[0]) < density  for every check c      (float32 compare; w and unit as at fgnn_bp4fb_decode)
+ *         if restart and a > 0: mu = 0 on every edge
+ *         for k in 1 .. T:
+ *             Sz = 0.0f;  for the qubit's hz slots in ascending order: Sz = Sz + mu_e;  if dup of that slot's check: Sz = Sz + mu_e
+ *                                                                                          (a second, separate add)
+ *             Sx likewise over the hx slots;  X = Sz + lam^X;  Z = Sx + lam^Z;  Y = (Sz + Sx) + lam^Y
+ *             BP4 qubit update, literal form (one log-sum-exp per edge; options 1, 2, 3, 5 ignored), on these totals: the edge's own
+ *             message is taken out ONCE
+ *             check update cn_type on both graphs, * normalization_factor;   its += 1
+ *             marginals M^X, M^Z, M^Y from the new messages with the same duplicated sums
+ *             d_v = argmin(0, M^X, M^Z, M^Y), first minimum wins (BP4's rule);  x_v = d_v & 1;  z_v = d_v >> 1
+ *             if hz.x == synd_z and hx.z == synd_x:  found = 1;  stop
+ *         if a == A: stop                                (found = 0; the output is the pair of this last test)
+ * x_hat, z_hat [B,n] = the pair of the last test made; stats [B,4] (int32) = found, the a of that test, its, the k of that test.
+ * pre_iter and attempt_iter >= 1, 0 <= max_attempts <= 65535, density finite and in [0, 1], restart 0 or 1 (anything else:
+ * FGNN_ERR_ARG); B = 0 returns FGNN_OK and needs no buffers.
+ *   With max_attempts = 0 the result is that of fgnn_bp4gd_decode with max_rounds = 0, bit for bit: no mark is ever set, and S + mu is
+ * the only add.
+ *   With restart = 1, attempt a >= 1 is plain BP4 from zero messages on the code with every row of {c : dup_c} inserted once more
+ * directly after itself, its syndrome bit repeated: in flooding BP from zero messages a copy sees the inputs of its original in the same
+ * order, so its messages equal the original's bit for bit, and a qubit's ascending sum meets the two equal messages one after the other.
+ * With restart = 0 the messages of the attempt before are kept and the copies start from their originals' messages.
+ *   Rigby et al. draw a subset of fixed size.  The per-row Bernoulli draw here marks the same expected fraction of the rows, needs no
+ * shuffle and depends on no order: a check's mark is a function of (seed, i, a, c) alone, so every thread that needs it re-derives it.
+ * Stream 5 is apart from the channel noise (streams 0-2) and the feedback rules (3, 4) of the same seed.
+ *   The messages, decisions and marks of a codeword stay in LDS for the whole launch: a mark byte per qubit on (3,3,6)-regular graphs
+ * under min-sum (the per-codeword byte count of fgnn_bp4gd_decode), a mark byte per edge otherwise; a graph they do not fit is refused
+ * (FGNN_ERR_ARG), there is no global-memory variant. */
+int fgnn_bp4aug_decode(const fgnn_graph* g, int cn_type, float normalization_factor, int pre_iter, int attempt_iter, int max_attempts,
+                       float density, int restart, uint64_t seed, uint64_t first_sample, const float* llr_ch, float llr_const,
+                       const uint8_t* synd_x, const uint8_t* synd_z, int B, uint8_t* x_hat, uint8_t* z_hat, int32_t* stats, void* stream);
 /* BP4 with message-strength control (MBP4 / AMBP4; Kuo, Lai, "Exploiting degeneracy in belief propagation decoding of quantum codes",
  * npj Quantum Information, 2022), flooding schedule: a qubit's belief is formed from its incoming check messages scaled by 1 / alpha,
  * while the message it sends back to a check has that check's own contribution removed at full strength (the inhibition term); the
