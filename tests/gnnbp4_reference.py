@@ -49,9 +49,12 @@ def _scatter(vals, idx, size):
     return out.index_add(1, idx, vals)
 
 
-def forward(g, cfg, w, synd_x, synd_z, num_iter):
+def forward(g, cfg, w, synd_x, synd_z, num_iter, record=None):
     """cfg = (D, H, L, reduce_op 0 sum / 1 mean, activation 0..3, use_bias); w tensors of one dtype (requires_grad ok);
-    syndromes [B, m] 0/1.  Returns (x_logit_all, z_logit_all, llr): lists of [B, m_z + k] / [B, m_x + k] and the last [B, 3, n]."""
+    syndromes [B, m] 0/1.  Returns (x_logit_all, z_logit_all, llr): lists of [B, m_z + k] / [B, m_x + k] and the last [B, 3, n].
+    ``record``: a dict that receives, per iteration, what the library's tape keeps — "h_vn" [B, n, D] after the VN update, "h_cn"
+    [B, m_x + m_z, D] the VN update read, "hlog" [B, m_x + m_z] the hx then hz logits — and "llr_x" / "llr_z" [B, n], the binary
+    LLRs the soft syndromes are taken from."""
     D, H, L, rop, act, bias = [int(x) for x in cfg[:6]]
     if rop not in (0, 1):
         raise NotImplementedError("sum / mean only")
@@ -105,7 +108,11 @@ def forward(g, cfg, w, synd_x, synd_z, num_iter):
     hc = [torch.zeros((B, s["m"], D), dtype=dt, device=dev) for s in g.sides]
     hc = update_cn(h_vn, hc, [torch.zeros_like(sg[0]), torch.zeros_like(sg[1])])
     xs, zs = [], []
+    if record is not None:
+        record.update(h_vn=[], h_cn=[], hlog=[], llr_x=[], llr_z=[])
     for it in range(num_iter):
+        if record is not None:
+            record["h_cn"].append(torch.cat(hc, 1))
         h_vn = update_vn(hc, h_vn)
         Lv = h_vn @ Winv
         if binv is not None:
@@ -117,6 +124,11 @@ def forward(g, cfg, w, synd_x, synd_z, num_iter):
         hx_l, lx_l = rows_logit("hx", llr_z), rows_logit("lx", llr_z)
         xs.append(torch.cat([hz_l, lz_l], 1))
         zs.append(torch.cat([hx_l, lx_l], 1))
+        if record is not None:
+            record["h_vn"].append(h_vn)
+            record["hlog"].append(torch.cat([hx_l, hz_l], 1))
+            record["llr_x"].append(llr_x)
+            record["llr_z"].append(llr_z)
         if it == num_iter - 1:
             break
         hc = update_cn(h_vn, hc, [hx_l * sg[0], hz_l * sg[1]])
