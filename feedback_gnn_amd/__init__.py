@@ -37,7 +37,7 @@ def __getattr__(name):
     if name in ("RelayBPDecoder", "BP2_Relay_Model", "RelayBP4Decoder", "BP4_Relay_Model"):
         from . import relay as _r
         return getattr(_r, name)
-    if name in ("BP4GDDecoder", "BP4_GD_Model"):
+    if name in ("BP4GDDecoder", "BP4_GD_Model", "GDGDecoder", "BP2_GDG_Model"):
         from . import decimation as _dm
         return getattr(_dm, name)
     if name in ("BP4FeedbackDecoder", "BP4_Feedback_Model"):

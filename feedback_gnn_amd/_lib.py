@@ -12,6 +12,8 @@ CSRC = os.path.join(_HERE, "csrc")
 
 CN_TYPES = {"boxplus": 0, "boxplus-phi": 1, "minsum": 2}
 FB_RULES = {"perturb": 0, "enhanced": 1}
+GDG_TAILS = {"most": 0, "least": 1}
+GDG_MAX_DEPTH = 6
 ROWS_X_LOGIT, ROWS_Z_LOGIT, ROWS_HX_PERP, ROWS_HZ_PERP, ROWS_LX, ROWS_LZ = 0, 1, 2, 3, 4, 5
 
 
@@ -103,6 +105,10 @@ _SIGNATURES = {
                                   C.c_void_p, C.c_void_p]),
     "fgnn_relay_decode": (C.c_int, [C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float,
                                     C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fgnn_gdg_workspace_bytes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "fgnn_gdg_decode": (C.c_int, [C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_float,
+                                  C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                  C.c_void_p]),
     "fgnn_relay4_decode": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float,
                                      C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "fgnn_bp4gd_decode": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_float,

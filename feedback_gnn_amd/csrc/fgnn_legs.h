@@ -19,6 +19,8 @@
 // keeps its three for the reason given there; settle's one branch encloses the kernel's write, so that the three assignments and
 // the write stay one region.  In this form the control sections branch as they did before the two kernels shared them.
 // Host and device: tests/leg_ctl_check.cpp walks the control on the CPU.
+// gdg_kernel (fgnn_gdg.hip) runs the same control with a decimation round as a leg: max_rounds + 1 legs, stop_nconv = 1, and the pick
+// of the bit to fix where next_leg() is called.  It adds nothing here.
 #ifndef FGNN_LEGS_H
 #define FGNN_LEGS_H
 

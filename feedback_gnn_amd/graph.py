@@ -860,6 +860,51 @@ class TannerGraph:
                                            _stream(self.device)))
         return hard, stats
 
+    def gdg_workspace_bytes(self, depth, nact):
+        """Bytes of device workspace `fgnn_gdg_decode` needs for `nact` samples at `depth`."""
+        nbytes = C.c_size_t()
+        check(_lib.lib().fgnn_gdg_workspace_bytes(self.handle, int(depth), int(nact), C.byref(nbytes)))
+        return int(nbytes.value)
+
+    def gdg_decode(self, synd, pre_iter, round_iter, max_rounds, depth, tail="least", decim_llr=25.0, factor=0.8, llr_ch=None,
+                   llr_const=0.0, B=None, index=None, nact=None, want_path_stats=False, out=None):
+        """BP-GDG on the hx graph (`fgnn_gdg_decode`): min-sum BP with guided decimation guessing, 2**depth paths per sample.  `tail`
+        = "least" / "most": the bit the picks after the first `depth` take; `max_rounds` None = n.  `index` (int32 on the device) lists
+        the samples to decode, `nact` how many of its entries count (None: all); the rows of the other samples are those of `out` =
+        `(hard, stats)`, written in place, or zeros without it.  Returns `(hard [B,n] uint8, stats [B,4] int32 = paths that found a
+        solution, weight, path, bits fixed)`, and with `want_path_stats` `path_stats [nact, 2**depth, 4]` int32 = (found, weight, bits
+        fixed, iterations) per listed sample and path.  The workspace is allocated here, from `fgnn_gdg_workspace_bytes`."""
+        if tail not in _lib.GDG_TAILS:
+            raise ValueError('tail must be "least" or "most"')
+        B, synd, llr_ch = self._binary_in(synd, llr_ch, B)
+        if B is None:
+            raise ValueError("without a syndrome and llr_ch, B must be given")
+        max_rounds = self.n if max_rounds is None else int(max_rounds)
+        if index is not None:
+            index = self._opt_any(index, torch.int32, "index")
+            nact = int(index.numel()) if nact is None else int(nact)
+            if not 0 <= nact <= min(int(index.numel()), B):
+                raise ValueError("nact must be in 0 .. min(len(index), B)")
+        else:
+            nact = B
+        if out is not None:
+            hard = self._chk_out(out[0], (B, self.n), torch.uint8, "hard")
+            stats = self._chk_out(out[1], (B, 4), torch.int32, "stats")
+        elif index is not None:
+            hard, stats = self._new((B, self.n), torch.uint8).zero_(), self._new((B, 4), torch.int32).zero_()
+        else:
+            hard, stats = self._new((B, self.n), torch.uint8), self._new((B, 4), torch.int32)
+        ws_bytes = self.gdg_workspace_bytes(depth, nact)
+        ws = self._new((max(ws_bytes, 1),), torch.uint8)
+        path_stats = self._new((nact, 1 << int(depth), 4), torch.int32) if want_path_stats else None
+        if index is not None and index.numel() == 0:
+            index = self._new((1,), torch.int32)  # an empty list still is a list: a NULL pointer would mean all B samples
+        check(_lib.lib().fgnn_gdg_decode(self.handle, float(factor), int(pre_iter), int(round_iter), max_rounds, int(depth),
+                                         _lib.GDG_TAILS[tail], float(decim_llr), _ptr(llr_ch), float(llr_const), _ptr(synd), B,
+                                         _ptr(index), nact, _ptr(hard), _ptr(stats), _ptr(path_stats), _ptr(ws), ws_bytes,
+                                         _stream(self.device)))
+        return (hard, stats, path_stats) if want_path_stats else (hard, stats)
+
     def relay4_decode(self, synd_x, synd_z, gamma, pre_iter, leg_iter, stop_nconv, factor=1.0, llr_ch=None, llr_const=0.0,
                       cn_type="minsum", B=None):
         """Relay-BP4 on both graphs (`fgnn_relay4_decode`): `gamma` [num_legs, n] float32 on the device, one row of memory strengths per

@@ -350,6 +350,53 @@ int fgnn_relay4_decode(const fgnn_graph* g, int cn_type, float normalization_fac
 int fgnn_bp4gd_decode(const fgnn_graph* g, int cn_type, float normalization_factor, int pre_iter, int round_iter, int max_rounds,
                       float decim_llr, const float* llr_ch, float llr_const, const uint8_t* synd_x, const uint8_t* synd_z, int B,
                       uint8_t* x_hat, uint8_t* z_hat, int32_t* stats, void* stream);
+/* BP-GDG: binary min-sum BP with guided decimation guessing over a path tree (GDG; Gong, Cammerer, Renes, "Toward low-latency iterative
+ * decoding of QLDPC codes under circuit-level noise", 2024; with depth = 0 and FGNN_GDG_MOST the binary BPGD of Yao et al. 2023).  BP
+ * runs, a free bit is fixed ("decimated"), BP goes on from the messages it has; for the first `depth` fixes both values are tried, which
+ * makes P = 2^depth paths per sample, each path then continues greedily, and the lowest-weight solution among the paths is the output.
+ * One simplification against the paper: the bits are ranked by the posterior of the last test, not by a history of posteriors.
+ * The decoder works on side 0 (hx).  llr_ch [B,n] logits or NULL (= llr_const everywhere) and synd [B,m_x] or NULL (all-zero) exactly
+ * as fgnn_relay_decode, the +-20 clip and the sign flip included.  index (device int32 [nact]) selects the samples as in fgnn_osd0 /
+ * fgnn_lsd, NULL = all B (nact is then ignored); with a list 0 <= nact <= B and the ids must be distinct; samples that are not
+ * selected are left untouched in every output.  Min-sum is the only check rule.  All arithmetic is float32 in the order written; a
+ * bit's slot sums run in ascending order from 0.0f.  With D = decim_llr and R = min(max_rounds, n):
+ *     L_v = -1 * clamp(llr_v, -20, 20);  q_v = (int32) rint(1024 * L_v)
+ * Per selected sample and per path p in 0 .. P-1, independently of every other path:
+ *     fix_v = free for all v;  mu = 0 on every edge;  its = 0;  found = 0
+ *     Lhat_v = L_v while free;  +D once fixed to 0;  -D once fixed to 1
+ *     for r in 0 .. R:                                  (r = bits fixed so far)
+ *         T = pre_iter if r == 0 else round_iter
+ *         for k in 1 .. T:
+ *             S_v = sum of mu over the bit's edges;  x = S_v + Lhat_v;  nu_e = x - mu_e
+ *             mu = min-sum check update of nu (clip +-20, * normalization_factor), as fgnn_relay_decode;  its += 1
+ *             P_v = Lhat_v + (sum of the new mu);  d_v = (P_v < 0)
+ *             if H d == s:  found = 1;  w = sum_v d_v q_v;  stop this path
+ *         if r == R: stop this path                     (found = 0; d of this last test is the path's output)
+ *         least = (r < depth) or (tail_pick == FGNN_GDG_LEAST)
+ *         v* = the free bit of smallest |P_v| if least, else of largest |P_v|; lowest index on ties
+ *         val = (P_v* < 0);  if r < depth: val ^= (p >> r) & 1
+ *         fix v* to val.  The messages are kept.
+ * Per sample, after its paths: the output is the d of the path with found = 1 that has the smallest w, compared as signed int32, ties
+ * to the lowest p; if no path found a solution, the d of path 0.  hard_out [B,n] = that d; stats [B,4] (int32) = the number of paths
+ * that found a solution, the w of the output (0 when none found), the path of the output, the bits fixed on that path.  path_stats
+ * [nact,P,4] (int32) or NULL = per listed sample and path (found, w or 0, bits fixed, its).
+ * pre_iter, round_iter >= 1, max_rounds >= 0, 0 <= depth <= FGNN_GDG_MAX_DEPTH, tail_pick FGNN_GDG_MOST or FGNN_GDG_LEAST,
+ * decim_llr > 0: anything else returns FGNN_ERR_ARG before any write.  workspace: caller-owned device memory (4-byte aligned) of
+ * fgnn_gdg_workspace_bytes(g, depth, nact) bytes (nact = B without a list): nact * P * (16 + n), the four result words and the decision
+ * row of every path; a smaller ws_bytes returns FGNN_ERR_ARG and the message names the required size.  B = 0 or nact = 0 returns
+ * FGNN_OK and needs no buffers.  Nothing is allocated; both kernels (the paths, then the selection) run on `stream`.
+ * Identities: depth = 0 and max_rounds = 0 is fgnn_relay_decode with gamma = 0, one leg and stop_nconv = 1 (hard_out, found, and on a
+ * solution its weight and k = its, bit for bit); path p at depth d is a depth-0 run in which the first d picks are forced to p's bits.
+ * The pick is an integer extremum of a total order ((float bits of |P_v|) << 32 with the index below) and w is an integer: nothing
+ * depends on arrival order or launch geometry.  A path is a virtual codeword of its own: its messages, posteriors and fix marks stay in
+ * LDS for the whole launch; a graph whose per-path state does not fit is refused (FGNN_ERR_ARG), there is no global-memory variant. */
+enum { FGNN_GDG_MOST = 0, FGNN_GDG_LEAST = 1 };
+enum { FGNN_GDG_MAX_DEPTH = 6 };
+int fgnn_gdg_workspace_bytes(const fgnn_graph* g, int depth, int nact, size_t* bytes);
+int fgnn_gdg_decode(const fgnn_graph* g, float normalization_factor, int pre_iter, int round_iter, int max_rounds, int depth,
+                    int tail_pick, float decim_llr, const float* llr_ch, float llr_const, const uint8_t* synd, int B,
+                    const int32_t* index, int nact, uint8_t* hard_out, int32_t* stats, int32_t* path_stats, void* workspace,
+                    size_t ws_bytes, void* stream);
 /* BP4 with prior feedback: when BP4 has run its iterations without a solution, the unsatisfied checks of its last estimate choose
  * qubits whose channel LLRs are changed, and BP4 runs again: the hand-written rules the learned feedback of the GNN replaces.
  *   FGNN_FB_PERTURB    random perturbation (Poulin, Chung, "On the iterative decoding of sparse quantum codes", 2008)
