@@ -3,7 +3,7 @@
 // attempt_iter check updates with factor[r] and own[r], the hard decision is tested after every update and the first test that
 // passes ends the codeword; a restarting attempt starts from zero messages.  An attempt takes T + 1 workgroup steps, k = 0 .. T
 // counting its finished check updates: step k = 0 sends the first messages, step k > 0 tests the decision after k updates and, for
-// k < T, runs update k + 1.  Host and device (FG_FN), like fgnn_cn_soft.h: tests/attempt_ctl_check.cpp walks the control on the CPU
+// k < T, runs update k + 1.  Host and device (FG_FN), like fgnn_cn.h: tests/attempt_ctl_check.cpp walks the control on the CPU
 // against the step bound below.
 #ifndef FGNN_ATTEMPTS_H
 #define FGNN_ATTEMPTS_H

@@ -1,7 +1,7 @@
 // fgnn_dsbp4.hip — soft-syndrome BP4 (Kuo, Chern, Lai, "Decoding of quantum data-syndrome codes via belief propagation", 2021;
 // Raveendran et al., "Soft syndrome decoding of quantum LDPC codes for joint correction of data and syndrome errors", 2022), flooding
 // schedule, LDS-resident, with the attempt list of AMBP4 kept.  Check c carries a syndrome LLR gamma_c: the error u_c of its measured
-// bit is a degree-one variable on the check, so it is one more constant input of the check rule (fgnn_cn_soft.h), held in a register,
+// bit is a degree-one variable on the check, so it is one more constant input of the check rule (fgnn_cn.h, NX = 1), held in a register,
 // and the decoder returns u_hat next to the data error.  A sample is solved when H e_hat == s ^ u_hat on both graphs.  The algorithm is
 // stated to the float operation at fgnn_dsbp4_decode in include/fgnn.h.  The kernel stands on the frame of the step-loop decoders
 // (fgnn_step.h): staged syndrome bits, a qubit's slots, a check's row and parity (started from s ^ u_hat), the output write; its
@@ -35,14 +35,11 @@
 #include <cmath>
 
 #include "fgnn_step.h"
-#include "fgnn_cn_soft.h"
+#include "fgnn_cn.h"
 
 #ifndef FGNN_DSBP4_WAVES
 #define FGNN_DSBP4_WAVES 7  // waves per SIMD the register allocation aims at
 #endif
-
-static_assert(FGNN_SOFT_BOXPLUS == FGNN_CN_BOXPLUS && FGNN_SOFT_BOXPLUS_PHI == FGNN_CN_BOXPLUS_PHI && FGNN_SOFT_MINSUM == FGNN_CN_MINSUM,
-              "fgnn_cn_soft.h restates the FGNN_CN_* values of include/fgnn.h");
 
 namespace {
 
@@ -96,6 +93,13 @@ __device__ __forceinline__ float gamma_at(const float* gx0, const float* gz0, fl
     const float* gl = is_x ? gx0 : gz0;
     const unsigned o = is_x ? (unsigned)(cwl * m_x + c) : (unsigned)(cwl * m_z + (c - m_x));
     return gl ? gl[o] : (is_x ? gamma_x : gamma_z);
+}
+
+// u_hat of a check: Gamma = gamma + w is one add
+FG_FN unsigned soft_u_hat(float gamma, float w)
+{
+    const float G = gamma + w;
+    return G < 0.0f ? 1u : 0u;
 }
 
 // DV/DC > 0: (DV,DV,DC)-regular graphs with the packed slot rows of g.cslot16 (min-sum); DV = DC = 0: runtime degrees, the loop.
@@ -153,15 +157,22 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_
                 const unsigned ut = (unsigned)uh[c] & 1u;  // u_hat of the check update before this step: this lane wrote it
                 unsigned un = ut;
                 bool odd = false;
+                float x[1] = {gm};  // the extra input of the check rule; w_c on return
                 if constexpr (REGULAR) {
                     unsigned off[DC];
                     row_unpack(g, c, off);
                     if (k > 0) odd = parity_regular<DV>(g, dec, off, is_x, sy ^ ut) != 0u;
-                    if (k < T) un = soft_u_hat(gm, cn_soft_minsum_regular<DC>(msg, off, DC, sy, gm, fac));
+                    if (k < T) {
+                        cn_minsum_regular<DC, 1>(msg, off, DC, sy, fac, x);
+                        un = soft_u_hat(gm, x[0]);
+                    }
                 } else {
                     const int c0 = g.cptr[c], deg = g.cptr[c + 1] - c0;
                     if (k > 0) odd = parity_csr(g, dec, c0, deg, is_x, sy ^ ut) != 0u;
-                    if (k < T) un = soft_u_hat(gm, cn_soft_update<CN_TYPE, PhiSoft>(msg, g.cslot + c0, deg, sy, gm, fac));
+                    if (k < T) {
+                        cn_update<CN_TYPE, PhiBp4, 1>(msg, g.cslot + c0, deg, sy, fac, x);
+                        un = soft_u_hat(gm, x[0]);
+                    }
                 }
                 uh[c] = (uint8_t)(un | (ut << 1));
                 if (odd) w.stamp[cwl] = step;

@@ -6,7 +6,7 @@
 // at fgnn_stbp4_decode in include/fgnn.h.  The kernel is a sibling of dsbp4_kernel (fgnn_dsbp4.hip) on the frame of the step-loop
 // decoders (fgnn_step.h): the parity of a check's row, the stats words; its attempt walk, `tab` table and the qubit phase of a round's
 // qubit are the ones mbp4_kernel and dsbp4_kernel run (fgnn_attempts.h, fgnn_step.h).  Its own are the window, the time variables and
-// the check rule with one or two time-like inputs (fgnn_cn_st.h).  Instantiations and dispatch as dsbp4_kernel: the runtime-degree loop
+// the check rule with one or two time-like inputs (fgnn_cn.h, NX = 1 and 2).  Instantiations and dispatch as dsbp4_kernel: the runtime-degree loop
 // for each check rule, and min-sum on the packed rows of a (3,3,6)-regular graph, whose BYTE offsets are taken from the round's area.
 //
 // LDS of one window, in floats, each area rounded up to 4 floats:
@@ -45,14 +45,11 @@
 #include <cmath>
 
 #include "fgnn_step.h"
-#include "fgnn_cn_st.h"
+#include "fgnn_cn.h"
 
 #ifndef FGNN_STBP4_WAVES
 #define FGNN_STBP4_WAVES 6  // waves per SIMD the register allocation aims at
 #endif
-
-static_assert(FGNN_SOFT_BOXPLUS == FGNN_CN_BOXPLUS && FGNN_SOFT_BOXPLUS_PHI == FGNN_CN_BOXPLUS_PHI && FGNN_SOFT_MINSUM == FGNN_CN_MINSUM,
-              "fgnn_cn_soft.h restates the FGNN_CN_* values of include/fgnn.h");
 
 namespace {
 
@@ -278,11 +275,11 @@ stbp4_kernel(GraphDev g, std::conditional_t<SOFT, StSoftArgs, StArgs> a)
                     if (k < T) {
                         if (t == 0) {
                             float x[1] = {bsl[j]};
-                            cn_st_minsum_regular<DC, 1>(msg, off, DC, sy, x, fac);
+                            cn_minsum_regular<DC, 1>(msg, off, DC, sy, fac, x);
                             bsl[j] = x[0];
                         } else {
                             float x[2] = {asl[j - m], bsl[j]};
-                            cn_st_minsum_regular<DC, 2>(msg, off, DC, sy, x, fac);
+                            cn_minsum_regular<DC, 2>(msg, off, DC, sy, fac, x);
                             asl[j - m] = x[0];
                             bsl[j] = x[1];
                         }
@@ -293,11 +290,11 @@ stbp4_kernel(GraphDev g, std::conditional_t<SOFT, StSoftArgs, StArgs> a)
                     if (k < T) {
                         if (t == 0) {
                             float x[1] = {bsl[j]};
-                            cn_st_update<CN_TYPE, 1, PhiSoft>(msg, g.cslot + c0, deg, sy, x, fac);
+                            cn_update<CN_TYPE, PhiBp4, 1>(msg, g.cslot + c0, deg, sy, fac, x);
                             bsl[j] = x[0];
                         } else {
                             float x[2] = {asl[j - m], bsl[j]};
-                            cn_st_update<CN_TYPE, 2, PhiSoft>(msg, g.cslot + c0, deg, sy, x, fac);
+                            cn_update<CN_TYPE, PhiBp4, 2>(msg, g.cslot + c0, deg, sy, fac, x);
                             asl[j - m] = x[0];
                             bsl[j] = x[1];
                         }

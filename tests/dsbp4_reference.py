@@ -1,7 +1,7 @@
 """Soft-syndrome BP4 (fgnn_dsbp4_decode, include/fgnn.h) restated in NumPy float32.
 
 The qubit update, totals, decisions and attempt control are those of tests/mbp4_reference.py (`Graph`, `decisions`, `mbp4_tables`).
-The soft check rule is written out here per rule, every float operation in the order of feedback_gnn_amd/csrc/fgnn_cn_soft.h, on
+The soft check rule is written out here per rule, every float operation in the order of feedback_gnn_amd/csrc/fgnn_cn.h, on
 float32 arrays (NumPy rounds every elementwise float32 operation once and never fuses two of them) and on the oracle's
 transcendentals (`math_apply`): a check with d edges is the rule of that cn_type on the d + 1 inputs (nu_1, .., nu_d, gamma) in that
 order; outputs 1 .. d times the factor are the c->v messages, output d + 1 times the factor is w_c, Gamma_c = gamma_c + w_c is one add

@@ -2,7 +2,7 @@
 
 The qubit update, totals, decisions and attempt control are those of tests/mbp4_reference.py (`Graph`, `decisions`), walked as
 tests/dsbp4_reference.py walks them.  The check rule with one or two time-like inputs and the time variable rule are written out here
-per rule, every float operation in the order of feedback_gnn_amd/csrc/fgnn_cn_st.h, on float32 arrays and on the oracle's
+per rule, every float operation in the order of feedback_gnn_amd/csrc/fgnn_cn.h, on float32 arrays and on the oracle's
 transcendentals (`math_apply`): check (c,t) with d edges is the rule of that cn_type on the inputs (nu_1, .., nu_d, b) for t = 0 and
 (nu_1, .., nu_d, a, b) for t >= 1, in that order.  tests/test_stbp4_reference_cpu.py ties the rule to `mbp4_reference.cn_update` on
 [h | I | I], to `dsbp4_reference.soft_rule` with one extra input, to the host build of the header, and the decoder with R = 1 to

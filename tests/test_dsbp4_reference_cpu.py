@@ -1,6 +1,7 @@
 """Soft-syndrome BP4: the restatement tests/dsbp4_reference.py, tied to `mbp4_reference.cn_update` (itself tied to the C oracle) on
-the data-syndrome matrix [h | I], to the host build of the rules of fgnn_cn_soft.h, and to `mbp4_reference.mbp4_decode`; checked for
-what the algorithm at fgnn_dsbp4_decode (include/fgnn.h) states; and the build surface of the feature.  CPU only."""
+the data-syndrome matrix [h | I], to the host build of the rules of fgnn_cn.h with one extra input, and to
+`mbp4_reference.mbp4_decode`; checked for what the algorithm at fgnn_dsbp4_decode (include/fgnn.h) states; and the build surface of
+the feature.  CPU only."""
 import ctypes
 import functools
 import os
@@ -122,19 +123,39 @@ def rule_rows():
     return np.concatenate([np.stack(edge), rows])
 
 
-def build_and_run(flags, table):
-    src = os.path.join(ROOT, "tests", "cn_soft_check.cpp")
+_BUILD = tempfile.TemporaryDirectory()  # the builds of cn_rule_check.cpp, one per set of flags, shared by the tests that run it
+
+
+@functools.lru_cache(maxsize=None)
+def cn_rule_exe(flags):
+    src = os.path.join(ROOT, "tests", "cn_rule_check.cpp")
     inc = os.path.join(ROOT, "feedback_gnn_amd", "csrc")
-    with tempfile.TemporaryDirectory() as tmp:
-        exe = os.path.join(tmp, "cn_soft_check")
-        cc = subprocess.run(["g++", "-O2", "-ffp-contract=off", "-mfma", "-Wall", "-Wextra", "-Wno-unused-function"] + flags +
-                            ["-I" + inc, src, "-o", exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        assert cc.returncode == 0, cc.stdout
-        run = subprocess.run([exe], input=np.ascontiguousarray(table, dtype=F32).tobytes(), stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+    exe = os.path.join(_BUILD.name, "cn_rule_check" + "".join(re.sub(r"\W", "_", f) for f in flags))
+    cc = subprocess.run(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-mfma", "-Wall", "-Wextra", "-Wno-unused-function"] + list(flags) +
+                        ["-I" + inc, src, "-o", exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert cc.returncode == 0, cc.stdout
+    return exe
+
+
+def run_cn_rule_check(flags, table):
+    """[N, 5 * 14] words of tests/cn_rule_check.cpp, built with `flags`, on (deg, syndrome bit, number of extras, factor, extra 0,
+    extra 1, 12 inputs) rows."""
+    run = subprocess.run([cn_rule_exe(tuple(flags))], input=np.ascontiguousarray(table, dtype=F32).tobytes(), stdout=subprocess.PIPE,
+                         stderr=subprocess.STDOUT)
     assert run.returncode == 0, run.stdout
     lines = run.stdout.decode().split("\n")[:-1]
     assert len(lines) == len(table), run.stdout[-2000:]
     return np.array([[int(h, 16) for h in ln.split()] for ln in lines], np.uint32)
+
+
+def build_and_run(flags, table):
+    """The (deg, syndrome bit, gamma, factor, 12 inputs) rows as rows with one extra input, gamma; [N, 5 * 13] words: the 12 slots and
+    w of each group.  The word of the second extra input, which these rows do not have, is 0."""
+    one = np.zeros((len(table), 6 + DMAX), F32)
+    one[:, 0], one[:, 1], one[:, 2], one[:, 3], one[:, 4], one[:, 6:] = table[:, 0], table[:, 1], 1, table[:, 3], table[:, 2], table[:, 4:]
+    got = run_cn_rule_check(flags, one).reshape(len(table), 5, 14)
+    assert not got[:, :, 13].any()
+    return np.ascontiguousarray(got[:, :, :13]).reshape(len(table), 5 * 13)
 
 
 @functools.lru_cache(maxsize=None)
@@ -284,8 +305,9 @@ def test_header_declares_and_library_exports_dsbp4_decode():
     assert re.search(r"\bint\s+fgnn_dsbp4_decode\s*\(", text)
     assert "fgnn_dsbp4_decode" in _lib.ABI_SYMBOLS
     assert hasattr(ctypes.CDLL(_lib.LIB_PATH), "fgnn_dsbp4_decode")
-    soft = open(os.path.join(ROOT, "feedback_gnn_amd", "csrc", "fgnn_cn_soft.h")).read()
-    assert re.search(r"FG_FN\s+float\s+cn_soft_update\s*\(", soft) and re.search(r"FG_FN\s+float\s+cn_soft_minsum_regular\s*\(", soft)
+    # the rule the kernel calls is declared FG_FN, so it is host-callable: tests/cn_rule_check.cpp runs it
+    rule = open(os.path.join(ROOT, "feedback_gnn_amd", "csrc", "fgnn_cn.h")).read()
+    assert re.search(r"FG_FN\s+void\s+cn_update\s*\(", rule) and re.search(r"FG_FN\s+void\s+cn_minsum_regular\s*\(", rule)
 
 
 def test_public_classes_import():

@@ -1,7 +1,7 @@
 """Soft-syndrome BP4 on the GPU (fgnn_dsbp4_decode) at every dsbp4_kernel instantiation, held to the restatement
 tests/dsbp4_reference.py bit for bit: x_hat, z_hat, u_x_hat and u_z_hat as bytes, all four stats columns as int32, no tolerance
 anywhere and no sample left out.  The restatement is NumPy float32 on the oracle's transcendentals; tests/test_dsbp4_reference_cpu.py
-ties it to the oracle's check rules, to the host build of fgnn_cn_soft.h and to the AMBP4 restatement.
+ties it to the oracle's check rules, to the host build of fgnn_cn.h and to the AMBP4 restatement.
 
 The data noise is the library's seeded depolarizing stream at the rate per code of tests/test_gpu_bp4gd.py (P_OF); the syndromes carry
 flips of the seeded syndrome-noise streams at q = 0.05.  Where a test relies on an outcome occurring it asserts so on the

@@ -2,7 +2,7 @@
 min-sum on the packed rows of a (3,3,6)-regular graph), held to the restatement tests/stbp4_reference.py bit for bit: x_hat, z_hat, u_x_hat and u_z_hat as bytes, all four stats columns as
 int32, no tolerance anywhere and no window left out.  The restatement is NumPy float32 on the oracle's transcendentals;
 tests/test_stbp4_reference_cpu.py ties it to the soft-syndrome restatement, to the oracle's check rules and to the host build of
-fgnn_cn_st.h.
+fgnn_cn.h.
 
 The data noise is the library's seeded depolarizing stream, a fresh error before every round; the syndromes are those of the
 accumulated error with flips of the seeded syndrome-noise streams.  Where a test relies on an outcome occurring it asserts so on the

@@ -1,11 +1,9 @@
 """Space-time BP4: the restatement tests/stbp4_reference.py, tied to `dsbp4_reference.dsbp4_decode` at R = 1, to
 `mbp4_reference.cn_update` on [h | I | I], to `dsbp4_reference.soft_rule` with one extra input and to the host build of the rules of
-fgnn_cn_st.h; checked for what the algorithm at fgnn_stbp4_decode (include/fgnn.h) states (decoupling under perfect measurements, a
-known answer worked by hand); the window loop of the sliding model; and the Python layer in front of the library.  CPU only."""
+fgnn_cn.h with one and two extra inputs; checked for what the algorithm at fgnn_stbp4_decode (include/fgnn.h) states (decoupling under
+perfect measurements, a known answer worked by hand); the window loop of the sliding model; and the Python layer in front of the library.  CPU only."""
 import functools
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
@@ -17,7 +15,7 @@ import stbp4_reference as ST
 import test_python_frontend_cpu as FE
 from helpers import code, llr_const, oracle_library_forms
 from test_bp4fb_reference_cpu import depolarizing
-from test_dsbp4_reference_cpu import GAMMA_TABLE, bits, gamma_of_q, syndrome_noise
+from test_dsbp4_reference_cpu import GAMMA_TABLE, bits, gamma_of_q, run_cn_rule_check, syndrome_noise
 from test_python_frontend_cpu import lib_graph  # noqa: F401  (the recording library, a fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -145,21 +143,6 @@ def rule_rows():
     return np.concatenate([np.stack(edge), rows])
 
 
-def build_and_run(flags, table):
-    src = os.path.join(ROOT, "tests", "cn_st_check.cpp")
-    inc = os.path.join(ROOT, "feedback_gnn_amd", "csrc")
-    with tempfile.TemporaryDirectory() as tmp:
-        exe = os.path.join(tmp, "cn_st_check")
-        cc = subprocess.run(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-mfma", "-Wall", "-Wextra", "-Wno-unused-function"] + flags +
-                            ["-I" + inc, src, "-o", exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        assert cc.returncode == 0, cc.stdout
-        run = subprocess.run([exe], input=np.ascontiguousarray(table, dtype=F32).tobytes(), stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-    assert run.returncode == 0, run.stdout
-    lines = run.stdout.decode().split("\n")[:-1]
-    assert len(lines) == len(table), run.stdout[-2000:]
-    return np.array([[int(h, 16) for h in ln.split()] for ln in lines], np.uint32)
-
-
 @functools.lru_cache(maxsize=None)
 def rule_rows_reference():
     """{cn_type: [N, 14] bits} of the restatement on rule_rows(): the 12 slots, then the outputs for the extras (0 for a missing one)."""
@@ -184,7 +167,7 @@ def rule_rows_reference():
 @pytest.mark.parametrize("flags", [[], ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"]], ids=["plain", "sanitized"])
 def test_the_rules_of_the_header_equal_the_restatement_bitwise(flags):
     rows = rule_rows()
-    got = build_and_run(flags, rows)
+    got = run_cn_rule_check(flags, rows)
     assert got.shape == (len(rows), 5 * 14)
     want = rule_rows_reference()
     for g, cn in enumerate(CN_TYPES):  # the loop form
@@ -508,7 +491,8 @@ def test_the_build_surface():
     assert hasattr(ctypes.CDLL(_lib.LIB_PATH), "fgnn_stbp4_decode")
     assert callable(F.SpaceTimeBP4Decoder) and callable(F.BP4_Phenomenological_Model) and callable(TannerGraph.stbp4_decode)
     make = open(os.path.join(ROOT, "feedback_gnn_amd", "csrc", "Makefile")).read()
-    assert "fgnn_stbp4.hip" in make and "fgnn_cn_st.h" in make
+    assert "fgnn_stbp4.hip" in make and "fgnn_cn.h" in make.split("HDRS :=")[1].split("\n")[0].split(), "the header the kernel includes"
+    assert '#include "fgnn_cn.h"' in open(os.path.join(ROOT, "feedback_gnn_amd", "csrc", "fgnn_stbp4.hip")).read()
     # the byte formula: a five-round window of [[882,24]] fits the LDS budget, a six-round one does not
     budget = 160 * 1024 - 256
     E, nq, m = 2 * 2646, 882, 882
