@@ -140,6 +140,12 @@ _SIGNATURES = {
     "fgnn_graph_layers": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
     "fgnn_bp4_decode_layered": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p,
                                           C.c_int] + [C.c_void_p] * 10),
+    "fgnn_greedy_bit_layers": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
+    "fgnn_validate_bit_layers": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "fgnn_graph_set_bit_layers": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "fgnn_graph_bit_layers": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
+    "fgnn_bp2_decode_layered": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_int,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "fgnn_bsc_noise": (C.c_int, [C.c_uint64, C.c_float, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "fgnn_residual_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 4),
     "fgnn_graph_set_basis": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),

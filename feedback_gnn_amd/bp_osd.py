@@ -9,6 +9,7 @@ import torch
 
 from ._frontend import ShardedModel, bsc_logit, depolarizing_llr
 from ._lib import ROWS_LX, ROWS_LZ
+from .decoding import _bp2_stage
 from .feedback_gnn import Pauli
 
 _SEARCH = "osd_cs"  # fgnn_osd_resident of a search method asks whether fgnn_osd (the kernel every osd() call runs) takes the basis
@@ -229,9 +230,10 @@ class BP2_OSD_Model(ShardedModel):
     output, OSD-0 on the samples whose estimate misses the syndrome, ``ls_hat = logical_pcm·(noise xor estimate)``."""
 
     def __init__(self, pcm, pcm_basis, pivot_pcm, logical_pcm, bp2_decoder, osd_decoder, *, seed=0x5EED, rank=0, world_size=1):
-        from .decoding import _binary_graph
+        from .decoding import _adopt_bit_layers, _binary_graph
         self.pcm, self.logical_pcm, self.bp2_decoder, self.osd_decoder = pcm, logical_pcm, bp2_decoder, osd_decoder
         self.graph = _binary_graph(pcm, logical_pcm, bp2_decoder.graph.device)
+        _adopt_bit_layers(self.graph, bp2_decoder)
         self.graph.set_basis(0, pivot_pcm)
         self._shard(seed, rank, world_size)
         self.last_num_osd = 0
@@ -244,7 +246,7 @@ class BP2_OSD_Model(ShardedModel):
         noise = g.bsc_noise(self.seed, p, self._take(B), B)
         zeros = torch.zeros_like(noise)
         synd, _ = g.syndrome(zeros, noise)
-        soft, noise_hat = g.bp2_decode(synd, d._num_iter, d._cn_type, d._normalization_factor, llr_const=bsc_logit(p), B=B)  # (:216)
+        soft, noise_hat = _bp2_stage(g, d, synd, llr_const=bsc_logit(p), B=B)  # (:216)
         _, _, flags = g.residual(noise, zeros, noise_hat, zeros, want_arrays=False)
         index, nact = g.compact(flags, 1)
         self.last_num_osd = nact

@@ -250,6 +250,8 @@ extern "C" void fgnn_graph_destroy(fgnn_graph* g)
         if (p) (void)hipFree(p);
     for (void* p : g->layer_alloc)
         if (p) (void)hipFree(p);
+    for (void* p : g->bit_layer_alloc)
+        if (p) (void)hipFree(p);
     for (void* p : g->allocs) (void)hipFree(p);
     for (auto& r : g->row_alloc)
         for (void* p : r)
@@ -441,14 +443,17 @@ void greedy_layers(int n, int m, const std::vector<int>& ptr, const std::vector<
     *num_layers = L;
 }
 
-int validate_layers(int n, int m_x, int m, const std::vector<int>& ptr, const std::vector<int>& vn, int num_layers, const int32_t* layer_of)
+// bits: the layering of side 0 alone (fgnn_validate_bit_layers) — its checks are "check c" and what two of them share is a bit
+int validate_layers(int n, int m_x, int m, const std::vector<int>& ptr, const std::vector<int>& vn, int num_layers, const int32_t* layer_of,
+                    bool bits = false)
 {
+    const auto name = [&](int c) { return bits ? "check " + std::to_string(c) : check_name(c, m_x); };
     if (!layer_of) return fgnn_fail(FGNN_ERR_ARG, "layer_of is NULL");
     if (num_layers < 1) return fgnn_fail(FGNN_ERR_ARG, "num_layers = " + std::to_string(num_layers) + " must be >= 1");
     std::vector<int> count(num_layers, 0);
     for (int c = 0; c < m; ++c) {
         if (layer_of[c] < 0 || layer_of[c] >= num_layers)
-            return fgnn_fail(FGNN_ERR_ARG, check_name(c, m_x) + " has layer " + std::to_string(layer_of[c]) + ", outside [0, " +
+            return fgnn_fail(FGNN_ERR_ARG, name(c) + " has layer " + std::to_string(layer_of[c]) + ", outside [0, " +
                                                std::to_string(num_layers) + ")");
         count[layer_of[c]]++;
     }
@@ -463,8 +468,8 @@ int validate_layers(int n, int m_x, int m, const std::vector<int>& ptr, const st
         for (int c : at[v]) {
             const int l = layer_of[c];
             if (stamp[l] == v && owner[l] != c)
-                return fgnn_fail(FGNN_ERR_ARG, check_name(owner[l], m_x) + " and " + check_name(c, m_x) + " of layer " + std::to_string(l) +
-                                                   " share qubit " + std::to_string(v));
+                return fgnn_fail(FGNN_ERR_ARG, name(owner[l]) + " and " + name(c) + " of layer " + std::to_string(l) +
+                                                   (bits ? " share bit " : " share qubit ") + std::to_string(v));
             stamp[l] = v;
             owner[l] = c;
         }
@@ -593,6 +598,113 @@ int fgnn_graph_ensure_layers(const fgnn_graph* g)
     if (g->num_layers > 0) return FGNN_OK;
     if (g->host_only) return fgnn_fail(FGNN_ERR_STATE, "a host-only graph carries no device tables");
     return install_layers(g, 0, nullptr);
+}
+
+// ---- layers of side 0 alone, for the binary serial schedule (fgnn_bp2_decode_layered) ----------------------------------------------
+namespace {
+
+// the bits of every check of one matrix, in the order of the edge list
+int check_bits(int n, int m, int nnz, const int32_t* chk, const int32_t* var, std::vector<int>& ptr, std::vector<int>& vn)
+{
+    if (n <= 0 || m <= 0 || nnz < 0) return fgnn_fail(FGNN_ERR_ARG, "n and m must be positive");
+    if (nnz && (!chk || !var)) return fgnn_fail(FGNN_ERR_ARG, "edge list is NULL");
+    ptr.assign(m + 1, 0);
+    for (int i = 0; i < nnz; ++i) {
+        if (chk[i] < 0 || chk[i] >= m || var[i] < 0 || var[i] >= n) return fgnn_fail(FGNN_ERR_ARG, "edge index out of range");
+        ptr[chk[i] + 1]++;
+    }
+    for (int c = 0; c < m; ++c) ptr[c + 1] += ptr[c];
+    vn.resize(ptr[m]);
+    std::vector<int> fill(ptr.begin(), ptr.end() - 1);
+    for (int i = 0; i < nnz; ++i) vn[fill[chk[i]]++] = var[i];
+    return FGNN_OK;
+}
+
+// validates (a refused layering leaves the installed one in place), then replaces the two device tables
+int install_bit_layers(const fgnn_graph* g, int num_layers, const int32_t* layer_of)
+{
+    const GraphDev& d = g->d;
+    std::vector<int> ptr, vn;
+    int rc = check_bits(d.n, d.m_x, d.E_x, g->h_chk[0].data(), g->h_var[0].data(), ptr, vn);
+    if (rc) return rc;
+    std::vector<int32_t> lay(d.m_x);
+    if (!layer_of) {
+        greedy_layers(d.n, d.m_x, ptr, vn, lay.data(), &num_layers);
+    } else {
+        if ((rc = validate_layers(d.n, d.m_x, d.m_x, ptr, vn, num_layers, layer_of, true))) return rc;
+        std::copy(layer_of, layer_of + d.m_x, lay.begin());
+    }
+    std::vector<int> lcptr(num_layers + 1, 0), lchk(d.m_x);
+    for (int c = 0; c < d.m_x; ++c) lcptr[lay[c] + 1]++;
+    for (int l = 0; l < num_layers; ++l) lcptr[l + 1] += lcptr[l];
+    std::vector<int> fill(lcptr.begin(), lcptr.end() - 1);
+    for (int c = 0; c < d.m_x; ++c) lchk[fill[lay[c]]++] = c;
+    fgnn_device_guard dg(g->device);
+    if (dg.err != hipSuccess) return fgnn_fail(FGNN_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(dg.err));
+    const auto drop = [&] {
+        for (void*& p : g->bit_layer_alloc)
+            if (p) {
+                (void)hipFree(p);  // waits for the launches that read it
+                p = nullptr;
+            }
+        g->num_bit_layers = 0;
+        g->h_bit_layer_of.clear();
+    };
+    drop();
+    const std::vector<int>* tabs[2] = {&lcptr, &lchk};
+    for (int i = 0; i < 2; ++i) {
+        hipError_t e = hipMalloc(&g->bit_layer_alloc[i], tabs[i]->size() * sizeof(int));
+        if (e == hipSuccess) e = hipMemcpy(g->bit_layer_alloc[i], tabs[i]->data(), tabs[i]->size() * sizeof(int), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            drop();
+            return fgnn_fail(FGNN_ERR_HIP, std::string("uploading the bit-layer tables: ") + hipGetErrorString(e));
+        }
+    }
+    g->num_bit_layers = num_layers;
+    g->h_bit_layer_of = lay;
+    return FGNN_OK;
+}
+
+}  // namespace
+
+extern "C" int fgnn_greedy_bit_layers(int n, int m, int nnz, const int32_t* chk, const int32_t* var, int32_t* layer_of, int32_t* num_layers)
+{
+    if (!layer_of || !num_layers) return fgnn_fail(FGNN_ERR_ARG, "layer_of or num_layers is NULL");
+    std::vector<int> ptr, vn;
+    const int rc = check_bits(n, m, nnz, chk, var, ptr, vn);
+    if (rc) return rc;
+    greedy_layers(n, m, ptr, vn, layer_of, num_layers);
+    return FGNN_OK;
+}
+
+extern "C" int fgnn_validate_bit_layers(int n, int m, int nnz, const int32_t* chk, const int32_t* var, int num_layers, const int32_t* layer_of)
+{
+    std::vector<int> ptr, vn;
+    const int rc = check_bits(n, m, nnz, chk, var, ptr, vn);
+    if (rc) return rc;
+    return validate_layers(n, m, m, ptr, vn, num_layers, layer_of, true);
+}
+
+extern "C" int fgnn_graph_set_bit_layers(fgnn_graph* g, int num_layers, const int32_t* layer_of)
+{
+    if (!g) return fgnn_fail(FGNN_ERR_ARG, "graph is NULL");
+    if (g->host_only) return fgnn_fail(FGNN_ERR_STATE, "a host-only graph carries no device tables");
+    return install_bit_layers(g, num_layers, layer_of);
+}
+
+extern "C" int fgnn_graph_bit_layers(const fgnn_graph* g, int32_t* num_layers, int32_t* layer_of)
+{
+    if (!g || !num_layers) return fgnn_fail(FGNN_ERR_ARG, "NULL argument");
+    *num_layers = g->num_bit_layers;
+    if (layer_of) std::copy(g->h_bit_layer_of.begin(), g->h_bit_layer_of.end(), layer_of);
+    return FGNN_OK;
+}
+
+int fgnn_graph_ensure_bit_layers(const fgnn_graph* g)
+{
+    if (g->num_bit_layers > 0) return FGNN_OK;
+    if (g->host_only) return fgnn_fail(FGNN_ERR_STATE, "a host-only graph carries no device tables");
+    return install_bit_layers(g, 0, nullptr);
 }
 
 // Per-launch timing of the BP4 kernel: HIP events recorded on the launch stream immediately before and

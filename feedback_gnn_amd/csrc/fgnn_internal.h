@@ -65,6 +65,12 @@ struct fgnn_graph {
     mutable int num_layers = 0;
     mutable std::vector<int32_t> h_layer_of;
     mutable void* layer_alloc[4] = {nullptr, nullptr, nullptr, nullptr};  // lay_cptr, lay_chk, lay_eptr, lay_edge
+    // layering of side 0 (hx) alone for the binary serial schedule (fgnn_graph_set_bit_layers; fgnn_bp2_decode_layered installs the
+    // greedy one on a graph without), kept next to the one above and independent of it: layer_of per hx check on the host; on the
+    // device the checks of layer l = lay_chk[lay_cptr[l] .. lay_cptr[l+1]) ascending
+    mutable int num_bit_layers = 0;
+    mutable std::vector<int32_t> h_bit_layer_of;
+    mutable void* bit_layer_alloc[2] = {nullptr, nullptr};  // lay_cptr, lay_chk
     // optional per-launch timing of the BP4 kernel with HIP events on the launch stream (fgnn_profile_*)
     mutable bool prof_on = false;
     mutable int prof_n = 0;
@@ -235,6 +241,8 @@ LaunchGeom fgnn_geom(const fgnn_graph* g, int B);
 
 // the greedy layering on a graph that has none (fgnn_bp4_decode_layered takes a const handle: the layer tables are mutable members)
 int fgnn_graph_ensure_layers(const fgnn_graph* g);
+// the same for the layering of side 0 alone (fgnn_bp2_decode_layered)
+int fgnn_graph_ensure_bit_layers(const fgnn_graph* g);
 
 // internal entry points with an optional slot->sample indirection (compacted sandwich rounds); bp4: flagged[b] (optional) = the
 // decision's syndrome differs from the measured one — the sandwich's flag test fused into the decoder's epilogue; llr_bound = what

@@ -20,8 +20,8 @@
 // whose LDS words leg_stage lays out here.
 // Every float operation stays where it was: the sums run hz before hx, each ascending from 0.
 //
-// The binary decoders on side 0 (hx), bp2_kernel (fgnn_bp2.hip), relay_kernel and gdg_kernel (fgnn_gdg.hip, whose codewords are the
-// paths of its samples), take StepCw (from B, tpc, cpb: their argument
+// The binary decoders on side 0 (hx), bp2_kernel (fgnn_bp2.hip), bp2_layered_kernel (fgnn_bp2_layered.hip), relay_kernel and gdg_kernel
+// (fgnn_gdg.hip, whose codewords are the paths of its samples), take StepCw (from B, tpc, cpb: their argument
 // structs are their own), StepSynd (over the m_x checks of hx) and row_unpack from the frame, and have their own part at the end:
 //   BitRows                        the llr_ch / output row and the syndrome row of a codeword, synd_of, the prior
 //   BitSlots<DV>                   a bit's message slots: fetch with the ascending sum (or zeros), store x - m_j; QubitSlots' binary sibling

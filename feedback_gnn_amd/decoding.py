@@ -23,21 +23,48 @@ def _binary_graph(pcm, logical_pcm, device):
     return TannerGraph(code, stage_one=True, device=device)
 
 
+def _adopt_bit_layers(graph, decoder):
+    """A binary model decodes on its own graph: under a layered decoder that graph takes the layering of the decoder's graph.  A
+    flooding decoder makes no call."""
+    if getattr(decoder, "schedule", "flooding") == "layered":
+        graph.set_bit_layers(decoder.graph.bit_layers()[1])  # None (no layering yet): the greedy one
+
+
+def _bp2_stage(graph, decoder, synd, **kw):
+    """The BP stage of the binary models on ``graph`` with the decoder's settings and schedule: `bp2_decode`, or under a layered decoder
+    `bp2_decode_layered` with its ``stop_early``.  Returns ``(soft, hard)``."""
+    d = decoder
+    if getattr(d, "schedule", "flooding") == "layered":
+        return graph.bp2_decode_layered(synd, d._num_iter, d._cn_type, d._normalization_factor, stop=d.stop_early, **kw)
+    return graph.bp2_decode(synd, d._num_iter, d._cn_type, d._normalization_factor, **kw)
+
+
 class LDPCBPDecoder:
-    """Flooding BP on one parity-check matrix with syndrome input.
+    """BP on one parity-check matrix with syndrome input, in the flooding schedule or the layered one.
 
     ``LDPCBPDecoder(pcm, trainable=False, cn_type='boxplus-phi', hard_out=True, track_exit=False, num_iter=32,
     normalization_factor=1.0, stateful=False, is_syndrome=False, output_dtype=torch.float32)`` (decoding.py:260-270).
     Call ``decoder((llr_ch[bs,n], syndrome[m,bs]))`` if ``is_syndrome`` else ``decoder(llr_ch)``; ``llr_ch`` are logits
     (log p(1)/p(0)); returns hard decisions (0/1 floats) or soft logits ``[bs,n]``.  Trainable weights, EXIT tracking and the
-    stateful mode of upstream Sionna are outside the QLDPC path and raise NotImplementedError.
+    stateful mode of upstream Sionna are outside the QLDPC path and raise NotImplementedError.  Extra keywords: ``schedule``
+    ('flooding', the reference's; 'layered' updates the checks layer by layer on running posteriors, each seeing the results of the
+    layers before it), ``layers`` (a layering for `TannerGraph.set_bit_layers`; default: the graph's own, else the greedy one) and
+    ``stop_early`` (layered only: a sample leaves after the first iteration whose decision reproduces its syndrome); ``device``;
+    ``graph`` (share another decoder's TannerGraph).
     """
 
     def __init__(self, pcm, trainable=False, cn_type='boxplus-phi', hard_out=True, track_exit=False, num_iter=32,
                  normalization_factor=1.0, stateful=False, is_syndrome=False, output_dtype=torch.float32, device=None, graph=None,
-                 **kwargs):
+                 schedule="flooding", layers=None, stop_early=False, **kwargs):
         if cn_type not in CN_TYPES:
             raise ValueError('Unknown node type.')
+        if schedule not in ("flooding", "layered"):
+            raise ValueError(f"schedule must be 'flooding' or 'layered', got {schedule!r}")
+        if layers is not None and schedule != "layered":
+            raise ValueError("layers= belongs to schedule='layered'")
+        if stop_early and schedule != "layered":
+            raise ValueError("stop_early=True belongs to schedule='layered'")
+        self._schedule, self._stop_early = schedule, bool(stop_early)
         if trainable or track_exit or stateful:
             raise NotImplementedError("trainable / track_exit / stateful are not part of the syndrome-decoding path")
         if not isinstance(num_iter, (int, np.integer)) or num_iter < 0:
@@ -48,6 +75,8 @@ class LDPCBPDecoder:
         self._cn_type, self._hard_out, self._num_iter = cn_type, bool(hard_out), int(num_iter)
         self._normalization_factor, self._is_syndrome, self._output_dtype = float(normalization_factor), bool(is_syndrome), output_dtype
         self.graph = graph if graph is not None else _binary_graph(pcm, None, device)
+        if schedule == "layered" and (layers is not None or self.graph.bit_layers()[0] == 0):
+            self.graph.set_bit_layers(layers)  # None: the greedy layering; a shared graph keeps the layering it already has
         self._num_vns, self._num_cns = self.graph.n, self.graph.m_x
         self._pcm = pcm
 
@@ -59,6 +88,15 @@ class LDPCBPDecoder:
     has_weights = property(lambda self: False)     # trainable=True is refused by the constructor
     output_dtype = property(lambda self: self._output_dtype)
     llr_max = property(lambda self: 20.0)          # the input clip of decoding.py:918-920, fixed in the kernel (fgnn_bp2_decode)
+
+    @property
+    def schedule(self):
+        """'flooding' (all bits, then all checks: fgnn_bp2_decode) or 'layered' (the checks layer by layer: fgnn_bp2_decode_layered)."""
+        return self._schedule
+
+    @property
+    def stop_early(self):
+        return self._stop_early
 
     @property
     def num_iter(self):
@@ -103,8 +141,7 @@ class LDPCBPDecoder:
             raise ValueError('Last dimension must be of length n.')
         shape = llr_ch.shape
         flat = llr_ch.reshape(-1, self._num_vns).to(torch.float32).contiguous()
-        soft, hard = g.bp2_decode(synd, self._num_iter, self._cn_type, self._normalization_factor, llr_ch=flat,
-                                  want_soft=not self._hard_out, want_hard=self._hard_out)
+        soft, hard = _bp2_stage(g, self, synd, llr_ch=flat, want_soft=not self._hard_out, want_hard=self._hard_out)
         out = hard.to(self._output_dtype) if self._hard_out else soft.to(self._output_dtype)
         return out.reshape(shape)
 
@@ -120,6 +157,7 @@ class BP_BSC_Model(ShardedModel):
         self.pcm, self.logical_pcm, self.decoder, self.p0 = pcm, logical_pcm, decoder, p0
         self.n = np.asarray(pcm).shape[1]
         self.graph = _binary_graph(pcm, logical_pcm, decoder.graph.device)
+        _adopt_bit_layers(self.graph, decoder)
         self._shard(seed, rank, world_size)
 
     def __call__(self, batch_size, ebno_db=None, **kw):
@@ -130,9 +168,7 @@ class BP_BSC_Model(ShardedModel):
         noise = g.bsc_noise(self.seed, p, self._take(B), B)
         zeros = torch.zeros_like(noise)
         synd, _ = g.syndrome(zeros, noise)  # syndrome_x = hx * noise_z with hx = pcm (:216-217)
-        d = self.decoder
-        _, noise_hat = g.bp2_decode(synd, d._num_iter, d._cn_type, d._normalization_factor, llr_const=llr_const, B=B,
-                                    want_soft=False)
+        _, noise_hat = _bp2_stage(g, self.decoder, synd, llr_const=llr_const, B=B, want_soft=False)
         if self.logical_pcm is None:
             return noise.to(torch.float32), noise_hat.to(torch.float32)
         # s_hat = pcm (noise xor noise_hat), ls_hat = logical_pcm (noise xor noise_hat) (:222-229): the x-halves of the

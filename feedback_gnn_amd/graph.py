@@ -848,6 +848,46 @@ class TannerGraph:
                                          _ptr(synd), B, _ptr(soft), _ptr(hard), _stream(self.device)))
         return soft, hard
 
+    # ---- layered (serial) schedule of binary BP ------------------------------------------------------------------
+    def set_bit_layers(self, layer_of=None):
+        """Install the layering of `bp2_decode_layered` (fgnn_graph_set_bit_layers): ``layer_of`` [m_x] gives every hx check its layer
+        0 .. max; None installs the greedy layering.  No layer may be empty and no two checks of a layer may share a bit: a ValueError
+        names the offender, and the installed layering stays.  Independent of `set_layers`."""
+        if layer_of is None:
+            check(_lib.lib().fgnn_graph_set_bit_layers(self.handle, 0, None))
+            return
+        lay = np.ascontiguousarray(layer_of, dtype=np.int32)
+        if lay.shape != (self.m_x,):
+            raise ValueError(f"layer_of must have shape ({self.m_x},), got {lay.shape}")
+        check(_lib.lib().fgnn_graph_set_bit_layers(self.handle, int(lay.max()) + 1, _np_ptr(lay)))
+
+    def bit_layers(self):
+        """(num_layers, layer_of [m_x] int32) of the installed bit layering; (0, None) when there is none yet."""
+        num = C.c_int32(0)
+        check(_lib.lib().fgnn_graph_bit_layers(self.handle, C.byref(num), None))
+        if num.value == 0:
+            return 0, None
+        lay = np.empty(self.m_x, np.int32)
+        check(_lib.lib().fgnn_graph_bit_layers(self.handle, C.byref(num), _np_ptr(lay)))
+        return int(num.value), lay
+
+    def bp2_decode_layered(self, synd, num_iter, cn_type="boxplus-phi", factor=1.0, llr_ch=None, llr_const=0.0, B=None, want_soft=True,
+                           want_hard=True, stop=False, want_stats=False):
+        """`bp2_decode` in the layered (serial) schedule (fgnn_bp2_decode_layered): the hx checks are updated layer by layer on running
+        posteriors, every update sees the results of the layers before it.  ``stop``: a sample leaves after the first iteration whose
+        decision reproduces its syndrome.  Returns `(soft, hard)`, or with ``want_stats`` `(soft, hard, stats)`, stats int32 [B,2] =
+        (the decision reproduces the syndrome, iterations run).  A graph without a bit layering gets the greedy one
+        (`set_bit_layers`)."""
+        cn = self._cn(cn_type)
+        B, synd, llr_ch = self._binary_in(synd, llr_ch, B)
+        soft = self._new((B, self.n), torch.float32) if want_soft else None
+        hard = self._new((B, self.n), torch.uint8) if want_hard else None
+        stats = self._new((B, 2), torch.int32) if want_stats else None
+        check(_lib.lib().fgnn_bp2_decode_layered(self.handle, cn, int(num_iter), float(factor), _ptr(llr_ch), float(llr_const),
+                                                 _ptr(synd), B, int(bool(stop)), _ptr(soft), _ptr(hard), _ptr(stats),
+                                                 _stream(self.device)))
+        return (soft, hard, stats) if want_stats else (soft, hard)
+
     def relay_decode(self, synd, gamma, pre_iter, leg_iter, stop_nconv, factor=1.0, llr_ch=None, llr_const=0.0, B=None):
         """Relay-BP on the hx graph (`fgnn_relay_decode`): `gamma` [num_legs, n] float32 on the device, one row of memory strengths per
         leg.  Returns `(hard [B,n] uint8, stats [B,4] int32 = found, weight, leg, k)`."""

@@ -7,6 +7,7 @@ import torch
 
 from ._frontend import ShardedModel, bsc_logit, depolarizing_llr
 from ._lib import ROWS_LX, ROWS_LZ
+from .decoding import _bp2_stage
 from .bp_osd import _OsdWorkspace, _run_osd0, _StandaloneOSD
 from .feedback_gnn import Pauli
 
@@ -113,9 +114,10 @@ class BP2_LSD_Model(ShardedModel):
     fallback's OSD-0 runs on all rows of ``pcm``, which may be dependent)."""
 
     def __init__(self, pcm, logical_pcm, bp2_decoder, lsd_decoder, *, seed=0x5EED, rank=0, world_size=1):
-        from .decoding import _binary_graph
+        from .decoding import _adopt_bit_layers, _binary_graph
         self.pcm, self.logical_pcm, self.bp2_decoder, self.lsd_decoder = pcm, logical_pcm, bp2_decoder, lsd_decoder
         self.graph = _binary_graph(pcm, logical_pcm, bp2_decoder.graph.device)
+        _adopt_bit_layers(self.graph, bp2_decoder)
         if lsd_decoder.fallback == "osd0":
             self.graph.set_basis(0, np.arange(self.graph.m_x, dtype=np.int32))
         self._shard(seed, rank, world_size)
@@ -129,7 +131,7 @@ class BP2_LSD_Model(ShardedModel):
         noise = g.bsc_noise(self.seed, p, self._take(B), B)
         zeros = torch.zeros_like(noise)
         synd, _ = g.syndrome(zeros, noise)
-        soft, noise_hat = g.bp2_decode(synd, d._num_iter, d._cn_type, d._normalization_factor, llr_const=bsc_logit(p), B=B)
+        soft, noise_hat = _bp2_stage(g, d, synd, llr_const=bsc_logit(p), B=B)
         _, _, flags = g.residual(noise, zeros, noise_hat, zeros, want_arrays=False)
         index, nact = g.compact(flags, 1)
         self.last_num_lsd, self.last_num_fallback = nact, 0

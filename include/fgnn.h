@@ -702,6 +702,47 @@ int fgnn_bp4_decode_layered(const fgnn_graph* g, int cn_type, int num_iter, floa
                             float llr_const, const uint8_t* synd_x, const uint8_t* synd_z, int B, const float* msg_init_x,
                             const float* msg_init_z, float* llr_out, uint8_t* x_hat, uint8_t* z_hat, float* x_logit,
                             float* z_logit, float* msg_out_x, float* msg_out_z, void* stream);
+/* Layers of side 0 (hx) alone, for the serial schedule of the binary decoder (fgnn_bp2_decode_layered).  The rules are those of
+ * fgnn_greedy_layers / fgnn_validate_layers restricted to the hx checks: layer_of[m] (m = m_x) with values in [0, num_layers), no layer
+ * empty, no two checks of a layer sharing a bit.  chk / var [nnz] are the edges of the one matrix; all pointers are host pointers;
+ * fgnn_greedy_bit_layers and fgnn_validate_bit_layers touch no device.
+ * fgnn_greedy_bit_layers: checks in ascending number, each into the lowest-numbered layer that holds no check sharing a bit with it.
+ * fgnn_validate_bit_layers: FGNN_OK, or FGNN_ERR_ARG with a message naming the check whose layer is out of range ("check 3 has layer
+ * 9, outside [0, 4)"), the empty layer ("layer 2 is empty"), or the two checks of one layer and the bit they share ("check 0 and check
+ * 5 of layer 1 share bit 7").
+ * fgnn_graph_set_bit_layers: layer_of = NULL installs the greedy layering (num_layers is ignored); a caller's layering is validated as
+ * above and uploaded as a list of checks per layer, ascending inside a layer; a refused layering leaves the installed one in place.
+ * fgnn_graph_bit_layers: the installed layering (*num_layers = 0 and layer_of untouched when there is none; layer_of may be NULL).
+ * This layering is kept next to the one of fgnn_graph_set_layers and is independent of it: installing one never changes the other,
+ * and neither changes any flooding decoder. */
+int fgnn_greedy_bit_layers(int n, int m, int nnz, const int32_t* chk, const int32_t* var, int32_t* layer_of, int32_t* num_layers);
+int fgnn_validate_bit_layers(int n, int m, int nnz, const int32_t* chk, const int32_t* var, int num_layers, const int32_t* layer_of);
+int fgnn_graph_set_bit_layers(fgnn_graph* g, int num_layers, const int32_t* layer_of);
+int fgnn_graph_bit_layers(const fgnn_graph* g, int32_t* num_layers, int32_t* layer_of);
+/* Binary syndrome BP in the layered (serial) schedule: the checks of side 0 (hx) are updated one layer at a time and every update sees
+ * the results of the layers before it.  Inputs as fgnn_bp2_decode: llr_ch [B,n] logits or NULL (= llr_const), synd [B,m_x] or NULL
+ * (all-zero), all three cn_types, soft_out / hard_out [B,n] (one of them may be NULL).  A graph without a bit layering gets the greedy
+ * one (fgnn_graph_set_bit_layers(g, 0, NULL)).  All arithmetic is float32 in the order written.  Per codeword:
+ *     L_v = -1 * clamp(llr_v, -20, 20);   P_v = L_v + 0.0f;   mu_e = 0 on every edge;   it_run = 0
+ *     for it in 1 .. num_iter:
+ *         for l in 0 .. num_layers-1:
+ *             for every check c of layer l (any order: they share no bit):
+ *                 nu_e  = P_v - mu_e                          on c's edges e = (c, v)
+ *                 mu_e  = check update cn_type of (nu_e)_e with c's syndrome bit, * normalization_factor
+ *                         (the rules of fgnn_bp2_decode unchanged: min-sum clips nu to +-20 inside the rule)
+ *                 P_v   = nu_e + mu_e                         (the new mu_e)
+ *         it_run = it
+ *         if stop and H d == s with d_v = (P_v < 0): leave the loop
+ *     soft_out_v = -1 * P_v;   hard_out_v = (0 < soft_out_v);   stats = (H hard_out == s, it_run)
+ * So num_iter = 0 returns the bytes of fgnn_bp2_decode with num_iter = 0.  stats [B,2] (int32) or NULL is written whenever it is given,
+ * with stop set or not; with stop = 0 the parity test runs once, after the last iteration.  stop is 0 or 1.
+ * One codeword's E_x messages and n posteriors stay in LDS for the whole launch, each area rounded up to 4 floats; a launch with stop
+ * or stats keeps one more word per codeword of the workgroup.  A graph that does not fit is refused (FGNN_ERR_ARG, the message gives
+ * the bytes needed and the limit); there is no global-memory variant.  Without fgnn_graph_set_launch a codeword gets at most 128 threads
+ * (one thread takes a check of the layer, and a layer holds a fraction of the checks).  B = 0: FGNN_OK. */
+int fgnn_bp2_decode_layered(const fgnn_graph* g, int cn_type, int num_iter, float normalization_factor, const float* llr_ch,
+                            float llr_const, const uint8_t* synd, int B, int stop, float* soft_out, uint8_t* hard_out,
+                            int32_t* stats /* [B,2] or NULL */, void* stream);
 /* BinarySymmetricChannel on the all-zero word, BP_BSC_Model.call feedback_gnn.py:213-214: noise = u < p (Philox stream). */
 int fgnn_bsc_noise(uint64_t seed, float p, uint64_t first_sample, int B, int n, uint8_t* noise, void* stream);
 
