@@ -40,6 +40,9 @@ def __getattr__(name):
     if name in ("BP4GDDecoder", "BP4_GD_Model", "GDGDecoder", "BP2_GDG_Model"):
         from . import decimation as _dm
         return getattr(_dm, name)
+    if name in ("SIDecoder", "BP2_SI_Model", "BP4_SI_Model"):
+        from . import inactivation as _si
+        return getattr(_si, name)
     if name in ("BP4FeedbackDecoder", "BP4_Feedback_Model"):
         from . import prior_feedback as _pf
         return getattr(_pf, name)

@@ -252,6 +252,8 @@ extern "C" void fgnn_graph_destroy(fgnn_graph* g)
         if (p) (void)hipFree(p);
     for (void* p : g->bit_layer_alloc)
         if (p) (void)hipFree(p);
+    for (void* p : g->si_alloc)
+        if (p) (void)hipFree(p);
     for (void* p : g->allocs) (void)hipFree(p);
     for (auto& r : g->row_alloc)
         for (void* p : r)

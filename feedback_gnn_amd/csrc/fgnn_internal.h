@@ -71,6 +71,14 @@ struct fgnn_graph {
     mutable int num_bit_layers = 0;
     mutable std::vector<int32_t> h_bit_layer_of;
     mutable void* bit_layer_alloc[2] = {nullptr, nullptr};  // lay_cptr, lay_chk
+    // solve tables of stabilizer inactivation (fgnn_si_decode builds them on its first call and keeps them): per group j = hz row j
+    // the adjacent hx checks adj[aptr[j] .. aptr[j+1]), one 64-bit mask over them per bit of the group (xmask, in the order of the
+    // hz edges of cvn) and one per consistency row cons[kptr[j] .. kptr[j+1]).  si_state: 0 not built, 1 uploaded, -1 a group is
+    // beyond the tables (si_error names it)
+    mutable int si_state = 0;
+    mutable int si_groups = 0;  // groups with at least one bit
+    mutable std::string si_error;
+    mutable void* si_alloc[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // aptr, adj, kptr, cons, xmask
     // optional per-launch timing of the BP4 kernel with HIP events on the launch stream (fgnn_profile_*)
     mutable bool prof_on = false;
     mutable int prof_n = 0;

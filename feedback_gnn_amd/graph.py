@@ -945,6 +945,38 @@ class TannerGraph:
                                          _stream(self.device)))
         return (hard, stats, path_stats) if want_path_stats else (hard, stats)
 
+    def si_decode(self, synd, num_iter, si_iter, max_groups, factor=0.8, llr_ch=None, llr_const=0.0, B=None, index=None, nact=None,
+                  out=None):
+        """BP-SI on the hx graph (`fgnn_si_decode`): min-sum BP, then stabilizer inactivation with the rows of side 1 (hz) as the
+        groups: up to `max_groups` of them, least reliable first, are erased one at a time, BP runs up to `si_iter` iterations on the
+        rest and the erased bits come from a small linear system.  `index` (int32 on the device) lists the samples to decode, `nact`
+        how many of its entries count (None: all); the rows of the other samples are those of `out` = `(hard, stats)`, written in
+        place, or zeros without it.  Returns `(hard [B,n] uint8, stats [B,4] int32 = found, attempt, iteration within it, group or
+        -1)`; a sample without a solution keeps plain BP's decision."""
+        B, synd, llr_ch = self._binary_in(synd, llr_ch, B)
+        if B is None:
+            raise ValueError("without a syndrome and llr_ch, B must be given")
+        if index is not None:
+            index = self._opt_any(index, torch.int32, "index")
+            nact = int(index.numel()) if nact is None else int(nact)
+            if not 0 <= nact <= min(int(index.numel()), B):
+                raise ValueError("nact must be in 0 .. min(len(index), B)")
+        else:
+            nact = B
+        if out is not None:
+            hard = self._chk_out(out[0], (B, self.n), torch.uint8, "hard")
+            stats = self._chk_out(out[1], (B, 4), torch.int32, "stats")
+        elif index is not None:
+            hard, stats = self._new((B, self.n), torch.uint8).zero_(), self._new((B, 4), torch.int32).zero_()
+        else:
+            hard, stats = self._new((B, self.n), torch.uint8), self._new((B, 4), torch.int32)
+        if index is not None and index.numel() == 0:
+            index = self._new((1,), torch.int32)  # an empty list still is a list: a NULL pointer would mean all B samples
+        check(_lib.lib().fgnn_si_decode(self.handle, float(factor), int(num_iter), int(si_iter), int(max_groups), _ptr(llr_ch),
+                                        float(llr_const), _ptr(synd), B, _ptr(index), nact, _ptr(hard), _ptr(stats),
+                                        _stream(self.device)))
+        return hard, stats
+
     def relay4_decode(self, synd_x, synd_z, gamma, pre_iter, leg_iter, stop_nconv, factor=1.0, llr_ch=None, llr_const=0.0,
                       cn_type="minsum", B=None):
         """Relay-BP4 on both graphs (`fgnn_relay4_decode`): `gamma` [num_legs, n] float32 on the device, one row of memory strengths per

@@ -397,6 +397,60 @@ int fgnn_gdg_decode(const fgnn_graph* g, float normalization_factor, int pre_ite
                     int tail_pick, float decim_llr, const float* llr_ch, float llr_const, const uint8_t* synd, int B,
                     const int32_t* index, int nact, uint8_t* hard_out, int32_t* stats, int32_t* path_stats, void* workspace,
                     size_t ws_bytes, void* stream);
+/* BP-SI: binary min-sum BP with stabilizer inactivation (du Crest, Mhalla, Savin, "Stabilizer inactivation for message-passing decoding
+ * of quantum LDPC codes", 2022).  BP on a degenerate code stalls between errors that differ by a stabilizer; so the least reliable
+ * stabilizer generator is taken, its few bits are erased ("inactivated"), BP runs again on the rest, and the erased bits are filled in
+ * from a small linear system.  No big matrix is inverted.
+ * H is side 0 (hx) of the graph, m_x checks by n bits.  The GROUPS are the rows of side 1 (hz): group j is the set of bits of hz row j.
+ * Nothing else of side 1 is used, and hx.hz^T = 0 is not required.  llr_ch [B,n] logits or NULL (= llr_const everywhere) and synd
+ * [B,m_x] or NULL (all-zero) exactly as fgnn_bp2_decode / fgnn_relay_decode, the +-20 clip and the sign flip included.  index (device
+ * int32 [nact]) selects the samples as in fgnn_gdg_decode, NULL = all B (nact is then ignored); with a list 0 <= nact <= B and the ids
+ * must be distinct; the rows of the samples that are not listed are left untouched in every output.  All arithmetic is float32 in the
+ * order written; a bit's sum runs over its slots ascending from 0.0f; the check update is the min-sum rule of fgnn_relay_decode (clip
+ * +-20 inside the rule, then * normalization_factor).  Per codeword:
+ *     L_v = -1 * clamp(llr_v, -20, 20)
+ *     attempt 0 (plain BP):  mu = 0;  for k = 0 .. num_iter:
+ *         S_v = sum of mu over v's edges
+ *         if k > 0:  P_v = L_v + S_v;  d_v = (P_v < 0)
+ *                    if H d == s:  found = 1, output d, stats = (1, 0, k, -1), done
+ *                    if k == num_iter: leave
+ *         nu_e = (S_v + L_v) - mu_e;  mu = minsum(nu) * normalization_factor
+ *     write d (the decision of k = num_iter) to hard_out: a sample nothing rescues keeps plain BP's output
+ *     score_j = ((0.0f + |P_v0|) + |P_v1|) + ... over group j's bits ascending, P of that last test; groups without a bit are left out
+ *     key_j = (bits(score_j) << 32) | j                 (score >= +0: the float bits order as unsigned integers)
+ *     for a = 1 .. min(max_groups, number of non-empty groups):
+ *         j = the group with the a-th smallest key;  I = its bits;  a check is "adjacent" if it holds a bit of I
+ *         mu = 0;  for k = 0 .. si_iter:
+ *             S_v as above;  if k > 0:  for v not in I: P_v = L_v + S_v, d_v = (P_v < 0);  d_v = 0 on I
+ *                 if every non-adjacent check has parity(d) == s_c:
+ *                     this ends attempt a whether or not the solve below succeeds
+ *                     r_c = s_c ^ parity(d over c) on the adjacent checks
+ *                     solve H[adjacent, I] x = r
+ *                     solvable: e = d with x on I;  found = 1, output e, stats = (1, a, k, j), done
+ *                     else: go to the next group
+ *                 if k == si_iter: next group
+ *             nu_e = (S_v + L_v) - mu_e for v not in I;  nu_e = +0.0f on every edge of a bit of I (erased in every iteration)
+ *             mu = minsum(nu) * normalization_factor
+ *     found = 0:  stats = (0, attempts made, 0, -1)
+ * The solve is unique by definition: take the bits of I in ascending order as columns; a column that depends on the earlier ones gets
+ * x = 0, the others are then determined.  With found = 1, H e == s holds exactly.  hard_out [B,n] (uint8), stats [B,4] (int32) =
+ * found, the attempt a of the output, its k, its group j (-1 for attempt 0).
+ * num_iter, si_iter >= 1, max_groups >= 0; NULL graph or outputs, bad counts, a graph whose state does not fit in LDS (the message
+ * gives the bytes needed and the limit), a group with more than FGNN_SI_MAX_GROUP_BITS bits or with more than FGNN_SI_MAX_ADJACENT
+ * adjacent checks (the message names the first such group; with max_groups = 0 too): FGNN_ERR_ARG before anything is launched or
+ * written.  B = 0 or nact = 0 returns FGNN_OK and needs no buffers.
+ * H[adjacent, I] depends on the group alone: on the first call the host eliminates it once per group and uploads, per group, the
+ * adjacent checks, one 64-bit mask over them per bit of I (x_i = parity(r & mask_i), 0 for a dependent column) and one per
+ * consistency row (solvable iff every parity(r & mask) is 0); the tables stay with the graph.  The kernel gathers r as one 64-bit
+ * word, which is what limits a group to 64 adjacent checks.
+ * Identities: attempt 0 is fgnn_relay_decode with one leg, gamma = 0 and stop_nconv = 1, bit for bit (hard_out, found, and on a
+ * solution k).  The pick is an integer minimum of a total order: nothing depends on arrival order or launch geometry.  Messages,
+ * posteriors, the m_z scores, the inactive marks and the adjacent checks' residual bits of a codeword stay in LDS for the whole launch;
+ * there is no global-memory variant. */
+enum { FGNN_SI_MAX_GROUP_BITS = 32, FGNN_SI_MAX_ADJACENT = 64 };
+int fgnn_si_decode(const fgnn_graph* g, float normalization_factor, int num_iter, int si_iter, int max_groups, const float* llr_ch,
+                   float llr_const, const uint8_t* synd, int B, const int32_t* index, int nact, uint8_t* hard_out, int32_t* stats,
+                   void* stream);
 /* BP4 with prior feedback: when BP4 has run its iterations without a solution, the unsatisfied checks of its last estimate choose
  * qubits whose channel LLRs are changed, and BP4 runs again: the hand-written rules the learned feedback of the GNN replaces.
  *   FGNN_FB_PERTURB    random perturbation (Poulin, Chung, "On the iterative decoding of sparse quantum codes", 2008)
