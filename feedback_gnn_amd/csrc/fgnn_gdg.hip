@@ -9,11 +9,13 @@
 // sample's, and the decisions and the four result words of a path go to row vb of the workspace.  Several paths of one sample may share a
 // workgroup, or lie in two.  gdg_select_kernel then reads a sample's P results, picks the path and copies its row to hard_out.
 //
-// The step is relay_kernel's (fgnn_relay.hip) with the memory term taken out and the fix marks put in: the frame of fgnn_step.h
-// (StepCw, BitRows, StepSynd, BitSlots, row_unpack), the min-sum rule of fgnn_cn.h, and the leg control of fgnn_legs.h with a round as
-// a leg: R + 1 legs, stop at the first solution.  LegCtl weighs the test that ends a path (integer atomics into wacc[cw], complete one
-// barrier interval later) and has the kernel write that decision.  A round differs from a leg in that the messages are kept: at k = 0 of
-// a round r > 0 the bit phase fetches them as they are and sends x - mu with the new Lhat.
+// The step is that of the binary leg decoders in fgnn_step.h (StepCw, BitRows, StepSynd, BitSlots; bit_check for the check phase,
+// bit_weigh for the weight of a decision, bit_sample for the sample's rows, BitArgs on the host), which relay_kernel (fgnn_relay.hip)
+// and si_kernel (fgnn_si.hip) run too; its own is the bit phase, relay_kernel's with the memory term taken out and the fix marks put
+// in, and the pick.  The control is that of fgnn_legs.h with a round as a leg: R + 1 legs, stop at the first solution.  LegCtl weighs
+// the test that ends a path (integer atomics into wacc[cw], complete one barrier interval later) and has the kernel write that
+// decision.  A round differs from a leg in that the messages are kept: at k = 0 of a round r > 0 the bit phase fetches them as they
+// are and sends x - mu with the new Lhat.
 //
 // The pick is bp4gd_kernel's (fgnn_bp4gd.hip): at the last test of a round (k = T) every free bit posts a 64-bit key into the
 // codeword's LDS word of that round's parity, and the control section of the same step, two barriers later, reads the winner; its owner
@@ -32,7 +34,6 @@
 //   stamp[cpb], wacc[cpb], ndone   the words of the leg control (leg_stage)
 // hx of [[882,24]]: 2648 + 884 + 224 floats = 15 024 bytes per path.
 #include "fgnn_step.h"
-#include "fgnn_cn.h"
 
 #ifndef FGNN_GDG_WAVES
 #define FGNN_GDG_WAVES 6  // waves per SIMD the register allocation aims at (relay_kernel's target)
@@ -44,16 +45,16 @@
 
 namespace {
 
-struct GdgArgs {
-    int VB, tpc, cpb, lds_per_cw, p_off, f_off, max_steps;  // VB = nact * P virtual codewords
+struct GdgArgs : BitArgs {   // B = nact * P virtual codewords
+    int f_off, max_steps;
     int depth, rounds, tail_least;
     LegSched legs;           // a round is a leg: pre_iter, rounds + 1, round_iter, 1
     float factor, llr_const, decim;
-    const float* llr_ch;     // [B,n] logits or null
-    const uint8_t* synd;     // [B,m_x] or null (all-zero syndrome)
+    const float* llr_ch;     // [.,n] logits or null
+    const uint8_t* synd;     // [.,m_x] or null (all-zero syndrome)
     const int32_t* index;    // [nact] samples or null (sample i is i)
-    uint8_t* dec;            // workspace: [VB,n] decisions
-    int32_t* res;            // workspace: [VB,4] found, w or 0, bits fixed, its
+    uint8_t* dec;            // workspace: [B,n] decisions
+    int32_t* res;            // workspace: [B,4] found, w or 0, bits fixed, its
 };
 
 __device__ __forceinline__ unsigned long long gdg_key_start(const bool least) { return least ? ~0ull : 0ull; }
@@ -63,14 +64,11 @@ template <int DV, int DC>
 __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_GDG_WAVES_OF(DC)))) gdg_kernel(GraphDev g, GdgArgs a)
 {
     FG_LOG_TAB_SETUP();  // cn_update names the phi policy: the table every kernel of that family installs
-    constexpr bool REGULAR = DV > 0;
     extern __shared__ float lds[];
-    const StepCw cw(a.VB, a.tpc, a.cpb);
+    const StepCw cw(a.B, a.tpc, a.cpb);
     const int cwl = cw.cwl, lane = cw.lane;
     const int path = cw.b & ((1 << a.depth) - 1);
-    // the input rows are the sample's: an inactive codeword reads nothing, the index list included
-    StepCw in = cw;
-    in.b = cw.active ? (a.index ? a.index[cw.b >> a.depth] : (cw.b >> a.depth)) : 0;
+    const StepCw in = bit_sample(cw, a.index, cw.b >> a.depth);  // the input rows are the sample's
     const BitRows rows(g, a.llr_ch, a.llr_const, a.synd, in);
     float* msg = lds + (size_t)cwl * a.lds_per_cw;
     float* P = msg + a.p_off;
@@ -145,45 +143,8 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_
         // ---- checks: parity of the decisions (k > 0), then the min-sum update (k < T) ----
         if (!ctl.done) {
             int i = 0;
-            for (int c = lane; c < m; c += a.tpc, ++i) {
-                const unsigned sy = synd.at(g, rows, i, c);
-                if constexpr (REGULAR) {
-                    unsigned off[DC];
-                    row_unpack(g, c, off);
-                    if (k > 0) {
-                        unsigned par = sy;
-#pragma unroll
-                        for (int j = 0; j < DC; ++j) par ^= (unsigned)(P[row_qubit<DV>(off[j], 0u)] < 0.0f);
-                        if (par) ws.stamp[cwl] = step;
-                    }
-                    if (k < T) cn_minsum_regular<DC>(msg, off, DC, sy, a.factor);
-                } else if constexpr (DC > 0) {
-                    const int c0 = g.cptr[c], deg = g.cptr[c + 1] - c0;
-                    if (k > 0) {  // before the slot list is loaded: the two index lists are never live together
-                        int vn[DC];
-#pragma unroll
-                        for (int j = 0; j < DC; ++j) vn[j] = (j < deg) ? g.cvn[c0 + j] : 0;
-                        unsigned par = sy;
-#pragma unroll
-                        for (int j = 0; j < DC; ++j) par ^= (unsigned)((j < deg) && (P[vn[j]] < 0.0f));
-                        if (par) ws.stamp[cwl] = step;
-                    }
-                    if (k < T) {
-                        unsigned off[DC];
-#pragma unroll
-                        for (int j = 0; j < DC; ++j) off[j] = (j < deg) ? 4u * (unsigned)g.cslot[c0 + j] : 0u;
-                        cn_minsum_regular<DC>(msg, off, deg, sy, a.factor);
-                    }
-                } else {
-                    const int c0 = g.cptr[c], deg = g.cptr[c + 1] - c0;
-                    if (k > 0) {
-                        unsigned par = sy;
-                        for (int j = 0; j < deg; ++j) par ^= (unsigned)(P[g.cvn[c0 + j]] < 0.0f);
-                        if (par) ws.stamp[cwl] = step;
-                    }
-                    if (k < T) cn_update<FGNN_CN_MINSUM, PhiGnn>(msg, g.cslot + c0, deg, sy, a.factor);
-                }
-            }
+            for (int c = lane; c < m; c += a.tpc, ++i)
+                bit_check<DV, DC>(g, msg, P, c, synd.at(g, rows, i, c), k > 0, k < T, a.factor, [&] { ws.stamp[cwl] = step; });
         }
         __syncthreads();
         // ---- per virtual codeword: solution found, round over (the pick), path finished (fgnn_legs.h) ----
@@ -194,9 +155,7 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_
             } else {
                 const LegTest t = ctl.test(a.legs, T, ws.stamp[cwl] != step);
                 if (t.weigh) {
-                    int part = 0;
-                    for (int v = lane; v < n; v += a.tpc)
-                        if (P[v] < 0.0f) part += (int)__builtin_rintf(1024.0f * rows.prior(v));
+                    const int part = bit_weigh(P, rows, n, lane, a.tpc);
                     if (part) atomicAdd(&ws.wacc[cwl], part);
                     ctl.weighed();
                 }
@@ -295,8 +254,7 @@ extern "C" int fgnn_gdg_decode(const fgnn_graph* g, float normalization_factor, 
     if (depth < 0 || depth > FGNN_GDG_MAX_DEPTH) return fgnn_fail(FGNN_ERR_ARG, "depth must be in 0 .. 6");
     if (tail_pick != FGNN_GDG_MOST && tail_pick != FGNN_GDG_LEAST) return fgnn_fail(FGNN_ERR_ARG, "tail_pick must be FGNN_GDG_MOST or FGNN_GDG_LEAST");
     if (!(decim_llr > 0.0f)) return fgnn_fail(FGNN_ERR_ARG, "decim_llr must be > 0");
-    if (index && (nact < 0 || nact > B)) return fgnn_fail(FGNN_ERR_ARG, "nact must be in 0 .. B");
-    if (!index) nact = B;  // as fgnn_osd0: no list = all B samples
+    if (int err = bit_check_list(index, B, nact)) return err;  // as fgnn_osd0: no list = all B samples
     if (B == 0 || nact == 0) return FGNN_OK;  // nothing to decode needs no buffers
     if (!hard_out || !stats) return fgnn_fail(FGNN_ERR_ARG, "no output buffer");
     if ((size_t)nact << depth > (size_t)INT_MAX) return fgnn_fail(FGNN_ERR_ARG, "nact * 2^depth must fit an int");
@@ -308,31 +266,17 @@ extern "C" int fgnn_gdg_decode(const fgnn_graph* g, float normalization_factor, 
     const int VB = nact << depth;
     const LaunchGeom L = fgnn_geom(g, VB);
     GdgArgs a;
-    a.VB = VB;
-    a.tpc = L.tpc;
-    a.cpb = L.cpb;
     a.depth = depth;
     a.rounds = std::min(max_rounds, g->d.n);
     a.tail_least = tail_pick == FGNN_GDG_LEAST;
-    a.legs = {pre_iter, a.rounds + 1, round_iter, 1};
-    a.max_steps = attempt_step_bound(pre_iter, a.rounds, round_iter);  // the step after a path's last weighs its last decision
-    a.factor = normalization_factor;
-    a.llr_const = llr_const;
-    a.decim = decim_llr;
-    a.llr_ch = llr_ch;
-    a.synd = synd;
+    bit_args_fill(a, VB, {pre_iter, a.rounds + 1, round_iter, 1}, normalization_factor, llr_ch, llr_const, synd);
     a.index = index;
+    a.decim = decim_llr;
     a.res = static_cast<int32_t*>(workspace);
     a.dec = reinterpret_cast<uint8_t*>(a.res + (size_t)VB * 4);
-    // per virtual codeword: E_x messages, n posteriors and n fix bytes, each rounded up to 4 floats; per workgroup: two 64-bit keys,
-    // stamp and wacc per codeword, ndone
-    a.p_off = (int)lds_round4(g->d.E_x);
-    a.f_off = a.p_off + (int)lds_round4(g->d.n);
-    a.lds_per_cw = a.f_off + (int)lds_bytes_as_floats(g->d.n);
-    const size_t lds_bytes = (size_t)a.lds_per_cw * sizeof(float) * (size_t)L.cpb + 16 * (size_t)L.cpb + lds_round4(leg_lds_words(L.cpb)) * sizeof(int);
-    if (lds_bytes > FGNN_LDS_BUDGET)
-        return fgnn_fail(FGNN_ERR_ARG, "code too large for the LDS-resident BP-GDG kernel: " + std::to_string(lds_bytes) +
-                                           " bytes of LDS per workgroup, the limit is " + std::to_string(FGNN_LDS_BUDGET));
+    // per virtual codeword: E_x messages, n posteriors and n fix bytes; per workgroup: two 64-bit keys per codeword, the leg words
+    size_t lds_bytes;
+    if (int err = bit_lds_bytes(a, g, L, "BP-GDG", {{(size_t)g->d.n, &a.f_off}}, 2, &lds_bytes)) return err;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (int err = bit_dispatch(g, FGNN_CN_MINSUM, true, [&](auto, auto dv, auto dc) {
             return fgnn_launch(gdg_kernel<decltype(dv)::value, decltype(dc)::value>, dim3(L.blocks), dim3(L.threads), lds_bytes, st, g->d, a);

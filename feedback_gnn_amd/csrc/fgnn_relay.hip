@@ -10,10 +10,10 @@
 // Codewords of one workgroup stop at different steps.  The leg / stop / weight control is the shared one of fgnn_legs.h (LegCtl:
 // registers every thread of a codeword holds identically; stamp[cw], wacc[cw] and ndone in LDS, laid out by leg_stage, written in
 // one barrier interval and read in the next); the kernel stands on the frame of fgnn_step.h (StepCw, BitRows, StepSynd, BitSlots,
-// row_unpack).  Its own are the memory term on the posteriors, the weight of a decision (the bits with P < 0, each the rounded
-// 1024-fold of its prior) and the write of the decisions from the signs of P.
+// row_unpack) and shares its check phase (bit_check), the weight of a decision (bit_weigh: the bits with P < 0, each the rounded
+// 1024-fold of its prior) and its host frame (BitArgs) with gdg_kernel and si_kernel there.  Its own are the memory term on the
+// posteriors and the write of the decisions from the signs of P.
 #include "fgnn_step.h"
-#include "fgnn_cn.h"
 
 #ifndef FGNN_RELAY_WAVES
 #define FGNN_RELAY_WAVES 6  // waves per SIMD the register allocation aims at (bp2_kernel's target)
@@ -24,8 +24,8 @@
 
 namespace {
 
-struct RelayArgs {
-    int B, tpc, cpb, lds_per_cw, p_off, max_steps;
+struct RelayArgs : BitArgs {
+    int max_steps;
     LegSched legs;
     float factor, llr_const;
     const float* gamma;    // [num_legs,n]
@@ -40,7 +40,6 @@ template <int DV, int DC>
 __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_RELAY_WAVES_OF(DC)))) relay_kernel(GraphDev g, RelayArgs a)
 {
     FG_LOG_TAB_SETUP();  // cn_update names the phi policy: the table every kernel of that family installs (FGNN_LDS_BUDGET leaves its 256 bytes)
-    constexpr bool REGULAR = DV > 0;
     extern __shared__ float lds[];
     const StepCw cw(a.B, a.tpc, a.cpb);
     const int cwl = cw.cwl, lane = cw.lane;
@@ -95,45 +94,8 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_
         // ---- checks: parity of the decisions (k > 0), then the min-sum update (k < T) ----
         if (!ctl.done) {
             int i = 0;
-            for (int c = lane; c < m; c += a.tpc, ++i) {
-                const unsigned sy = synd.at(g, rows, i, c);
-                if constexpr (REGULAR) {
-                    unsigned off[DC];
-                    row_unpack(g, c, off);
-                    if (k > 0) {
-                        unsigned par = sy;
-#pragma unroll
-                        for (int j = 0; j < DC; ++j) par ^= (unsigned)(P[row_qubit<DV>(off[j], 0u)] < 0.0f);
-                        if (par) ws.stamp[cwl] = step;
-                    }
-                    if (k < T) cn_minsum_regular<DC>(msg, off, DC, sy, a.factor);
-                } else if constexpr (DC > 0) {
-                    const int c0 = g.cptr[c], deg = g.cptr[c + 1] - c0;
-                    if (k > 0) {  // before the slot list is loaded: the two index lists are never live together
-                        int vn[DC];
-#pragma unroll
-                        for (int j = 0; j < DC; ++j) vn[j] = (j < deg) ? g.cvn[c0 + j] : 0;
-                        unsigned par = sy;
-#pragma unroll
-                        for (int j = 0; j < DC; ++j) par ^= (unsigned)((j < deg) && (P[vn[j]] < 0.0f));
-                        if (par) ws.stamp[cwl] = step;
-                    }
-                    if (k < T) {
-                        unsigned off[DC];
-#pragma unroll
-                        for (int j = 0; j < DC; ++j) off[j] = (j < deg) ? 4u * (unsigned)g.cslot[c0 + j] : 0u;
-                        cn_minsum_regular<DC>(msg, off, deg, sy, a.factor);
-                    }
-                } else {
-                    const int c0 = g.cptr[c], deg = g.cptr[c + 1] - c0;
-                    if (k > 0) {
-                        unsigned par = sy;
-                        for (int j = 0; j < deg; ++j) par ^= (unsigned)(P[g.cvn[c0 + j]] < 0.0f);
-                        if (par) ws.stamp[cwl] = step;
-                    }
-                    if (k < T) cn_update<FGNN_CN_MINSUM, PhiGnn>(msg, g.cslot + c0, deg, sy, a.factor);
-                }
-            }
+            for (int c = lane; c < m; c += a.tpc, ++i)
+                bit_check<DV, DC>(g, msg, P, c, synd.at(g, rows, i, c), k > 0, k < T, a.factor, [&] { ws.stamp[cwl] = step; });
         }
         __syncthreads();
         // ---- per codeword: solution found, leg over, decoder finished (fgnn_legs.h) ----
@@ -143,9 +105,7 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_
             } else {
                 const LegTest t = ctl.test(a.legs, T, ws.stamp[cwl] != step);
                 if (t.weigh) {
-                    int part = 0;
-                    for (int v = lane; v < n; v += a.tpc)
-                        if (P[v] < 0.0f) part += (int)__builtin_rintf(1024.0f * rows.prior(v));
+                    const int part = bit_weigh(P, rows, n, lane, a.tpc);
                     if (part) atomicAdd(&ws.wacc[cwl], part);
                     ctl.weighed();
                 }
@@ -178,23 +138,13 @@ extern "C" int fgnn_relay_decode(const fgnn_graph* g, float normalization_factor
     FGNN_DEVICE_GUARD(g->device);
     LaunchGeom L = fgnn_geom(g, B);
     RelayArgs a;
-    a.B = B;
-    a.tpc = L.tpc;
-    a.cpb = L.cpb;
-    a.legs = {pre_iter, num_legs, leg_iter, stop_nconv};
-    a.max_steps = attempt_step_bound(pre_iter, num_legs - 1, leg_iter);  // the step after a codeword's last weighs its last decision
-    a.factor = normalization_factor;
-    a.llr_const = llr_const;
+    bit_args_fill(a, B, {pre_iter, num_legs, leg_iter, stop_nconv}, normalization_factor, llr_ch, llr_const, synd);
     a.gamma = gamma;
-    a.llr_ch = llr_ch;
-    a.synd = synd;
     a.hard_out = hard_out;
     a.stats = stats;
-    // per codeword: E_x messages and n posteriors, each rounded up to 4 floats; per workgroup: stamp and wacc per codeword, ndone
-    a.p_off = (int)lds_round4(g->d.E_x);
-    a.lds_per_cw = a.p_off + (int)lds_round4(g->d.n);
-    const size_t lds_bytes = (size_t)a.lds_per_cw * sizeof(float) * (size_t)L.cpb + lds_round4(leg_lds_words(L.cpb)) * sizeof(int);
-    if (lds_bytes > FGNN_LDS_BUDGET) return fgnn_fail(FGNN_ERR_ARG, "code too large for the LDS-resident kernel");
+    // per codeword: E_x messages and n posteriors; per workgroup: stamp and wacc per codeword, ndone
+    size_t lds_bytes;
+    if (int err = bit_lds_bytes(a, g, L, nullptr, {}, 0, &lds_bytes)) return err;
     hipStream_t st = static_cast<hipStream_t>(stream);
     return bit_dispatch(g, FGNN_CN_MINSUM, true, [&](auto, auto dv, auto dc) {
         return fgnn_launch(relay_kernel<decltype(dv)::value, decltype(dc)::value>, dim3(L.blocks), dim3(L.threads), lds_bytes, st, g->d, a);

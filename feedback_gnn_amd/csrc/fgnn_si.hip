@@ -6,9 +6,11 @@
 // include/fgnn.h states at fgnn_si_decode.  The parity-check matrix is side 0 (hx) of an fgnn_graph; the groups to inactivate are the
 // rows of side 1 (hz), read from the graph's check-major tables (cptr / cvn from row m_x on).  Nothing else of side 1 is used.
 //
-// The step is relay_kernel's (fgnn_relay.hip) with the memory term taken out and the inactive marks put in: the frame of fgnn_step.h
-// (StepCw, BitRows, StepSynd, BitSlots, row_unpack), the min-sum rule of fgnn_cn.h, and the leg control of fgnn_legs.h with an attempt as
-// a leg: 1 + min(max_groups, non-empty groups) legs, stop at the first solution.  A decision has no weight here, so nothing is weighed
+// The step is that of the binary leg decoders in fgnn_step.h (StepCw, BitRows, StepSynd, BitSlots; bit_check for the check phase, with
+// its own action on an odd check, bit_sample for the sample's rows, BitArgs on the host), which relay_kernel (fgnn_relay.hip) and
+// gdg_kernel (fgnn_gdg.hip) run too; its own is the bit phase, relay_kernel's with the memory term taken out and the inactive marks put
+// in, the groups and the solve.  The control is that of fgnn_legs.h with an attempt as a leg: 1 + min(max_groups, non-empty groups)
+// legs, stop at the first solution.  A decision has no weight here, so nothing is weighed
 // or settled: what an attempt's end writes it writes in the control section of that step, from P, which still holds the tested decision.
 // An attempt ends at its last test (k = T) or, from attempt 1 on, at the first test that leaves every non-adjacent check satisfied;
 // LegCtl::test is told so by T = k.
@@ -40,7 +42,6 @@
 //   key[2], res[2] per codeword (64-bit), then stamp[cpb], wacc[cpb] (unused), ndone: the words of the leg control (leg_stage)
 // hx of [[882,24]] with its hz as groups: 2648 + 884 + 444 + 224 + 112 floats = 17 248 bytes per codeword.
 #include "fgnn_step.h"
-#include "fgnn_cn.h"
 
 #ifndef FGNN_SI_WAVES
 #define FGNN_SI_WAVES 6  // waves per SIMD the register allocation aims at (relay_kernel's target)
@@ -62,15 +63,15 @@ struct SiTabs {
     const u64* xmask;   // [E_z] one mask per hz edge, in the order of g.cvn from g.cptr[m_x] on
 };
 
-struct SiArgs {
-    int nact, tpc, cpb, lds_per_cw, p_off, s_off, i_off, a_off, max_steps;
+struct SiArgs : BitArgs {   // B = the nact listed samples
+    int s_off, i_off, a_off, max_steps;
     LegSched legs;          // an attempt is a leg: num_iter, 1 + attempts, si_iter, 1
     float factor, llr_const;
-    const float* llr_ch;    // [B,n] logits or null
-    const uint8_t* synd;    // [B,m_x] or null (all-zero syndrome)
+    const float* llr_ch;    // [.,n] logits or null
+    const uint8_t* synd;    // [.,m_x] or null (all-zero syndrome)
     const int32_t* index;   // [nact] samples or null (sample i is i)
-    uint8_t* hard_out;      // [B,n]
-    int32_t* stats;         // [B,4]
+    uint8_t* hard_out;      // [.,n]
+    int32_t* stats;         // [.,4]
     SiTabs t;
 };
 
@@ -81,13 +82,10 @@ template <int DV, int DC>
 __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_SI_WAVES_OF(DC)))) si_kernel(GraphDev g, SiArgs a)
 {
     FG_LOG_TAB_SETUP();  // cn_update names the phi policy: the table every kernel of that family installs
-    constexpr bool REGULAR = DV > 0;
     extern __shared__ float lds[];
-    const StepCw cw(a.nact, a.tpc, a.cpb);
+    const StepCw cw(a.B, a.tpc, a.cpb);
     const int cwl = cw.cwl, lane = cw.lane;
-    // the rows, input and output, are the sample's: an inactive codeword reads nothing, the index list included
-    StepCw in = cw;
-    in.b = cw.active ? (a.index ? a.index[cw.b] : cw.b) : 0;
+    const StepCw in = bit_sample(cw, a.index, cw.b);  // the rows, input and output, are the sample's
     const BitRows rows(g, a.llr_ch, a.llr_const, a.synd, in);
     float* msg = lds + (size_t)cwl * a.lds_per_cw;
     float* P = msg + a.p_off;
@@ -177,44 +175,8 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(FGNN_
             };
             int i = 0;
             for (int c = lane; c < m; c += a.tpc, ++i) {
-                const unsigned sy = synd.at(g, rows, i, c);
                 const unsigned ap = r > 0 ? adjpos[c] : 0u;
-                if constexpr (REGULAR) {
-                    unsigned off[DC];
-                    row_unpack(g, c, off);
-                    if (k > 0) {
-                        unsigned par = sy;
-#pragma unroll
-                        for (int j = 0; j < DC; ++j) par ^= (unsigned)(P[row_qubit<DV>(off[j], 0u)] < 0.0f);
-                        if (par) odd(ap);
-                    }
-                    if (k < T) cn_minsum_regular<DC>(msg, off, DC, sy, a.factor);
-                } else if constexpr (DC > 0) {
-                    const int c0 = g.cptr[c], deg = g.cptr[c + 1] - c0;
-                    if (k > 0) {  // before the slot list is loaded: the two index lists are never live together
-                        int vn[DC];
-#pragma unroll
-                        for (int j = 0; j < DC; ++j) vn[j] = (j < deg) ? g.cvn[c0 + j] : 0;
-                        unsigned par = sy;
-#pragma unroll
-                        for (int j = 0; j < DC; ++j) par ^= (unsigned)((j < deg) && (P[vn[j]] < 0.0f));
-                        if (par) odd(ap);
-                    }
-                    if (k < T) {
-                        unsigned off[DC];
-#pragma unroll
-                        for (int j = 0; j < DC; ++j) off[j] = (j < deg) ? 4u * (unsigned)g.cslot[c0 + j] : 0u;
-                        cn_minsum_regular<DC>(msg, off, deg, sy, a.factor);
-                    }
-                } else {
-                    const int c0 = g.cptr[c], deg = g.cptr[c + 1] - c0;
-                    if (k > 0) {
-                        unsigned par = sy;
-                        for (int j = 0; j < deg; ++j) par ^= (unsigned)(P[g.cvn[c0 + j]] < 0.0f);
-                        if (par) odd(ap);
-                    }
-                    if (k < T) cn_update<FGNN_CN_MINSUM, PhiGnn>(msg, g.cslot + c0, deg, sy, a.factor);
-                }
+                bit_check<DV, DC>(g, msg, P, c, synd.at(g, rows, i, c), k > 0, k < T, a.factor, [&] { odd(ap); });
             }
         }
         __syncthreads();
@@ -380,35 +342,20 @@ extern "C" int fgnn_si_decode(const fgnn_graph* g, float normalization_factor, i
     if (B < 0) return fgnn_fail(FGNN_ERR_ARG, "B must be >= 0");
     if (num_iter < 1 || si_iter < 1) return fgnn_fail(FGNN_ERR_ARG, "num_iter and si_iter must be >= 1");
     if (max_groups < 0) return fgnn_fail(FGNN_ERR_ARG, "max_groups must be >= 0");
-    if (index && (nact < 0 || nact > B)) return fgnn_fail(FGNN_ERR_ARG, "nact must be in 0 .. B");
-    if (!index) nact = B;  // as fgnn_gdg_decode: no list = all B samples
+    if (int err = bit_check_list(index, B, nact)) return err;  // as fgnn_gdg_decode: no list = all B samples
     if (B == 0 || nact == 0) return FGNN_OK;  // nothing to decode needs no buffers
     if (!hard_out || !stats) return fgnn_fail(FGNN_ERR_ARG, "no output buffer");
     const LaunchGeom L = fgnn_geom(g, nact);
     SiArgs a;
-    a.nact = nact;
-    a.tpc = L.tpc;
-    a.cpb = L.cpb;
-    // per codeword: E_x messages, n posteriors, m_z scores, n inactive bytes and m_x adjacent bytes, each rounded up to 4 floats; per
-    // workgroup: four 64-bit words, stamp and wacc per codeword, ndone
-    a.p_off = (int)lds_round4(g->d.E_x);
-    a.s_off = a.p_off + (int)lds_round4(g->d.n);
-    a.i_off = a.s_off + (int)lds_round4(g->d.m_z);
-    a.a_off = a.i_off + (int)lds_bytes_as_floats(g->d.n);
-    a.lds_per_cw = a.a_off + (int)lds_bytes_as_floats(g->d.m_x);
-    const size_t lds_bytes = (size_t)a.lds_per_cw * sizeof(float) * (size_t)L.cpb + 32 * (size_t)L.cpb + lds_round4(leg_lds_words(L.cpb)) * sizeof(int);
-    if (lds_bytes > FGNN_LDS_BUDGET)
-        return fgnn_fail(FGNN_ERR_ARG, "code too large for the LDS-resident BP-SI kernel: " + std::to_string(lds_bytes) +
-                                           " bytes of LDS per workgroup, the limit is " + std::to_string(FGNN_LDS_BUDGET));
+    // per codeword: E_x messages, n posteriors, m_z scores, n inactive and m_x adjacent bytes; per workgroup: four 64-bit words per codeword
+    size_t lds_bytes;
+    if (int err = bit_lds_bytes(a, g, L, "BP-SI", {{4 * (size_t)g->d.m_z, &a.s_off}, {(size_t)g->d.n, &a.i_off}, {(size_t)g->d.m_x, &a.a_off}},
+                                4, &lds_bytes))
+        return err;
     FGNN_DEVICE_GUARD(g->device);
     if (int err = si_ensure(g)) return err;
     const int attempts = std::min(max_groups, g->si_groups);
-    a.legs = {num_iter, attempts + 1, si_iter, 1};
-    a.max_steps = attempt_step_bound(num_iter, attempts, si_iter);
-    a.factor = normalization_factor;
-    a.llr_const = llr_const;
-    a.llr_ch = llr_ch;
-    a.synd = synd;
+    bit_args_fill(a, nact, {num_iter, attempts + 1, si_iter, 1}, normalization_factor, llr_ch, llr_const, synd);
     a.index = index;
     a.hard_out = hard_out;
     a.stats = stats;

@@ -20,22 +20,29 @@
 // whose LDS words leg_stage lays out here.
 // Every float operation stays where it was: the sums run hz before hx, each ascending from 0.
 //
-// The binary decoders on side 0 (hx), bp2_kernel (fgnn_bp2.hip), bp2_layered_kernel (fgnn_bp2_layered.hip), relay_kernel and gdg_kernel
-// (fgnn_gdg.hip, whose codewords are the paths of its samples), take StepCw (from B, tpc, cpb: their argument
-// structs are their own), StepSynd (over the m_x checks of hx) and row_unpack from the frame, and have their own part at the end:
+// The binary decoders on side 0 (hx), bp2_kernel (fgnn_bp2.hip), bp2_layered_kernel (fgnn_bp2_layered.hip), relay_kernel
+// (fgnn_relay.hip), gdg_kernel (fgnn_gdg.hip, whose codewords are the paths of its samples) and si_kernel (fgnn_si.hip), take StepCw
+// (from B, tpc, cpb), StepSynd (over the m_x checks of hx) and row_unpack from the frame, and have their own part at the end:
 //   BitRows                        the llr_ch / output row and the syndrome row of a codeword, synd_of, the prior
 //   BitSlots<DV>                   a bit's message slots: fetch with the ascending sum (or zeros), store x - m_j; QubitSlots' binary sibling
-// and on the host bit_dispatch over (check rule, regular (3,6) / (4,8), predicated runtime degrees up to 8 / 16, loop).
+// and on the host bit_dispatch over (check rule, regular (3,6) / (4,8), predicated runtime degrees up to 8 / 16, loop).  The three on
+// the leg control, relay_kernel, gdg_kernel and si_kernel, keep their bit phases and share
+//   bit_check<DV, DC>              one check of a step: parity of the signs of P, the caller's action where it is odd, the min-sum update
+//   bit_weigh / bit_sample         a lane's part of the weight of the decision in P; the codeword with the rows of a listed sample
+// and on the host BitArgs (the head of their argument structs), bit_args_fill (the inputs, max_steps from the legs), bit_lds_bytes
+// (geometry, offsets, LDS bytes or the refusal, through step_lds_bytes) and bit_check_list (index / nact).
 #ifndef FGNN_STEP_H
 #define FGNN_STEP_H
 
 #include <algorithm>
 #include <climits>
 #include <cmath>
+#include <initializer_list>
 #include <type_traits>
 
 #include "fgnn_internal.h"
 #include "fgnn_math.h"
+#include "fgnn_cn.h"
 #include "fgnn_vn.h"
 #include "fgnn_attempts.h"
 #include "fgnn_legs.h"
@@ -79,13 +86,16 @@ inline size_t lds_round4(size_t floats) { return (floats + 3) & ~(size_t)3; }
 inline size_t lds_bytes_as_floats(size_t bytes) { return lds_round4((bytes + 3) / 4); }
 
 // the LDS of a launch: per_cw floats for each of the cpb codewords, `table_floats` floats and `words` ints per workgroup.  Sets
-// a.lds_per_cw; a launch over the budget is refused under the decoder's name
-inline int step_lds_bytes(StepArgs& a, const char* decoder, size_t per_cw, size_t table_floats, size_t words, size_t* lds_bytes)
+// a.lds_per_cw; a launch over the budget is refused under the decoder's name (Relay-BP gives none).  ARGS: StepArgs or BitArgs
+template <typename ARGS>
+int step_lds_bytes(ARGS& a, const char* decoder, size_t per_cw, size_t table_floats, size_t words, size_t* lds_bytes)
 {
     *lds_bytes = per_cw * sizeof(float) * (size_t)a.cpb + table_floats * sizeof(float) + lds_round4(words) * sizeof(int);
-    if (*lds_bytes > FGNN_LDS_BUDGET)
+    if (*lds_bytes > FGNN_LDS_BUDGET) {
+        if (!decoder) return fgnn_fail(FGNN_ERR_ARG, "code too large for the LDS-resident kernel");
         return fgnn_fail(FGNN_ERR_ARG, std::string("code too large for the LDS-resident ") + decoder + " kernel: " + std::to_string(*lds_bytes) +
                                            " bytes of LDS per workgroup, the limit is " + std::to_string(FGNN_LDS_BUDGET));
+    }
     a.lds_per_cw = (int)per_cw;
     return FGNN_OK;
 }
@@ -189,6 +199,56 @@ int bit_dispatch(const fgnn_graph* g, int cn_type, bool predicated, LAUNCH launc
     if (phi) return launch(PHI, loop, loop);
     if (minsum) return launch(MINSUM, loop, loop);
     return launch(integral_constant<int, FGNN_CN_BOXPLUS>(), loop, loop);
+}
+
+// The head of what a binary decoder on the leg control is told: the codewords of the launch and what bit_lds_bytes lays out (p_off:
+// the posteriors, in floats from msg).  RelayArgs, GdgArgs and SiArgs derive from it.  Required of each of them, behind the head and
+// in its own order (the struct is the kernel's argument; DESIGN.md has what moving them costs): int max_steps; LegSched legs;
+// float factor, llr_const; const float* llr_ch; const uint8_t* synd.  bit_args_fill writes these by name
+struct BitArgs {
+    int B, tpc, cpb, lds_per_cw, p_off;
+};
+
+// the inputs of a checked call, into B and the fields BitArgs requires of ARGS
+template <typename ARGS>
+void bit_args_fill(ARGS& a, int B, const LegSched& legs, float factor, const float* llr_ch, float llr_const, const uint8_t* synd)
+{
+    a.B = B;
+    a.legs = legs;
+    a.max_steps = attempt_step_bound(legs.pre_iter, legs.num_legs - 1, legs.leg_iter);  // the step after a codeword's last weighs its last decision
+    a.factor = factor;
+    a.llr_const = llr_const;
+    a.llr_ch = llr_ch;
+    a.synd = synd;
+}
+
+// The geometry and the LDS of a launch.  Per codeword: E_x messages, n posteriors at a.p_off, then the decoder's own areas of so many
+// bytes, whose offsets are written through `off`, each area rounded up to 4 floats; per workgroup: words64 64-bit words per codeword
+// (keys, residuals: 16-byte aligned), then the words of the leg control, which leg_stage finds at lds + 2 * words64 * cpb
+struct BitArea {
+    size_t bytes;
+    int* off;
+};
+inline int bit_lds_bytes(BitArgs& a, const fgnn_graph* g, const LaunchGeom& L, const char* decoder, std::initializer_list<BitArea> behind_p,
+                         size_t words64, size_t* lds_bytes)
+{
+    a.tpc = L.tpc;
+    a.cpb = L.cpb;
+    a.p_off = (int)lds_round4(g->d.E_x);
+    size_t per_cw = a.p_off + lds_round4(g->d.n);
+    for (const BitArea& area : behind_p) {
+        *area.off = (int)per_cw;
+        per_cw += lds_bytes_as_floats(area.bytes);
+    }
+    return step_lds_bytes(a, decoder, per_cw, 2 * words64 * (size_t)L.cpb, leg_lds_words(L.cpb), lds_bytes);
+}
+
+// the sample list of a call: nact of the B samples, or without a list all of them
+inline int bit_check_list(const int32_t* index, int B, int& nact)
+{
+    if (index && (nact < 0 || nact > B)) return fgnn_fail(FGNN_ERR_ARG, "nact must be in 0 .. B");
+    if (!index) nact = B;
+    return FGNN_OK;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -473,7 +533,7 @@ __device__ __forceinline__ void step_finish(const StepArgs& a, const size_t row,
 }
 
 // ---------------------------------------------------------------------------------------------
-// The binary decoders on side 0 (hx): bp2_kernel (fgnn_bp2.hip) and relay_kernel (fgnn_relay.hip)
+// The binary decoders on side 0 (hx): the rows and slots of all five, then the check, weight and sample of the three on the leg control
 // ---------------------------------------------------------------------------------------------
 
 // the rows of a thread's codeword b: element v of its llr_ch and output rows is at(v), its syndrome bits are synd_of; the pointers are
@@ -560,5 +620,68 @@ struct BitSlots {
         }
     }
 };
+
+// codeword cw reads and writes the rows of the pos-th listed sample, index[pos] (pos without a list): StepCw with that b.  An inactive
+// codeword reads nothing, the index list included
+__device__ __forceinline__ StepCw bit_sample(const StepCw& cw, const int32_t* index, const int pos)
+{
+    StepCw in = cw;
+    in.b = cw.active ? (index ? index[pos] : pos) : 0;
+    return in;
+}
+
+// One check c of a step of the leg decoders, syndrome bit sy: with `test` (k > 0) the parity of the decisions, the signs of the
+// posteriors P, over the check's bits, and odd() where it is odd; with `update` (k < T) the min-sum update of the check's slots.
+// DV/DC > 0: the packed row; DV = 0, DC > 0: runtime degrees up to DC, predicated; DV = DC = 0: the loop
+template <int DV, int DC, typename ODD>
+__device__ __forceinline__ void bit_check(const GraphDev& g, float* msg, const float* P, const int c, const unsigned sy, const bool test,
+                                          const bool update, const float factor, ODD odd)
+{
+    if constexpr (DV > 0) {
+        unsigned off[DC];
+        row_unpack(g, c, off);
+        if (test) {
+            unsigned par = sy;
+#pragma unroll
+            for (int j = 0; j < DC; ++j) par ^= (unsigned)(P[row_qubit<DV>(off[j], 0u)] < 0.0f);
+            if (par) odd();
+        }
+        if (update) cn_minsum_regular<DC>(msg, off, DC, sy, factor);
+    } else if constexpr (DC > 0) {
+        const int c0 = g.cptr[c], deg = g.cptr[c + 1] - c0;
+        if (test) {  // before the slot list is loaded: the two index lists are never live together
+            int vn[DC];
+#pragma unroll
+            for (int j = 0; j < DC; ++j) vn[j] = (j < deg) ? g.cvn[c0 + j] : 0;
+            unsigned par = sy;
+#pragma unroll
+            for (int j = 0; j < DC; ++j) par ^= (unsigned)((j < deg) && (P[vn[j]] < 0.0f));
+            if (par) odd();
+        }
+        if (update) {
+            unsigned off[DC];
+#pragma unroll
+            for (int j = 0; j < DC; ++j) off[j] = (j < deg) ? 4u * (unsigned)g.cslot[c0 + j] : 0u;
+            cn_minsum_regular<DC>(msg, off, deg, sy, factor);
+        }
+    } else {
+        const int c0 = g.cptr[c], deg = g.cptr[c + 1] - c0;
+        if (test) {
+            unsigned par = sy;
+            for (int j = 0; j < deg; ++j) par ^= (unsigned)(P[g.cvn[c0 + j]] < 0.0f);
+            if (par) odd();
+        }
+        if (update) cn_update<FGNN_CN_MINSUM, PhiGnn>(msg, g.cslot + c0, deg, sy, factor);
+    }
+}
+
+// a lane's part of the weight of the decision in P: over its bits with P < 0, the rounded 1024-fold of the prior
+__device__ __forceinline__ int bit_weigh(const float* P, const BitRows& rows, const int n, const int lane, const int tpc)
+{
+    int part = 0;
+    for (int v = lane; v < n; v += tpc)
+        if (P[v] < 0.0f) part += (int)__builtin_rintf(1024.0f * rows.prior(v));
+    return part;
+}
 
 #endif

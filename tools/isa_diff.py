@@ -3,8 +3,11 @@
 
 Each directory holds <file>.s for the same .hip files, compiled device-only to assembly with the Makefile's FLAGS (tools/isa_count.sh
 shows the command line).  Per kernel: whether the instruction lines are identical once the .LBB label numbers are renumbered in
-order of appearance, the instruction counts, and vgpr_count / sgpr_count / private_segment_fixed_size / group_segment_fixed_size
-from the code object metadata.  Exit status 1 if a kernel exists on one side only, gains scratch, or gains VGPRs."""
+order of appearance, whether the instruction counts are equal, whether the opcode histograms are (the first token of every
+instruction line, compared as a multiset: equal where only register numbers, offsets and the order of instructions moved), and
+vgpr_count / sgpr_count / private_segment_fixed_size / group_segment_fixed_size from the code object metadata.  Exit status 1 if a
+kernel exists on one side only, gains scratch, or gains VGPRs."""
+import collections
 import json
 import os
 import re
@@ -37,8 +40,13 @@ def kernels(path):
                 continue
             l = re.sub(r"\.LBB\d+_\d+", lambda m: labels.setdefault(m.group(0), ".L%d" % len(labels)), l)
             ins.append(" ".join(l.split()))
-        out[name] = {"stream": ins, "instructions": sum(not i.startswith(".L") for i in ins), **{k: int(md[k]) for k in META}}
+        ops = collections.Counter(i.split()[0] for i in ins if not i.startswith(".L"))
+        out[name] = {"stream": ins, "opcodes": ops, "instructions": sum(ops.values()), **{k: int(md[k]) for k in META}}
     return out
+
+
+def shown(k):
+    return {key: v for key, v in k.items() if key not in ("stream", "opcodes")}
 
 
 def main():
@@ -53,15 +61,16 @@ def main():
         per = {}
         for name in sorted(set(kp) & set(kn)):
             p, n = kp[name], kn[name]
-            per[name] = {"identical": p["stream"] == n["stream"],
-                         "parent": {k: v for k, v in p.items() if k != "stream"}, "new": {k: v for k, v in n.items() if k != "stream"}}
+            per[name] = {"identical": p["stream"] == n["stream"], "same_instruction_count": p["instructions"] == n["instructions"],
+                         "same_opcode_histogram": p["opcodes"] == n["opcodes"], "parent": shown(p), "new": shown(n)}
             if n["private_segment_fixed_size"] > p["private_segment_fixed_size"] or n["vgpr_count"] > p["vgpr_count"]:
                 bad.append(name + ": more scratch or VGPRs than the parent")
         res[f[:-2] + ".hip"] = {"kernels": len(per), "identical": sum(k["identical"] for k in per.values()), "per_kernel": per}
         print(f"{f[:-2]}.hip: {len(per)} kernels, {res[f[:-2] + '.hip']['identical']} identical to the parent")
         for name, k in per.items():
             if not k["identical"]:
-                print("   differs:", name, k["parent"], k["new"])
+                print("   differs:", name, "instruction count", "equal," if k["same_instruction_count"] else "DIFFERS,",
+                      "opcode histogram", "equal" if k["same_opcode_histogram"] else "DIFFERS", k["parent"], k["new"])
     if len(sys.argv) > 3:
         json.dump(res, open(sys.argv[3], "w"), indent=1)
     for b in bad:
