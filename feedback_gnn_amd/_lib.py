@@ -105,6 +105,8 @@ _SIGNATURES = {
                                   C.c_void_p, C.c_void_p]),
     "fgnn_relay_decode": (C.c_int, [C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float,
                                     C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fgnn_relay_decode_layered": (C.c_int, [C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float,
+                                            C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "fgnn_gdg_workspace_bytes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     "fgnn_gdg_decode": (C.c_int, [C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_float,
                                   C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,

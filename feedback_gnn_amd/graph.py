@@ -900,6 +900,19 @@ class TannerGraph:
                                            _stream(self.device)))
         return hard, stats
 
+    def relay_decode_layered(self, synd, gamma, pre_iter, leg_iter, stop_nconv, factor=1.0, llr_ch=None, llr_const=0.0, B=None):
+        """`relay_decode` with legs in the layered (serial) schedule (`fgnn_relay_decode_layered`): every iteration of a leg updates the
+        hx checks layer by layer on running posteriors.  Arguments and return as `relay_decode`.  A graph without a bit layering gets
+        the greedy one (`set_bit_layers`)."""
+        B, synd, llr_ch = self._binary_in(synd, llr_ch, B)
+        gamma = self._gamma_in(gamma)
+        hard = self._new((B, self.n), torch.uint8)
+        stats = self._new((B, 4), torch.int32)
+        check(_lib.lib().fgnn_relay_decode_layered(self.handle, float(factor), int(pre_iter), int(gamma.shape[0]), int(leg_iter),
+                                                   int(stop_nconv), _ptr(gamma), _ptr(llr_ch), float(llr_const), _ptr(synd), B, _ptr(hard),
+                                                   _ptr(stats), _stream(self.device)))
+        return hard, stats
+
     def gdg_workspace_bytes(self, depth, nact):
         """Bytes of device workspace `fgnn_gdg_decode` needs for `nact` samples at `depth`."""
         nbytes = C.c_size_t()

@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from ._frontend import CodeDecoder, DepolarizingBP4Model, ShardedModel, alias, bsc_logit
-from .decoding import _binary_graph
+from .decoding import _adopt_bit_layers, _binary_graph
 
 
 def _relay_schedule(pre_iter, num_sets, set_max_iter, gamma_dist_interval, stop_nconv):
@@ -44,14 +44,25 @@ class RelayBPDecoder:
 
     Call ``decoder((llr_ch[bs,n], syndrome[m,bs]))`` as ``LDPCBPDecoder(is_syndrome=True, hard_out=True)``: ``llr_ch`` are logits
     (log p(1)/p(0)), the result is the estimate ``e_hat[bs,n]`` (0/1 floats).  ``last_stats[bs,4]`` (int32) = solutions found, weight
-    of the estimate (sum of rint(1024 * |clipped logit|) signed as the prior), its leg and its iteration within the leg."""
+    of the estimate (sum of rint(1024 * |clipped logit|) signed as the prior), its leg and its iteration within the leg.
+
+    ``schedule="flooding"`` (the default) runs every leg as flooding min-sum (`fgnn_relay_decode`); ``schedule="layered"`` runs the legs
+    in the layered (serial) check schedule (`fgnn_relay_decode_layered`), on the bit layering of the graph: ``layers`` [m] gives every
+    check its layer and is handed to ``graph.set_bit_layers`` (None: the layering the graph has, or the greedy one)."""
+
+    SCHEDULES = ("flooding", "layered")
 
     def __init__(self, pcm, gamma0=0.125, pre_iter=80, num_sets=60, set_max_iter=60, gamma_dist_interval=(-0.24, 0.66), stop_nconv=1,
-                 normalization_factor=1.0, seed=0, device=None, graph=None):
+                 normalization_factor=1.0, seed=0, device=None, graph=None, schedule="flooding", layers=None):
         pcm = np.asarray(pcm.toarray() if hasattr(pcm, "toarray") else pcm)
         if not np.array_equal(pcm, pcm.astype(bool)):
             raise AssertionError('PC matrix must be binary.')
+        if not isinstance(schedule, str) or schedule not in self.SCHEDULES:
+            raise ValueError(f"schedule must be 'flooding' or 'layered', got {schedule!r}")
+        if layers is not None and schedule != "layered":
+            raise ValueError("layers= belongs to schedule='layered'")
         lo, hi = _relay_schedule(pre_iter, num_sets, set_max_iter, gamma_dist_interval, stop_nconv)
+        self.schedule = schedule
         self._pcm = pcm
         self.pre_iter, self.num_sets, self.set_max_iter, self.stop_nconv = int(pre_iter), int(num_sets), int(set_max_iter), int(stop_nconv)
         self.gamma0, self.gamma_dist_interval, self.seed = float(gamma0), (lo, hi), int(seed)
@@ -59,6 +70,8 @@ class RelayBPDecoder:
         self.graph = graph if graph is not None else _binary_graph(pcm, None, device)
         self._num_vns, self._num_cns = self.graph.n, self.graph.m_x
         self.gamma = _draw_gamma(self.gamma0, self.num_sets, self._num_vns, lo, hi, self.seed)
+        if schedule == "layered" and (layers is not None or self.graph.bit_layers()[0] == 0):
+            self.graph.set_bit_layers(layers)  # None: the greedy layering; a shared graph keeps the layering it already has
         self.last_stats = None
 
     pcm = property(lambda self: self._pcm)
@@ -80,10 +93,14 @@ class RelayBPDecoder:
 
     def decode(self, synd, llr_ch=None, llr_const=0.0, B=None):
         """Estimates and stats for syndromes [B, m] (uint8, device) under per-bit logits ``llr_ch`` [B, n] or one logit for every bit."""
-        hard, stats = self.graph.relay_decode(synd, self._gamma, self.pre_iter, self.set_max_iter, self.stop_nconv,
+        hard, stats = self._entry(self.graph)(synd, self._gamma, self.pre_iter, self.set_max_iter, self.stop_nconv,
                                               self.normalization_factor, llr_ch=llr_ch, llr_const=llr_const, B=B)
         self.last_stats = stats
         return hard, stats
+
+    def _entry(self, graph):
+        """The wrapper of `graph` that runs this decoder's schedule."""
+        return graph.relay_decode_layered if self.schedule == "layered" else graph.relay_decode
 
     def __call__(self, inputs):
         g = self.graph
@@ -108,11 +125,13 @@ class BP2_Relay_Model(ShardedModel):
     """``BP2_Relay_Model(pcm, logical_pcm, relay_decoder)``; ``model(batch_size, p)`` → ``(s_hat[bs,m], ls_hat[bs,rows(logical_pcm)])``,
     shaped like ``BP2_OSD_Model``: BSC(p) noise, its syndrome, Relay-BP.  ``s_hat = pcm·(noise xor estimate)`` is non-zero exactly on
     the samples for which no solution was found, ``ls_hat = logical_pcm·(noise xor estimate)``.  After a call ``last_noise``,
-    ``last_estimate`` (uint8 [bs,n]), ``last_stats`` (int32 [bs,4]) and ``last_num_unsolved`` describe that batch."""
+    ``last_estimate`` (uint8 [bs,n]), ``last_stats`` (int32 [bs,4]) and ``last_num_unsolved`` describe that batch.  The model follows
+    its decoder's ``schedule``: under a layered decoder its graph takes the decoder's layering and the legs run layered."""
 
     def __init__(self, pcm, logical_pcm, relay_decoder, *, seed=0x5EED, rank=0, world_size=1):
         self.pcm, self.logical_pcm, self.relay_decoder = pcm, logical_pcm, relay_decoder
         self.graph = _binary_graph(pcm, logical_pcm, relay_decoder.graph.device)
+        _adopt_bit_layers(self.graph, relay_decoder)  # a layered decoder: its layering on the model's own graph
         self._shard(seed, rank, world_size)
         self.last_noise = self.last_estimate = self.last_stats = None
         self.last_num_unsolved = 0
@@ -123,8 +142,8 @@ class BP2_Relay_Model(ShardedModel):
         noise = g.bsc_noise(self.seed, p, self._take(B), B)
         zeros = torch.zeros_like(noise)
         synd, _ = g.syndrome(zeros, noise)
-        noise_hat, stats = g.relay_decode(synd, d.gamma, d.pre_iter, d.set_max_iter, d.stop_nconv, d.normalization_factor,
-                                          llr_const=bsc_logit(p), B=B)
+        noise_hat, stats = d._entry(g)(synd, d.gamma, d.pre_iter, d.set_max_iter, d.stop_nconv, d.normalization_factor,
+                                       llr_const=bsc_logit(p), B=B)
         d.last_stats = stats
         self.last_noise, self.last_estimate, self.last_stats = noise, noise_hat, stats
         self.last_num_unsolved = int((stats[:, 0] == 0).sum().item())

@@ -797,6 +797,32 @@ int fgnn_graph_bit_layers(const fgnn_graph* g, int32_t* num_layers, int32_t* lay
 int fgnn_bp2_decode_layered(const fgnn_graph* g, int cn_type, int num_iter, float normalization_factor, const float* llr_ch,
                             float llr_const, const uint8_t* synd, int B, int stop, float* soft_out, uint8_t* hard_out,
                             int32_t* stats /* [B,2] or NULL */, void* stream);
+/* Relay-BP whose legs run in the layered (serial) schedule: fgnn_relay_decode's chain of min-sum legs with per-bit memory strengths,
+ * every iteration of a leg updating the hx checks one layer at a time on running posteriors as fgnn_bp2_decode_layered does.  The
+ * arguments, hard_out [B,n], stats [B,4] and the refusals are those of fgnn_relay_decode.  It runs on the bit layering of the graph
+ * (fgnn_graph_set_bit_layers; a graph without one gets the greedy one) and is min-sum only.  All arithmetic is float32 in the order
+ * written; a bit's sum runs over its slots in ascending order from 0.0f.  Per codeword:
+ *     L_v = -1 * clamp(llr_v, -20, 20);  q_v = (int32) rint(1024 * L_v);  P_v = L_v;  found = 0
+ *     for r in 0 .. num_legs-1:   T = pre_iter if r == 0 else leg_iter;  mu_e = 0 on every edge;  gam_v = gamma[r, v]
+ *         for k in 1 .. T:                                   (k = finished iterations of this leg)
+ *             Lam_v = (1.0f - gam_v) * L_v + gam_v * P_v     (two products, then one add; P_v is what the previous iteration, or the previous leg, ended with)
+ *             P_v = Lam_v + S_v,  S_v = sum of mu_e over the bit's edges      (re-summed once per iteration; at k = 1 S_v = 0.0f)
+ *             for each layer in order, for each check c of the layer:
+ *                 nu_e = P_v - mu_e on c's edges;  mu = min-sum update of nu (clip +-20, * normalization_factor);  P_v = nu_e + mu_e
+ *             d_v = (P_v < 0)
+ *             if H d == s:  w = sum_v d_v q_v;  found += 1;  if found == 1 or w < best_w: best = (d, w, r, k);  end this leg
+ *         if found == stop_nconv: stop
+ * hard_out = the best d if found > 0, else the d of the last test made (last leg, k = T);  stats = found, w of the output, its leg, its k.
+ * The posterior is re-summed at the head of an iteration, not corrected by the change of Lam: no rounding drift builds up over
+ * hundreds of iterations and no second per-bit array is kept.  The consequence: with gamma = 0 and one leg the decisions equal those of
+ * fgnn_bp2_decode_layered (min-sum, stop = 1) bit for bit at pre_iter = 1 only, where P = L + 0.0f on both sides; from the second
+ * iteration on the two associate the same sum differently (Lam + (mu_0 + mu_1 + ..) here, ((L + ..) - mu_e) + mu_e' there).
+ * The messages and posteriors of a codeword stay in LDS for the whole launch, laid out as for fgnn_relay_decode; a graph they do not
+ * fit is refused (FGNN_ERR_ARG), there is no global-memory variant.  Without fgnn_graph_set_launch a codeword gets at most 128 threads,
+ * as in fgnn_bp2_decode_layered.  B = 0: FGNN_OK. */
+int fgnn_relay_decode_layered(const fgnn_graph* g, float normalization_factor, int pre_iter, int num_legs, int leg_iter, int stop_nconv,
+                              const float* gamma, const float* llr_ch, float llr_const, const uint8_t* synd, int B, uint8_t* hard_out,
+                              int32_t* stats, void* stream);
 /* BinarySymmetricChannel on the all-zero word, BP_BSC_Model.call feedback_gnn.py:213-214: noise = u < p (Philox stream). */
 int fgnn_bsc_noise(uint64_t seed, float p, uint64_t first_sample, int B, int n, uint8_t* noise, void* stream);
 
