@@ -252,6 +252,8 @@ extern "C" void fgnn_graph_destroy(fgnn_graph* g)
         if (p) (void)hipFree(p);
     for (void* p : g->bit_layer_alloc)
         if (p) (void)hipFree(p);
+    for (void* p : g->qubit_layer_alloc)
+        if (p) (void)hipFree(p);
     for (void* p : g->si_alloc)
         if (p) (void)hipFree(p);
     for (void* p : g->allocs) (void)hipFree(p);
@@ -707,6 +709,181 @@ int fgnn_graph_ensure_bit_layers(const fgnn_graph* g)
     if (g->num_bit_layers > 0) return FGNN_OK;
     if (g->host_only) return fgnn_fail(FGNN_ERR_STATE, "a host-only graph carries no device tables");
     return install_bit_layers(g, 0, nullptr);
+}
+
+// ---- layers of the qubits, for the schedule that is serial along qubits (fgnn_mbp4_decode_serial) -------------------------------------
+namespace {
+
+// the checks of every qubit (combined numbers, hx checks first), ascending, from the qubits of every check
+void qubit_checks(int n, int m, const std::vector<int>& cptr, const std::vector<int>& cvn, std::vector<int>& vptr, std::vector<int>& vchk)
+{
+    vptr.assign(n + 1, 0);
+    for (int v : cvn) vptr[v + 1]++;
+    for (int v = 0; v < n; ++v) vptr[v + 1] += vptr[v];
+    vchk.resize(cvn.size());
+    std::vector<int> fill(vptr.begin(), vptr.end() - 1);
+    for (int c = 0; c < m; ++c)
+        for (int p = cptr[c]; p < cptr[c + 1]; ++p) vchk[fill[cvn[p]]++] = c;
+}
+
+// checks ascending, a check's qubits ascending: the first qubit that meets an earlier one of its check in its own layer is refused
+int validate_qubit_layers(int n, int m_x, int m, const std::vector<int>& cptr, const std::vector<int>& cvn, int num_layers,
+                          const int32_t* layer_of)
+{
+    if (!layer_of) return fgnn_fail(FGNN_ERR_ARG, "layer_of is NULL");
+    if (num_layers < 1) return fgnn_fail(FGNN_ERR_ARG, "num_layers = " + std::to_string(num_layers) + " must be >= 1");
+    std::vector<int> count(num_layers, 0);
+    for (int v = 0; v < n; ++v) {
+        if (layer_of[v] < 0 || layer_of[v] >= num_layers)
+            return fgnn_fail(FGNN_ERR_ARG, "qubit " + std::to_string(v) + " has layer " + std::to_string(layer_of[v]) + ", outside [0, " +
+                                               std::to_string(num_layers) + ")");
+        count[layer_of[v]]++;
+    }
+    for (int l = 0; l < num_layers; ++l)
+        if (!count[l]) return fgnn_fail(FGNN_ERR_ARG, "layer " + std::to_string(l) + " is empty");
+    // stamp[l] = the last check with a qubit in layer l, owner[l] = that qubit: two of one check in one layer collide
+    std::vector<int> owner(num_layers, -1), stamp(num_layers, -1), row;
+    for (int c = 0; c < m; ++c) {
+        row.assign(cvn.begin() + cptr[c], cvn.begin() + cptr[c + 1]);
+        std::sort(row.begin(), row.end());
+        for (int v : row) {
+            const int l = layer_of[v];
+            if (stamp[l] == c && owner[l] != v)
+                return fgnn_fail(FGNN_ERR_ARG, "qubit " + std::to_string(owner[l]) + " and qubit " + std::to_string(v) + " of layer " +
+                                                   std::to_string(l) + " share " + check_name(c, m_x));
+            stamp[l] = c;
+            owner[l] = v;
+        }
+    }
+    return FGNN_OK;
+}
+
+void free_qubit_layers(const fgnn_graph* g)
+{
+    for (void*& p : g->qubit_layer_alloc)
+        if (p) {
+            (void)hipFree(p);  // waits for the launches that read it
+            p = nullptr;
+        }
+    g->num_qubit_layers = 0;
+    g->h_qubit_layer_of.clear();
+}
+
+// validates (a refused layering leaves the installed one in place), then replaces the five device tables
+int install_qubit_layers(const fgnn_graph* g, int num_layers, const int32_t* layer_of)
+{
+    const GraphDev& d = g->d;
+    std::vector<int> cptr, cvn;
+    int rc = check_qubits(d.n, d.m_x, d.m_z, d.E_x, g->h_chk[0].data(), g->h_var[0].data(), d.E_z, g->h_chk[1].data(),
+                          g->h_var[1].data(), cptr, cvn);
+    if (rc) return rc;
+    std::vector<int32_t> lay(d.n);
+    if (!layer_of) {
+        std::vector<int> vptr, vchk;
+        qubit_checks(d.n, d.m, cptr, cvn, vptr, vchk);
+        greedy_layers(d.m, d.n, vptr, vchk, lay.data(), &num_layers);  // the check layering with the two kinds of node exchanged
+    } else {
+        if ((rc = validate_qubit_layers(d.n, d.m_x, d.m, cptr, cvn, num_layers, layer_of))) return rc;
+        std::copy(layer_of, layer_of + d.n, lay.begin());
+    }
+    // the canonical edge lists are sorted by (qubit, check): slot e of a side is its e-th edge, and a check's row of the graph's
+    // check-major view (cslot) lists its edges by ascending qubit, which is the order check_qubits leaves them in
+    std::vector<int> cj((size_t)2 * d.E);
+    {
+        std::vector<int> fill(cptr.begin(), cptr.end() - 1);
+        for (int s = 0; s < 2; ++s)
+            for (int e = 0; e < (s ? d.E_z : d.E_x); ++e) {
+                const int c = (s ? d.m_x : 0) + g->h_chk[s][e];
+                const size_t slot = (size_t)e + (s ? d.E_x : 0);
+                cj[2 * slot] = c;
+                cj[2 * slot + 1] = fill[c]++ - cptr[c];
+            }
+    }
+    std::vector<int> vpx(d.n + 1, 0), vpz(d.n + 1, 0);
+    for (int v : g->h_var[0]) vpx[v + 1]++;
+    for (int v : g->h_var[1]) vpz[v + 1]++;
+    for (int v = 0; v < d.n; ++v) {
+        vpx[v + 1] += vpx[v];
+        vpz[v + 1] += vpz[v];
+    }
+    std::vector<int> qptr(num_layers + 1, 0), qub(d.n), eptr(num_layers + 1, 0), eslot(d.E);
+    for (int v = 0; v < d.n; ++v) qptr[lay[v] + 1]++;
+    for (int l = 0; l < num_layers; ++l) qptr[l + 1] += qptr[l];
+    {
+        std::vector<int> fill(qptr.begin(), qptr.end() - 1);
+        for (int v = 0; v < d.n; ++v) qub[fill[lay[v]]++] = v;
+    }
+    int ne = 0;
+    for (int l = 0; l < num_layers; ++l) {
+        for (int i = qptr[l]; i < qptr[l + 1]; ++i) {
+            const int v = qub[i];
+            for (int e = vpx[v]; e < vpx[v + 1]; ++e) eslot[ne++] = e;
+            for (int e = vpz[v]; e < vpz[v + 1]; ++e) eslot[ne++] = d.E_x + e;
+        }
+        eptr[l + 1] = ne;
+    }
+    fgnn_device_guard dg(g->device);
+    if (dg.err != hipSuccess) return fgnn_fail(FGNN_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(dg.err));
+    free_qubit_layers(g);
+    const std::vector<int>* tabs[5] = {&qptr, &qub, &eptr, &eslot, &cj};
+    for (int i = 0; i < 5; ++i) {
+        const size_t bytes = std::max<size_t>(tabs[i]->size(), 2) * sizeof(int);
+        hipError_t e = hipMalloc(&g->qubit_layer_alloc[i], bytes);
+        if (e == hipSuccess && !tabs[i]->empty())
+            e = hipMemcpy(g->qubit_layer_alloc[i], tabs[i]->data(), tabs[i]->size() * sizeof(int), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            free_qubit_layers(g);
+            return fgnn_fail(FGNN_ERR_HIP, std::string("uploading the qubit-layer tables: ") + hipGetErrorString(e));
+        }
+    }
+    g->num_qubit_layers = num_layers;
+    g->h_qubit_layer_of = lay;
+    return FGNN_OK;
+}
+
+}  // namespace
+
+extern "C" int fgnn_greedy_qubit_layers(int n, int m_x, int m_z, int nnz_x, const int32_t* chk_x, const int32_t* var_x, int nnz_z,
+                                        const int32_t* chk_z, const int32_t* var_z, int32_t* layer_of, int32_t* num_layers)
+{
+    if (!layer_of || !num_layers) return fgnn_fail(FGNN_ERR_ARG, "layer_of or num_layers is NULL");
+    std::vector<int> cptr, cvn, vptr, vchk;
+    const int rc = check_qubits(n, m_x, m_z, nnz_x, chk_x, var_x, nnz_z, chk_z, var_z, cptr, cvn);
+    if (rc) return rc;
+    qubit_checks(n, m_x + m_z, cptr, cvn, vptr, vchk);
+    greedy_layers(m_x + m_z, n, vptr, vchk, layer_of, num_layers);
+    return FGNN_OK;
+}
+
+extern "C" int fgnn_validate_qubit_layers(int n, int m_x, int m_z, int nnz_x, const int32_t* chk_x, const int32_t* var_x, int nnz_z,
+                                          const int32_t* chk_z, const int32_t* var_z, int num_layers, const int32_t* layer_of)
+{
+    std::vector<int> cptr, cvn;
+    const int rc = check_qubits(n, m_x, m_z, nnz_x, chk_x, var_x, nnz_z, chk_z, var_z, cptr, cvn);
+    if (rc) return rc;
+    return validate_qubit_layers(n, m_x, m_x + m_z, cptr, cvn, num_layers, layer_of);
+}
+
+extern "C" int fgnn_graph_set_qubit_layers(fgnn_graph* g, int num_layers, const int32_t* layer_of)
+{
+    if (!g) return fgnn_fail(FGNN_ERR_ARG, "graph is NULL");
+    if (g->host_only) return fgnn_fail(FGNN_ERR_STATE, "a host-only graph carries no device tables");
+    return install_qubit_layers(g, num_layers, layer_of);
+}
+
+extern "C" int fgnn_graph_qubit_layers(const fgnn_graph* g, int32_t* num_layers, int32_t* layer_of)
+{
+    if (!g || !num_layers) return fgnn_fail(FGNN_ERR_ARG, "NULL argument");
+    *num_layers = g->num_qubit_layers;
+    if (layer_of) std::copy(g->h_qubit_layer_of.begin(), g->h_qubit_layer_of.end(), layer_of);
+    return FGNN_OK;
+}
+
+int fgnn_graph_ensure_qubit_layers(const fgnn_graph* g)
+{
+    if (g->num_qubit_layers > 0) return FGNN_OK;
+    if (g->host_only) return fgnn_fail(FGNN_ERR_STATE, "a host-only graph carries no device tables");
+    return install_qubit_layers(g, 0, nullptr);
 }
 
 // Per-launch timing of the BP4 kernel: HIP events recorded on the launch stream immediately before and

@@ -71,6 +71,14 @@ struct fgnn_graph {
     mutable int num_bit_layers = 0;
     mutable std::vector<int32_t> h_bit_layer_of;
     mutable void* bit_layer_alloc[2] = {nullptr, nullptr};  // lay_cptr, lay_chk
+    // layering of the qubits for the schedule that is serial along qubits (fgnn_graph_set_qubit_layers; fgnn_mbp4_decode_serial installs
+    // the greedy one on a graph without), independent of the two above: layer_of per qubit on the host; on the device the qubits of
+    // layer l = lay_qub[lay_qptr[l] .. lay_qptr[l+1]) ascending, the slots of their edges = lay_slot[lay_eptr[l] .. lay_eptr[l+1]) in
+    // that order (a qubit's hx slots, then its hz slots), and for every slot e its check and its place in the check's row, slot_cj[e]
+    // = (combined check c, j with cslot[cptr[c] + j] = e)
+    mutable int num_qubit_layers = 0;
+    mutable std::vector<int32_t> h_qubit_layer_of;
+    mutable void* qubit_layer_alloc[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // lay_qptr, lay_qub, lay_eptr, lay_slot, slot_cj
     // solve tables of stabilizer inactivation (fgnn_si_decode builds them on its first call and keeps them): per group j = hz row j
     // the adjacent hx checks adj[aptr[j] .. aptr[j+1]), one 64-bit mask over them per bit of the group (xmask, in the order of the
     // hz edges of cvn) and one per consistency row cons[kptr[j] .. kptr[j+1]).  si_state: 0 not built, 1 uploaded, -1 a group is
@@ -251,6 +259,8 @@ LaunchGeom fgnn_geom(const fgnn_graph* g, int B);
 int fgnn_graph_ensure_layers(const fgnn_graph* g);
 // the same for the layering of side 0 alone (fgnn_bp2_decode_layered)
 int fgnn_graph_ensure_bit_layers(const fgnn_graph* g);
+// the same for the layering of the qubits (fgnn_mbp4_decode_serial)
+int fgnn_graph_ensure_qubit_layers(const fgnn_graph* g);
 
 // internal entry points with an optional slot->sample indirection (compacted sandwich rounds); bp4: flagged[b] (optional) = the
 // decision's syndrome differs from the measured one — the sandwich's flag test fused into the decoder's epilogue; llr_bound = what

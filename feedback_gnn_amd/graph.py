@@ -1069,14 +1069,51 @@ class TannerGraph:
         base / alpha_a); with `restart` every attempt after the first starts from zero messages; `llr_ch` [B, 3, n] or one
         `llr_const` for all three LLRs of every qubit; a syndrome that is None is all-zero.  Returns `(x_hat [B,n] uint8, z_hat [B,n]
         uint8, stats [B,4] int32 = found, the attempt of the last test, iterations, k of the last test)`."""
+        return self._mbp4_run(_lib.lib().fgnn_mbp4_decode, synd_x, synd_z, factors, owns, pre_iter, attempt_iter, cn_type, restart, llr_ch,
+                              llr_const, B)
+
+    def _mbp4_run(self, fn, synd_x, synd_z, factors, owns, pre_iter, attempt_iter, cn_type, restart, llr_ch, llr_const, B):
+        """The body of `mbp4_decode` and `mbp4_decode_serial`: ``fn`` is `fgnn_mbp4_decode` or `fgnn_mbp4_decode_serial` (one
+        signature)."""
         cn = self._cn(cn_type)
         factors, owns = self._tables_in(factors, owns)
         B, synd_x, synd_z, llr_ch = self._quaternary_in(synd_x, synd_z, llr_ch, B)
         xh, zh, stats = self._new_xzs(B)
-        check(_lib.lib().fgnn_mbp4_decode(self.handle, cn, len(factors), factors.ctypes.data, owns.ctypes.data,
-                                          int(pre_iter), int(attempt_iter), int(restart), _ptr(llr_ch), float(llr_const), _ptr(synd_x),
-                                          _ptr(synd_z), B, _ptr(xh), _ptr(zh), _ptr(stats), _stream(self.device)))
+        check(fn(self.handle, cn, len(factors), factors.ctypes.data, owns.ctypes.data, int(pre_iter), int(attempt_iter), int(restart),
+                 _ptr(llr_ch), float(llr_const), _ptr(synd_x), _ptr(synd_z), B, _ptr(xh), _ptr(zh), _ptr(stats), _stream(self.device)))
         return xh, zh, stats
+
+    # ---- serial schedule of MBP4: qubit by qubit -------------------------------------------------------------------
+    def set_qubit_layers(self, layer_of=None):
+        """Install the layering of `mbp4_decode_serial` (fgnn_graph_set_qubit_layers): ``layer_of`` [n] gives every qubit its layer
+        0 .. max; None installs the greedy layering.  No layer may be empty and no two qubits of a layer may share a check, on hx or on
+        hz: a ValueError names the offender, and the installed layering stays.  ``np.arange(n)`` is Kuo and Lai's literal order.
+        Independent of `set_layers` and `set_bit_layers`."""
+        if layer_of is None:
+            check(_lib.lib().fgnn_graph_set_qubit_layers(self.handle, 0, None))
+            return
+        lay = np.ascontiguousarray(layer_of, dtype=np.int32)
+        if lay.shape != (self.n,):
+            raise ValueError(f"layer_of must have shape ({self.n},), got {lay.shape}")
+        check(_lib.lib().fgnn_graph_set_qubit_layers(self.handle, int(lay.max()) + 1, _np_ptr(lay)))
+
+    def qubit_layers(self):
+        """(num_layers, layer_of [n] int32) of the installed qubit layering; (0, None) when there is none yet."""
+        num = C.c_int32(0)
+        check(_lib.lib().fgnn_graph_qubit_layers(self.handle, C.byref(num), None))
+        if num.value == 0:
+            return 0, None
+        lay = np.empty(self.n, np.int32)
+        check(_lib.lib().fgnn_graph_qubit_layers(self.handle, C.byref(num), _np_ptr(lay)))
+        return int(num.value), lay
+
+    def mbp4_decode_serial(self, synd_x, synd_z, factors, owns, pre_iter, attempt_iter, cn_type="minsum", restart=True, llr_ch=None,
+                           llr_const=0.0, B=None):
+        """`mbp4_decode` in Kuo and Lai's serial schedule (fgnn_mbp4_decode_serial): the qubits are visited layer by layer, and a qubit
+        sees the messages the qubits of the layers before it have just sent.  Same arguments and the same result; a graph without a
+        qubit layering gets the greedy one (`set_qubit_layers`)."""
+        return self._mbp4_run(_lib.lib().fgnn_mbp4_decode_serial, synd_x, synd_z, factors, owns, pre_iter, attempt_iter, cn_type, restart,
+                              llr_ch, llr_const, B)
 
     def dsbp4_decode(self, synd_x, synd_z, factors, owns, pre_iter, attempt_iter, cn_type="minsum", restart=True, llr_ch=None,
                      llr_const=0.0, synd_llr_x=None, synd_llr_z=None, gamma_x=float("inf"), gamma_z=float("inf"), B=None):

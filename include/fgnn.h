@@ -571,6 +571,55 @@ int fgnn_bp4aug_decode(const fgnn_graph* g, int cn_type, float normalization_fac
 int fgnn_mbp4_decode(const fgnn_graph* g, int cn_type, int num_attempts, const float* factor, const float* own, int pre_iter,
                      int attempt_iter, int restart, const float* llr_ch, float llr_const, const uint8_t* synd_x, const uint8_t* synd_z,
                      int B, uint8_t* x_hat, uint8_t* z_hat, int32_t* stats, void* stream);
+/* Layers of the qubits, for the schedule that is serial along qubits (fgnn_mbp4_decode_serial).  layer_of[n] with values in
+ * [0, num_layers), no layer empty, no two qubits of a layer sharing a check, on hx or on hz.  Arguments as fgnn_greedy_layers /
+ * fgnn_validate_layers: chk / var [nnz] are the edges of the two matrices; all pointers are host pointers; fgnn_greedy_qubit_layers and
+ * fgnn_validate_qubit_layers touch no device.  layer_of[v] = v with num_layers = n is always valid: the literal order 1 .. N of Kuo
+ * and Lai.
+ * fgnn_greedy_qubit_layers: qubits in ascending number, each into the lowest-numbered layer that holds no qubit sharing a check with it.
+ * fgnn_validate_qubit_layers: FGNN_OK, or FGNN_ERR_ARG with a message naming the qubit whose layer is out of range ("qubit 3 has layer
+ * 9, outside [0, 4)"), the empty layer ("layer 2 is empty"), or the two qubits of one layer and the check they share ("qubit 0 and
+ * qubit 5 of layer 1 share hx check 7", "... share hz check 2 (number 9)"): checks are scanned in ascending combined number (hx rows
+ * first), a check's qubits in ascending number, and the first qubit that meets an earlier one of its check in its own layer is named.
+ * fgnn_graph_set_qubit_layers: layer_of = NULL installs the greedy layering (num_layers is ignored); a caller's layering is validated as
+ * above and uploaded as a list of qubits per layer, ascending inside a layer; a refused layering leaves the installed one in place.
+ * fgnn_graph_qubit_layers: the installed layering (*num_layers = 0 and layer_of untouched when there is none; layer_of may be NULL).
+ * This layering is kept next to those of fgnn_graph_set_layers and fgnn_graph_set_bit_layers and is independent of them: installing
+ * one never changes another, and none changes any flooding decoder. */
+int fgnn_greedy_qubit_layers(int n, int m_x, int m_z, int nnz_x, const int32_t* chk_x, const int32_t* var_x, int nnz_z,
+                             const int32_t* chk_z, const int32_t* var_z, int32_t* layer_of, int32_t* num_layers);
+int fgnn_validate_qubit_layers(int n, int m_x, int m_z, int nnz_x, const int32_t* chk_x, const int32_t* var_x, int nnz_z,
+                               const int32_t* chk_z, const int32_t* var_z, int num_layers, const int32_t* layer_of);
+int fgnn_graph_set_qubit_layers(fgnn_graph* g, int num_layers, const int32_t* layer_of);
+int fgnn_graph_qubit_layers(const fgnn_graph* g, int32_t* num_layers, int32_t* layer_of);
+/* fgnn_mbp4_decode in Kuo and Lai's serial schedule: the qubits are visited one layer after the other, and a qubit sees the messages
+ * the qubits of the layers before it have just sent.  Arguments, argument checks, outputs, the four stats columns and the B = 0 case
+ * are those of fgnn_mbp4_decode; a graph without a qubit layering gets the greedy one (fgnn_graph_set_qubit_layers(g, 0, NULL)).  All
+ * arithmetic is float32 in the order written, and every routine (totals, the edge rule with own[a], the check rules, the decision) is
+ * the one of fgnn_mbp4_decode.  A codeword keeps two arrays in fgnn_bp4_decode's slot layout, nu (v->c) and mu (c->v):
+ *     mu = 0 on every edge;  nu = the qubit rule of fgnn_mbp4_decode on mu = 0 (all qubits);  its = 0
+ *     for a in 0 .. num_attempts-1:
+ *         T = pre_iter if a == 0 else attempt_iter
+ *         if restart and a > 0: mu = 0 and nu re-formed from it as above
+ *         for k in 1 .. T:
+ *             for l in 0 .. num_layers-1, for every qubit v of layer l (in any order: they share no check):
+ *                 for every edge e = (c, v):  mu_e = output e of check update cn_type on the CURRENT nu of c's edges with c's
+ *                                             syndrome bit, * factor[a]      (the bits the check update of fgnn_mbp4_decode writes to slot e)
+ *                 Sz, Sx, X, Y, Z from v's mu as fgnn_mbp4_decode forms them
+ *                 d_v = BP4's decision from (X, Z, Y);  x_v = d_v & 1;  z_v = d_v >> 1
+ *                 nu_e = the edge rule of fgnn_mbp4_decode with own_e = own[a] * mu_e, for every edge e of v
+ *             its += 1
+ *             if hz.x == synd_z and hx.z == synd_x:  found = 1;  stop
+ * With mu = 0 the product own[a] * mu_e is 0 for every own[a], so the first nu does not depend on the attempt.  On a graph for which
+ * one layer is valid (no two qubits share a check) this is fgnn_mbp4_decode bit for bit whenever num_attempts = 1, restart = 1 or all
+ * own[a] are equal; with restart = 0 and different weights the first check update of attempt a > 0 reads the nu formed with own[a-1]
+ * here and with own[a] there.  No result depends on the launch geometry or on the order of the qubits inside a layer.
+ *   nu, mu and a decision byte per qubit stay in LDS for the whole launch (2 E floats and n bytes per codeword, next to the two
+ * 64-float tables of factor and own); a graph they do not fit is refused (FGNN_ERR_ARG) with the bytes needed and the limit, there is
+ * no global-memory variant.  Runtime degrees only: there is no (3,3,6) instantiation. */
+int fgnn_mbp4_decode_serial(const fgnn_graph* g, int cn_type, int num_attempts, const float* factor, const float* own, int pre_iter,
+                            int attempt_iter, int restart, const float* llr_ch, float llr_const, const uint8_t* synd_x,
+                            const uint8_t* synd_z, int B, uint8_t* x_hat, uint8_t* z_hat, int32_t* stats, void* stream);
 /* Soft-syndrome BP4: data and syndrome errors decoded together (Kuo, Chern, Lai, "Decoding of quantum data-syndrome codes via belief
  * propagation", 2021; Raveendran et al., "Soft syndrome decoding of quantum LDPC codes for joint correction of data and syndrome
  * errors", 2022; Berent et al., "Analog information decoding of bosonic quantum LDPC codes", 2023), flooding schedule, with the attempt
