@@ -67,6 +67,22 @@ def alpha_list(alphas, max_alphas, num_iter, factor, cn_type):
     return alphas
 
 
+def schedule_in(schedule, layers, serial):
+    """The constructor checks of a decoder that runs 'flooding' or the serial schedule named ``serial`` ('layered', 'serial'); made
+    before the decoder builds a graph, so a refusal touches no device."""
+    if not isinstance(schedule, str) or schedule not in ("flooding", serial):
+        raise ValueError(f"schedule must be 'flooding' or {serial!r}, got {schedule!r}")
+    if layers is not None and schedule != serial:
+        raise ValueError(f"layers= belongs to schedule={serial!r}")
+
+
+def install_layering(graph, schedule, layers, serial, getter, setter):
+    """A decoder in the serial schedule hands ``layers`` to the graph's ``setter`` (`set_layers`, `set_bit_layers`, `set_qubit_layers`;
+    None: the greedy layering) — unless it names none and the graph, shared with another decoder, has one already (``getter``)."""
+    if schedule == serial and (layers is not None or getattr(graph, getter)()[0] == 0):
+        getattr(graph, setter)(layers)
+
+
 def alias(name):
     """A read/write property that is another attribute under a second (historical) name."""
     return property(lambda self: getattr(self, name), lambda self, value: setattr(self, name, value))

@@ -190,7 +190,7 @@ extern "C" int fgnn_bp2_decode_layered(const fgnn_graph* g, int cn_type, int num
     Bp2LayArgs a;
     a.B = B;
     a.num_iter = num_iter;
-    a.num_layers = g->num_bit_layers;
+    a.num_layers = g->bit_layers.num;
     a.tpc = L.tpc;
     a.cpb = L.cpb;
     a.lds_per_cw = (int)per_cw;
@@ -198,8 +198,8 @@ extern "C" int fgnn_bp2_decode_layered(const fgnn_graph* g, int cn_type, int num
     a.stop = stop;
     a.factor = normalization_factor;
     a.llr_const = llr_const;
-    a.lay_cptr = static_cast<const int*>(g->bit_layer_alloc[0]);
-    a.lay_chk = static_cast<const int*>(g->bit_layer_alloc[1]);
+    a.lay_cptr = g->bit_layers.table<int>(LAY_CPTR);
+    a.lay_chk = g->bit_layers.table<int>(LAY_CHK);
     a.llr_ch = llr_ch;
     a.synd = synd;
     a.soft_out = soft_out;

@@ -201,17 +201,17 @@ extern "C" int fgnn_bp4_decode_layered(const fgnn_graph* g, int cn_type, int num
     LayArgs a;
     a.B = B;
     a.num_iter = num_iter;
-    a.num_layers = g->num_layers;
+    a.num_layers = g->check_layers.num;
     a.tpc = L.tpc;
     a.cpb = L.cpb;
     a.lds_per_cw = (int)per_cw;
     a.t_off = (int)t_off;
     a.factor = normalization_factor;
     a.llr_const = llr_const;
-    a.lay_cptr = static_cast<const int*>(g->layer_alloc[0]);
-    a.lay_chk = static_cast<const int*>(g->layer_alloc[1]);
-    a.lay_eptr = static_cast<const int*>(g->layer_alloc[2]);
-    a.lay_edge = static_cast<const int2*>(g->layer_alloc[3]);
+    a.lay_cptr = g->check_layers.table<int>(LAY_CPTR);
+    a.lay_chk = g->check_layers.table<int>(LAY_CHK);
+    a.lay_eptr = g->check_layers.table<int>(LAY_EPTR);
+    a.lay_edge = g->check_layers.table<int2>(LAY_EDGE);
     a.llr_ch = llr_ch;
     a.synd_x = synd_x;
     a.synd_z = synd_z;

@@ -8,6 +8,7 @@
 #include <optional>
 
 #include "fgnn_internal.h"
+#include "fgnn_layers.h"
 
 static thread_local std::string g_err;
 void fgnn_set_error(const std::string& s) { g_err = s; }
@@ -226,6 +227,11 @@ static int graph_build(int n, int m_x, int m_z, int nnz_x, const int32_t* chk_x,
         fgnn_graph_destroy(g);
         return rc;
     }
+    g->h_vptr[0] = std::move(vptr_x);  // the layerings are built from these views (install_layers)
+    g->h_vptr[1] = std::move(vptr_z);
+    g->h_cptr = std::move(cptr);
+    g->h_cslot = std::move(cslot);
+    g->h_cvn = std::move(cvn);
     default_launch(g);
     *out = g;
     return FGNN_OK;
@@ -248,12 +254,7 @@ extern "C" void fgnn_graph_destroy(fgnn_graph* g)
     for (hipEvent_t e : g->prof_ev) (void)hipEventDestroy(e);
     for (void* p : g->basis_dev)
         if (p) (void)hipFree(p);
-    for (void* p : g->layer_alloc)
-        if (p) (void)hipFree(p);
-    for (void* p : g->bit_layer_alloc)
-        if (p) (void)hipFree(p);
-    for (void* p : g->qubit_layer_alloc)
-        if (p) (void)hipFree(p);
+    for (fgnn_layering* rec : {&g->check_layers, &g->bit_layers, &g->qubit_layers}) rec->free();
     for (void* p : g->si_alloc)
         if (p) (void)hipFree(p);
     for (void* p : g->allocs) (void)hipFree(p);
@@ -394,14 +395,17 @@ extern "C" int fgnn_check_rows(int n, int m_x, int m_z, int nnz_x, const int32_t
     return FGNN_OK;
 }
 
-// ---- layers of the serial schedule (fgnn_bp4_decode_layered) ------------------------------------------------------------------
+// ---- the layerings of the serial schedules: checks (fgnn_bp4_decode_layered), bits = hx alone (fgnn_bp2_decode_layered,
+// fgnn_relay_decode_layered) and qubits (fgnn_mbp4_decode_serial); the algorithms are in fgnn_layers.h --------------------------------
 namespace {
 
-// the qubits of every check, hx checks 0..m_x-1 then hz checks m_x..m_x+m_z-1, in the order of the edge lists
-int check_qubits(int n, int m_x, int m_z, int nnz_x, const int32_t* chk_x, const int32_t* var_x, int nnz_z, const int32_t* chk_z,
-                 const int32_t* var_z, std::vector<int>& ptr, std::vector<int>& vn)
+// a caller's edge lists check-major: the qubits of every check, hx checks 0..m_x-1 then hz checks m_x..m_x+m_z-1, in the order of the
+// lists; one_sided: one matrix alone (m_z = nnz_z = 0), whose nodes are bits
+int check_qubits(bool one_sided, int n, int m_x, int m_z, int nnz_x, const int32_t* chk_x, const int32_t* var_x, int nnz_z,
+                 const int32_t* chk_z, const int32_t* var_z, std::vector<int>& ptr, std::vector<int>& vn)
 {
-    if (n <= 0 || m_x <= 0 || m_z <= 0 || nnz_x < 0 || nnz_z < 0) return fgnn_fail(FGNN_ERR_ARG, "n, m_x and m_z must be positive");
+    if (n <= 0 || m_x <= 0 || (!one_sided && m_z <= 0) || nnz_x < 0 || nnz_z < 0)
+        return fgnn_fail(FGNN_ERR_ARG, one_sided ? "n and m must be positive" : "n, m_x and m_z must be positive");
     if ((nnz_x && (!chk_x || !var_x)) || (nnz_z && (!chk_z || !var_z))) return fgnn_fail(FGNN_ERR_ARG, "edge list is NULL");
     const int32_t* chk[2] = {chk_x, chk_z};
     const int32_t* var[2] = {var_x, var_z};
@@ -422,142 +426,94 @@ int check_qubits(int n, int m_x, int m_z, int nnz_x, const int32_t* chk_x, const
     return FGNN_OK;
 }
 
-std::string check_name(int c, int m_x)
+// fgnn_greedy_layers / _bit_layers / _qubit_layers: no graph, no device
+int greedy_of_lists(fgnn_layer_kind kind, int n, int m_x, int m_z, int nnz_x, const int32_t* chk_x, const int32_t* var_x, int nnz_z,
+                    const int32_t* chk_z, const int32_t* var_z, int32_t* layer_of, int32_t* num_layers)
 {
-    return c < m_x ? "hx check " + std::to_string(c) : "hz check " + std::to_string(c - m_x) + " (number " + std::to_string(c) + ")";
-}
-
-void greedy_layers(int n, int m, const std::vector<int>& ptr, const std::vector<int>& vn, int32_t* layer_of, int32_t* num_layers)
-{
-    std::vector<std::vector<int>> at(n);  // the layers that hold a check of qubit v
-    std::vector<int> seen;                // seen[l] == c + 1: layer l holds a check that shares a qubit with check c
-    int L = 0;
-    for (int c = 0; c < m; ++c) {
-        for (int p = ptr[c]; p < ptr[c + 1]; ++p)
-            for (int l : at[vn[p]]) seen[l] = c + 1;
-        int l = 0;
-        while (l < L && seen[l] == c + 1) ++l;
-        if (l == L) {
-            ++L;
-            seen.push_back(0);
-        }
-        layer_of[c] = l;
-        for (int p = ptr[c]; p < ptr[c + 1]; ++p) at[vn[p]].push_back(l);
-    }
-    *num_layers = L;
-}
-
-// bits: the layering of side 0 alone (fgnn_validate_bit_layers) — its checks are "check c" and what two of them share is a bit
-int validate_layers(int n, int m_x, int m, const std::vector<int>& ptr, const std::vector<int>& vn, int num_layers, const int32_t* layer_of,
-                    bool bits = false)
-{
-    const auto name = [&](int c) { return bits ? "check " + std::to_string(c) : check_name(c, m_x); };
-    if (!layer_of) return fgnn_fail(FGNN_ERR_ARG, "layer_of is NULL");
-    if (num_layers < 1) return fgnn_fail(FGNN_ERR_ARG, "num_layers = " + std::to_string(num_layers) + " must be >= 1");
-    std::vector<int> count(num_layers, 0);
-    for (int c = 0; c < m; ++c) {
-        if (layer_of[c] < 0 || layer_of[c] >= num_layers)
-            return fgnn_fail(FGNN_ERR_ARG, name(c) + " has layer " + std::to_string(layer_of[c]) + ", outside [0, " +
-                                               std::to_string(num_layers) + ")");
-        count[layer_of[c]]++;
-    }
-    for (int l = 0; l < num_layers; ++l)
-        if (!count[l]) return fgnn_fail(FGNN_ERR_ARG, "layer " + std::to_string(l) + " is empty");
-    // per qubit: the checks at it; stamp[l] = the last qubit with a check in layer l, owner[l] = that check: two in one layer collide
-    std::vector<int> owner(num_layers, -1), stamp(num_layers, -1);
-    std::vector<std::vector<int>> at(n);
-    for (int c = 0; c < m; ++c)
-        for (int p = ptr[c]; p < ptr[c + 1]; ++p) at[vn[p]].push_back(c);
-    for (int v = 0; v < n; ++v)
-        for (int c : at[v]) {
-            const int l = layer_of[c];
-            if (stamp[l] == v && owner[l] != c)
-                return fgnn_fail(FGNN_ERR_ARG, name(owner[l]) + " and " + name(c) + " of layer " + std::to_string(l) +
-                                                   (bits ? " share bit " : " share qubit ") + std::to_string(v));
-            stamp[l] = v;
-            owner[l] = c;
-        }
+    if (!layer_of || !num_layers) return fgnn_fail(FGNN_ERR_ARG, "layer_of or num_layers is NULL");
+    std::vector<int> cptr, cvn;
+    if (int rc = check_qubits(kind == LAYER_BITS, n, m_x, m_z, nnz_x, chk_x, var_x, nnz_z, chk_z, var_z, cptr, cvn)) return rc;
+    fgnn_layers::greedy(kind, n, m_x + m_z, cptr, cvn, layer_of, num_layers);
     return FGNN_OK;
 }
 
-void free_layers(const fgnn_graph* g)
+// fgnn_validate_layers / _bit_layers / _qubit_layers: no graph, no device
+int validate_of_lists(fgnn_layer_kind kind, int n, int m_x, int m_z, int nnz_x, const int32_t* chk_x, const int32_t* var_x, int nnz_z,
+                      const int32_t* chk_z, const int32_t* var_z, int num_layers, const int32_t* layer_of)
 {
-    for (void*& p : g->layer_alloc)
-        if (p) {
-            (void)hipFree(p);  // waits for the launches that read it
-            p = nullptr;
-        }
-    g->num_layers = 0;
-    g->h_layer_of.clear();
+    std::vector<int> cptr, cvn;
+    if (int rc = check_qubits(kind == LAYER_BITS, n, m_x, m_z, nnz_x, chk_x, var_x, nnz_z, chk_z, var_z, cptr, cvn)) return rc;
+    const std::string refused = fgnn_layers::validate(kind, n, m_x, m_x + m_z, cptr, cvn, num_layers, layer_of);
+    return refused.empty() ? FGNN_OK : fgnn_fail(FGNN_ERR_ARG, refused);
 }
 
-int install_layers(const fgnn_graph* g, int num_layers, const int32_t* layer_of)
+fgnn_layering& layering(const fgnn_graph* g, fgnn_layer_kind kind)
 {
+    return kind == LAYER_CHECKS ? g->check_layers : kind == LAYER_BITS ? g->bit_layers : g->qubit_layers;
+}
+
+// The greedy layering (layer_of NULL) or the caller's, validated — a refused one leaves the installed layering in place —, then the
+// kind's tables replace the installed ones on the device.  Everything comes from the host views graph_build kept.
+int install_layers(const fgnn_graph* g, fgnn_layer_kind kind, int num_layers, const int32_t* layer_of)
+{
+    namespace FL = fgnn_layers;
+    static const char* const tables_of[] = {"layer", "bit-layer", "qubit-layer"};
+    if (g->host_only) return fgnn_fail(FGNN_ERR_STATE, "a host-only graph carries no device tables");
     const GraphDev& d = g->d;
-    std::vector<int> ptr, vn;
-    int rc = check_qubits(d.n, d.m_x, d.m_z, d.E_x, g->h_chk[0].data(), g->h_var[0].data(), d.E_z, g->h_chk[1].data(),
-                          g->h_var[1].data(), ptr, vn);
-    if (rc) return rc;
-    std::vector<int32_t> lay(d.m);
+    const int m = kind == LAYER_BITS ? d.m_x : d.m, items = FL::item_count(kind, d.n, m);
+    std::vector<int32_t> lay(items);
     if (!layer_of) {
-        greedy_layers(d.n, d.m, ptr, vn, lay.data(), &num_layers);
+        FL::greedy(kind, d.n, m, g->h_cptr, g->h_cvn, lay.data(), &num_layers);
     } else {
-        if ((rc = validate_layers(d.n, d.m_x, d.m, ptr, vn, num_layers, layer_of))) return rc;
-        std::copy(layer_of, layer_of + d.m, lay.begin());
+        const std::string refused = FL::validate(kind, d.n, d.m_x, m, g->h_cptr, g->h_cvn, num_layers, layer_of);
+        if (!refused.empty()) return fgnn_fail(FGNN_ERR_ARG, refused);
+        lay.assign(layer_of, layer_of + items);
     }
-    // the device tables, from the graph's own check-major view: a check's edges in ascending qubit order, slot = VN-major message slot
-    std::vector<int> cptr(d.m + 1, 0), cslot(d.E), cvn(d.E);
-    {
-        std::vector<int> vptr[2];
-        for (int s = 0; s < 2; ++s) {
-            vptr[s].assign(d.n + 1, 0);
-            for (int v : g->h_var[s]) vptr[s][v + 1]++;
-            for (int v = 0; v < d.n; ++v) vptr[s][v + 1] += vptr[s][v];
-        }
-        for (int s = 0; s < 2; ++s)
-            for (int c : g->h_chk[s]) cptr[(s ? d.m_x : 0) + c + 1]++;
-        for (int c = 0; c < d.m; ++c) cptr[c + 1] += cptr[c];
-        std::vector<int> fill(cptr.begin(), cptr.end() - 1);
-        for (int s = 0; s < 2; ++s)
-            for (int e = 0; e < (s ? d.E_z : d.E_x); ++e) {  // the canonical lists are sorted by (qubit, check): slot e of the side
-                const int pos = fill[(s ? d.m_x : 0) + g->h_chk[s][e]]++;
-                cslot[pos] = e + (s ? d.E_x : 0);
-                cvn[pos] = g->h_var[s][e];
-            }
-    }
-    std::vector<int> lcptr(num_layers + 1, 0), lchk(d.m), leptr(num_layers + 1, 0), ledge((size_t)2 * d.E);
-    for (int c = 0; c < d.m; ++c) lcptr[lay[c] + 1]++;
-    for (int l = 0; l < num_layers; ++l) lcptr[l + 1] += lcptr[l];
-    {
-        std::vector<int> fill(lcptr.begin(), lcptr.end() - 1);
-        for (int c = 0; c < d.m; ++c) lchk[fill[lay[c]]++] = c;
-    }
-    int ne = 0;
-    for (int l = 0; l < num_layers; ++l) {
-        for (int i = lcptr[l]; i < lcptr[l + 1]; ++i)
-            for (int p = cptr[lchk[i]]; p < cptr[lchk[i] + 1]; ++p, ++ne) {
-                ledge[2 * (size_t)ne] = cslot[p];
-                ledge[2 * (size_t)ne + 1] = cvn[p];
-            }
-        leptr[l + 1] = ne;
-    }
+    std::vector<std::vector<int>> tabs(kind == LAYER_CHECKS ? 4 : kind == LAYER_BITS ? 2 : 5);  // in the order of the LAY_* slots
+    FL::bucket_by_layer(items, num_layers, lay.data(), tabs[0], tabs[1]);
+    if (kind == LAYER_CHECKS)
+        FL::check_layer_tables(tabs[LAY_CPTR], tabs[LAY_CHK], g->h_cptr, g->h_cslot, g->h_cvn, tabs[LAY_EPTR], tabs[LAY_EDGE]);
+    if (kind == LAYER_QUBITS)
+        FL::qubit_layer_tables(tabs[LAY_QPTR], tabs[LAY_QUB], g->h_vptr[0], g->h_vptr[1], g->h_cptr, g->h_cslot, tabs[LAY_QEPTR],
+                               tabs[LAY_SLOT], tabs[LAY_SLOT_CJ]);
     fgnn_device_guard dg(g->device);
     if (dg.err != hipSuccess) return fgnn_fail(FGNN_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(dg.err));
-    free_layers(g);
-    const std::vector<int>* tabs[4] = {&lcptr, &lchk, &leptr, &ledge};
-    for (int i = 0; i < 4; ++i) {
-        const size_t bytes = std::max<size_t>(tabs[i]->size(), 2) * sizeof(int);
-        hipError_t e = hipMalloc(&g->layer_alloc[i], bytes);
-        if (e == hipSuccess && !tabs[i]->empty())
-            e = hipMemcpy(g->layer_alloc[i], tabs[i]->data(), tabs[i]->size() * sizeof(int), hipMemcpyHostToDevice);
+    fgnn_layering& rec = layering(g, kind);
+    rec.free();
+    for (const std::vector<int>& t : tabs) {
+        void* p = nullptr;
+        hipError_t e = hipMalloc(&p, std::max<size_t>(t.size(), 2) * sizeof(int));
+        if (e == hipSuccess) {
+            rec.dev.push_back(p);
+            if (!t.empty()) e = hipMemcpy(p, t.data(), t.size() * sizeof(int), hipMemcpyHostToDevice);
+        }
         if (e != hipSuccess) {
-            free_layers(g);
-            return fgnn_fail(FGNN_ERR_HIP, std::string("uploading the layer tables: ") + hipGetErrorString(e));
+            rec.free();
+            return fgnn_fail(FGNN_ERR_HIP, std::string("uploading the ") + tables_of[kind] + " tables: " + hipGetErrorString(e));
         }
     }
-    g->num_layers = num_layers;
-    g->h_layer_of = lay;
+    rec.num = num_layers;
+    rec.layer_of = lay;
     return FGNN_OK;
+}
+
+int set_layers(fgnn_graph* g, fgnn_layer_kind kind, int num_layers, const int32_t* layer_of)
+{
+    return g ? install_layers(g, kind, num_layers, layer_of) : fgnn_fail(FGNN_ERR_ARG, "graph is NULL");
+}
+
+int get_layers(const fgnn_graph* g, fgnn_layer_kind kind, int32_t* num_layers, int32_t* layer_of)
+{
+    if (!g || !num_layers) return fgnn_fail(FGNN_ERR_ARG, "NULL argument");
+    const fgnn_layering& rec = layering(g, kind);
+    *num_layers = rec.num;
+    if (layer_of) std::copy(rec.layer_of.begin(), rec.layer_of.end(), layer_of);
+    return FGNN_OK;
+}
+
+int ensure_layers(const fgnn_graph* g, fgnn_layer_kind kind)
+{
+    return layering(g, kind).num > 0 ? FGNN_OK : install_layers(g, kind, 0, nullptr);
 }
 
 }  // namespace
@@ -565,326 +521,66 @@ int install_layers(const fgnn_graph* g, int num_layers, const int32_t* layer_of)
 extern "C" int fgnn_greedy_layers(int n, int m_x, int m_z, int nnz_x, const int32_t* chk_x, const int32_t* var_x, int nnz_z,
                                   const int32_t* chk_z, const int32_t* var_z, int32_t* layer_of, int32_t* num_layers)
 {
-    if (!layer_of || !num_layers) return fgnn_fail(FGNN_ERR_ARG, "layer_of or num_layers is NULL");
-    std::vector<int> ptr, vn;
-    const int rc = check_qubits(n, m_x, m_z, nnz_x, chk_x, var_x, nnz_z, chk_z, var_z, ptr, vn);
-    if (rc) return rc;
-    greedy_layers(n, m_x + m_z, ptr, vn, layer_of, num_layers);
-    return FGNN_OK;
+    return greedy_of_lists(LAYER_CHECKS, n, m_x, m_z, nnz_x, chk_x, var_x, nnz_z, chk_z, var_z, layer_of, num_layers);
 }
 
 extern "C" int fgnn_validate_layers(int n, int m_x, int m_z, int nnz_x, const int32_t* chk_x, const int32_t* var_x, int nnz_z,
                                     const int32_t* chk_z, const int32_t* var_z, int num_layers, const int32_t* layer_of)
 {
-    std::vector<int> ptr, vn;
-    const int rc = check_qubits(n, m_x, m_z, nnz_x, chk_x, var_x, nnz_z, chk_z, var_z, ptr, vn);
-    if (rc) return rc;
-    return validate_layers(n, m_x, m_x + m_z, ptr, vn, num_layers, layer_of);
+    return validate_of_lists(LAYER_CHECKS, n, m_x, m_z, nnz_x, chk_x, var_x, nnz_z, chk_z, var_z, num_layers, layer_of);
 }
-
-extern "C" int fgnn_graph_set_layers(fgnn_graph* g, int num_layers, const int32_t* layer_of)
-{
-    if (!g) return fgnn_fail(FGNN_ERR_ARG, "graph is NULL");
-    if (g->host_only) return fgnn_fail(FGNN_ERR_STATE, "a host-only graph carries no device tables");
-    return install_layers(g, num_layers, layer_of);
-}
-
-extern "C" int fgnn_graph_layers(const fgnn_graph* g, int32_t* num_layers, int32_t* layer_of)
-{
-    if (!g || !num_layers) return fgnn_fail(FGNN_ERR_ARG, "NULL argument");
-    *num_layers = g->num_layers;
-    if (layer_of) std::copy(g->h_layer_of.begin(), g->h_layer_of.end(), layer_of);
-    return FGNN_OK;
-}
-
-int fgnn_graph_ensure_layers(const fgnn_graph* g)
-{
-    if (g->num_layers > 0) return FGNN_OK;
-    if (g->host_only) return fgnn_fail(FGNN_ERR_STATE, "a host-only graph carries no device tables");
-    return install_layers(g, 0, nullptr);
-}
-
-// ---- layers of side 0 alone, for the binary serial schedule (fgnn_bp2_decode_layered) ----------------------------------------------
-namespace {
-
-// the bits of every check of one matrix, in the order of the edge list
-int check_bits(int n, int m, int nnz, const int32_t* chk, const int32_t* var, std::vector<int>& ptr, std::vector<int>& vn)
-{
-    if (n <= 0 || m <= 0 || nnz < 0) return fgnn_fail(FGNN_ERR_ARG, "n and m must be positive");
-    if (nnz && (!chk || !var)) return fgnn_fail(FGNN_ERR_ARG, "edge list is NULL");
-    ptr.assign(m + 1, 0);
-    for (int i = 0; i < nnz; ++i) {
-        if (chk[i] < 0 || chk[i] >= m || var[i] < 0 || var[i] >= n) return fgnn_fail(FGNN_ERR_ARG, "edge index out of range");
-        ptr[chk[i] + 1]++;
-    }
-    for (int c = 0; c < m; ++c) ptr[c + 1] += ptr[c];
-    vn.resize(ptr[m]);
-    std::vector<int> fill(ptr.begin(), ptr.end() - 1);
-    for (int i = 0; i < nnz; ++i) vn[fill[chk[i]]++] = var[i];
-    return FGNN_OK;
-}
-
-// validates (a refused layering leaves the installed one in place), then replaces the two device tables
-int install_bit_layers(const fgnn_graph* g, int num_layers, const int32_t* layer_of)
-{
-    const GraphDev& d = g->d;
-    std::vector<int> ptr, vn;
-    int rc = check_bits(d.n, d.m_x, d.E_x, g->h_chk[0].data(), g->h_var[0].data(), ptr, vn);
-    if (rc) return rc;
-    std::vector<int32_t> lay(d.m_x);
-    if (!layer_of) {
-        greedy_layers(d.n, d.m_x, ptr, vn, lay.data(), &num_layers);
-    } else {
-        if ((rc = validate_layers(d.n, d.m_x, d.m_x, ptr, vn, num_layers, layer_of, true))) return rc;
-        std::copy(layer_of, layer_of + d.m_x, lay.begin());
-    }
-    std::vector<int> lcptr(num_layers + 1, 0), lchk(d.m_x);
-    for (int c = 0; c < d.m_x; ++c) lcptr[lay[c] + 1]++;
-    for (int l = 0; l < num_layers; ++l) lcptr[l + 1] += lcptr[l];
-    std::vector<int> fill(lcptr.begin(), lcptr.end() - 1);
-    for (int c = 0; c < d.m_x; ++c) lchk[fill[lay[c]]++] = c;
-    fgnn_device_guard dg(g->device);
-    if (dg.err != hipSuccess) return fgnn_fail(FGNN_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(dg.err));
-    const auto drop = [&] {
-        for (void*& p : g->bit_layer_alloc)
-            if (p) {
-                (void)hipFree(p);  // waits for the launches that read it
-                p = nullptr;
-            }
-        g->num_bit_layers = 0;
-        g->h_bit_layer_of.clear();
-    };
-    drop();
-    const std::vector<int>* tabs[2] = {&lcptr, &lchk};
-    for (int i = 0; i < 2; ++i) {
-        hipError_t e = hipMalloc(&g->bit_layer_alloc[i], tabs[i]->size() * sizeof(int));
-        if (e == hipSuccess) e = hipMemcpy(g->bit_layer_alloc[i], tabs[i]->data(), tabs[i]->size() * sizeof(int), hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            drop();
-            return fgnn_fail(FGNN_ERR_HIP, std::string("uploading the bit-layer tables: ") + hipGetErrorString(e));
-        }
-    }
-    g->num_bit_layers = num_layers;
-    g->h_bit_layer_of = lay;
-    return FGNN_OK;
-}
-
-}  // namespace
 
 extern "C" int fgnn_greedy_bit_layers(int n, int m, int nnz, const int32_t* chk, const int32_t* var, int32_t* layer_of, int32_t* num_layers)
 {
-    if (!layer_of || !num_layers) return fgnn_fail(FGNN_ERR_ARG, "layer_of or num_layers is NULL");
-    std::vector<int> ptr, vn;
-    const int rc = check_bits(n, m, nnz, chk, var, ptr, vn);
-    if (rc) return rc;
-    greedy_layers(n, m, ptr, vn, layer_of, num_layers);
-    return FGNN_OK;
+    return greedy_of_lists(LAYER_BITS, n, m, 0, nnz, chk, var, 0, nullptr, nullptr, layer_of, num_layers);
 }
 
 extern "C" int fgnn_validate_bit_layers(int n, int m, int nnz, const int32_t* chk, const int32_t* var, int num_layers, const int32_t* layer_of)
 {
-    std::vector<int> ptr, vn;
-    const int rc = check_bits(n, m, nnz, chk, var, ptr, vn);
-    if (rc) return rc;
-    return validate_layers(n, m, m, ptr, vn, num_layers, layer_of, true);
+    return validate_of_lists(LAYER_BITS, n, m, 0, nnz, chk, var, 0, nullptr, nullptr, num_layers, layer_of);
 }
-
-extern "C" int fgnn_graph_set_bit_layers(fgnn_graph* g, int num_layers, const int32_t* layer_of)
-{
-    if (!g) return fgnn_fail(FGNN_ERR_ARG, "graph is NULL");
-    if (g->host_only) return fgnn_fail(FGNN_ERR_STATE, "a host-only graph carries no device tables");
-    return install_bit_layers(g, num_layers, layer_of);
-}
-
-extern "C" int fgnn_graph_bit_layers(const fgnn_graph* g, int32_t* num_layers, int32_t* layer_of)
-{
-    if (!g || !num_layers) return fgnn_fail(FGNN_ERR_ARG, "NULL argument");
-    *num_layers = g->num_bit_layers;
-    if (layer_of) std::copy(g->h_bit_layer_of.begin(), g->h_bit_layer_of.end(), layer_of);
-    return FGNN_OK;
-}
-
-int fgnn_graph_ensure_bit_layers(const fgnn_graph* g)
-{
-    if (g->num_bit_layers > 0) return FGNN_OK;
-    if (g->host_only) return fgnn_fail(FGNN_ERR_STATE, "a host-only graph carries no device tables");
-    return install_bit_layers(g, 0, nullptr);
-}
-
-// ---- layers of the qubits, for the schedule that is serial along qubits (fgnn_mbp4_decode_serial) -------------------------------------
-namespace {
-
-// the checks of every qubit (combined numbers, hx checks first), ascending, from the qubits of every check
-void qubit_checks(int n, int m, const std::vector<int>& cptr, const std::vector<int>& cvn, std::vector<int>& vptr, std::vector<int>& vchk)
-{
-    vptr.assign(n + 1, 0);
-    for (int v : cvn) vptr[v + 1]++;
-    for (int v = 0; v < n; ++v) vptr[v + 1] += vptr[v];
-    vchk.resize(cvn.size());
-    std::vector<int> fill(vptr.begin(), vptr.end() - 1);
-    for (int c = 0; c < m; ++c)
-        for (int p = cptr[c]; p < cptr[c + 1]; ++p) vchk[fill[cvn[p]]++] = c;
-}
-
-// checks ascending, a check's qubits ascending: the first qubit that meets an earlier one of its check in its own layer is refused
-int validate_qubit_layers(int n, int m_x, int m, const std::vector<int>& cptr, const std::vector<int>& cvn, int num_layers,
-                          const int32_t* layer_of)
-{
-    if (!layer_of) return fgnn_fail(FGNN_ERR_ARG, "layer_of is NULL");
-    if (num_layers < 1) return fgnn_fail(FGNN_ERR_ARG, "num_layers = " + std::to_string(num_layers) + " must be >= 1");
-    std::vector<int> count(num_layers, 0);
-    for (int v = 0; v < n; ++v) {
-        if (layer_of[v] < 0 || layer_of[v] >= num_layers)
-            return fgnn_fail(FGNN_ERR_ARG, "qubit " + std::to_string(v) + " has layer " + std::to_string(layer_of[v]) + ", outside [0, " +
-                                               std::to_string(num_layers) + ")");
-        count[layer_of[v]]++;
-    }
-    for (int l = 0; l < num_layers; ++l)
-        if (!count[l]) return fgnn_fail(FGNN_ERR_ARG, "layer " + std::to_string(l) + " is empty");
-    // stamp[l] = the last check with a qubit in layer l, owner[l] = that qubit: two of one check in one layer collide
-    std::vector<int> owner(num_layers, -1), stamp(num_layers, -1), row;
-    for (int c = 0; c < m; ++c) {
-        row.assign(cvn.begin() + cptr[c], cvn.begin() + cptr[c + 1]);
-        std::sort(row.begin(), row.end());
-        for (int v : row) {
-            const int l = layer_of[v];
-            if (stamp[l] == c && owner[l] != v)
-                return fgnn_fail(FGNN_ERR_ARG, "qubit " + std::to_string(owner[l]) + " and qubit " + std::to_string(v) + " of layer " +
-                                                   std::to_string(l) + " share " + check_name(c, m_x));
-            stamp[l] = c;
-            owner[l] = v;
-        }
-    }
-    return FGNN_OK;
-}
-
-void free_qubit_layers(const fgnn_graph* g)
-{
-    for (void*& p : g->qubit_layer_alloc)
-        if (p) {
-            (void)hipFree(p);  // waits for the launches that read it
-            p = nullptr;
-        }
-    g->num_qubit_layers = 0;
-    g->h_qubit_layer_of.clear();
-}
-
-// validates (a refused layering leaves the installed one in place), then replaces the five device tables
-int install_qubit_layers(const fgnn_graph* g, int num_layers, const int32_t* layer_of)
-{
-    const GraphDev& d = g->d;
-    std::vector<int> cptr, cvn;
-    int rc = check_qubits(d.n, d.m_x, d.m_z, d.E_x, g->h_chk[0].data(), g->h_var[0].data(), d.E_z, g->h_chk[1].data(),
-                          g->h_var[1].data(), cptr, cvn);
-    if (rc) return rc;
-    std::vector<int32_t> lay(d.n);
-    if (!layer_of) {
-        std::vector<int> vptr, vchk;
-        qubit_checks(d.n, d.m, cptr, cvn, vptr, vchk);
-        greedy_layers(d.m, d.n, vptr, vchk, lay.data(), &num_layers);  // the check layering with the two kinds of node exchanged
-    } else {
-        if ((rc = validate_qubit_layers(d.n, d.m_x, d.m, cptr, cvn, num_layers, layer_of))) return rc;
-        std::copy(layer_of, layer_of + d.n, lay.begin());
-    }
-    // the canonical edge lists are sorted by (qubit, check): slot e of a side is its e-th edge, and a check's row of the graph's
-    // check-major view (cslot) lists its edges by ascending qubit, which is the order check_qubits leaves them in
-    std::vector<int> cj((size_t)2 * d.E);
-    {
-        std::vector<int> fill(cptr.begin(), cptr.end() - 1);
-        for (int s = 0; s < 2; ++s)
-            for (int e = 0; e < (s ? d.E_z : d.E_x); ++e) {
-                const int c = (s ? d.m_x : 0) + g->h_chk[s][e];
-                const size_t slot = (size_t)e + (s ? d.E_x : 0);
-                cj[2 * slot] = c;
-                cj[2 * slot + 1] = fill[c]++ - cptr[c];
-            }
-    }
-    std::vector<int> vpx(d.n + 1, 0), vpz(d.n + 1, 0);
-    for (int v : g->h_var[0]) vpx[v + 1]++;
-    for (int v : g->h_var[1]) vpz[v + 1]++;
-    for (int v = 0; v < d.n; ++v) {
-        vpx[v + 1] += vpx[v];
-        vpz[v + 1] += vpz[v];
-    }
-    std::vector<int> qptr(num_layers + 1, 0), qub(d.n), eptr(num_layers + 1, 0), eslot(d.E);
-    for (int v = 0; v < d.n; ++v) qptr[lay[v] + 1]++;
-    for (int l = 0; l < num_layers; ++l) qptr[l + 1] += qptr[l];
-    {
-        std::vector<int> fill(qptr.begin(), qptr.end() - 1);
-        for (int v = 0; v < d.n; ++v) qub[fill[lay[v]]++] = v;
-    }
-    int ne = 0;
-    for (int l = 0; l < num_layers; ++l) {
-        for (int i = qptr[l]; i < qptr[l + 1]; ++i) {
-            const int v = qub[i];
-            for (int e = vpx[v]; e < vpx[v + 1]; ++e) eslot[ne++] = e;
-            for (int e = vpz[v]; e < vpz[v + 1]; ++e) eslot[ne++] = d.E_x + e;
-        }
-        eptr[l + 1] = ne;
-    }
-    fgnn_device_guard dg(g->device);
-    if (dg.err != hipSuccess) return fgnn_fail(FGNN_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(dg.err));
-    free_qubit_layers(g);
-    const std::vector<int>* tabs[5] = {&qptr, &qub, &eptr, &eslot, &cj};
-    for (int i = 0; i < 5; ++i) {
-        const size_t bytes = std::max<size_t>(tabs[i]->size(), 2) * sizeof(int);
-        hipError_t e = hipMalloc(&g->qubit_layer_alloc[i], bytes);
-        if (e == hipSuccess && !tabs[i]->empty())
-            e = hipMemcpy(g->qubit_layer_alloc[i], tabs[i]->data(), tabs[i]->size() * sizeof(int), hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            free_qubit_layers(g);
-            return fgnn_fail(FGNN_ERR_HIP, std::string("uploading the qubit-layer tables: ") + hipGetErrorString(e));
-        }
-    }
-    g->num_qubit_layers = num_layers;
-    g->h_qubit_layer_of = lay;
-    return FGNN_OK;
-}
-
-}  // namespace
 
 extern "C" int fgnn_greedy_qubit_layers(int n, int m_x, int m_z, int nnz_x, const int32_t* chk_x, const int32_t* var_x, int nnz_z,
                                         const int32_t* chk_z, const int32_t* var_z, int32_t* layer_of, int32_t* num_layers)
 {
-    if (!layer_of || !num_layers) return fgnn_fail(FGNN_ERR_ARG, "layer_of or num_layers is NULL");
-    std::vector<int> cptr, cvn, vptr, vchk;
-    const int rc = check_qubits(n, m_x, m_z, nnz_x, chk_x, var_x, nnz_z, chk_z, var_z, cptr, cvn);
-    if (rc) return rc;
-    qubit_checks(n, m_x + m_z, cptr, cvn, vptr, vchk);
-    greedy_layers(m_x + m_z, n, vptr, vchk, layer_of, num_layers);
-    return FGNN_OK;
+    return greedy_of_lists(LAYER_QUBITS, n, m_x, m_z, nnz_x, chk_x, var_x, nnz_z, chk_z, var_z, layer_of, num_layers);
 }
 
 extern "C" int fgnn_validate_qubit_layers(int n, int m_x, int m_z, int nnz_x, const int32_t* chk_x, const int32_t* var_x, int nnz_z,
                                           const int32_t* chk_z, const int32_t* var_z, int num_layers, const int32_t* layer_of)
 {
-    std::vector<int> cptr, cvn;
-    const int rc = check_qubits(n, m_x, m_z, nnz_x, chk_x, var_x, nnz_z, chk_z, var_z, cptr, cvn);
-    if (rc) return rc;
-    return validate_qubit_layers(n, m_x, m_x + m_z, cptr, cvn, num_layers, layer_of);
+    return validate_of_lists(LAYER_QUBITS, n, m_x, m_z, nnz_x, chk_x, var_x, nnz_z, chk_z, var_z, num_layers, layer_of);
 }
 
+extern "C" int fgnn_graph_set_layers(fgnn_graph* g, int num_layers, const int32_t* layer_of)
+{
+    return set_layers(g, LAYER_CHECKS, num_layers, layer_of);
+}
+extern "C" int fgnn_graph_set_bit_layers(fgnn_graph* g, int num_layers, const int32_t* layer_of)
+{
+    return set_layers(g, LAYER_BITS, num_layers, layer_of);
+}
 extern "C" int fgnn_graph_set_qubit_layers(fgnn_graph* g, int num_layers, const int32_t* layer_of)
 {
-    if (!g) return fgnn_fail(FGNN_ERR_ARG, "graph is NULL");
-    if (g->host_only) return fgnn_fail(FGNN_ERR_STATE, "a host-only graph carries no device tables");
-    return install_qubit_layers(g, num_layers, layer_of);
+    return set_layers(g, LAYER_QUBITS, num_layers, layer_of);
 }
 
+extern "C" int fgnn_graph_layers(const fgnn_graph* g, int32_t* num_layers, int32_t* layer_of)
+{
+    return get_layers(g, LAYER_CHECKS, num_layers, layer_of);
+}
+extern "C" int fgnn_graph_bit_layers(const fgnn_graph* g, int32_t* num_layers, int32_t* layer_of)
+{
+    return get_layers(g, LAYER_BITS, num_layers, layer_of);
+}
 extern "C" int fgnn_graph_qubit_layers(const fgnn_graph* g, int32_t* num_layers, int32_t* layer_of)
 {
-    if (!g || !num_layers) return fgnn_fail(FGNN_ERR_ARG, "NULL argument");
-    *num_layers = g->num_qubit_layers;
-    if (layer_of) std::copy(g->h_qubit_layer_of.begin(), g->h_qubit_layer_of.end(), layer_of);
-    return FGNN_OK;
+    return get_layers(g, LAYER_QUBITS, num_layers, layer_of);
 }
 
-int fgnn_graph_ensure_qubit_layers(const fgnn_graph* g)
-{
-    if (g->num_qubit_layers > 0) return FGNN_OK;
-    if (g->host_only) return fgnn_fail(FGNN_ERR_STATE, "a host-only graph carries no device tables");
-    return install_qubit_layers(g, 0, nullptr);
-}
+int fgnn_graph_ensure_layers(const fgnn_graph* g) { return ensure_layers(g, LAYER_CHECKS); }
+int fgnn_graph_ensure_bit_layers(const fgnn_graph* g) { return ensure_layers(g, LAYER_BITS); }
+int fgnn_graph_ensure_qubit_layers(const fgnn_graph* g) { return ensure_layers(g, LAYER_QUBITS); }
 
 // Per-launch timing of the BP4 kernel: HIP events recorded on the launch stream immediately before and
 // after each bp4 launch (inside fgnn_bp4_decode and inside fgnn_sandwich_decode), read back afterwards.

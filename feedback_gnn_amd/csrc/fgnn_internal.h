@@ -37,6 +37,32 @@ struct GraphDev {
                                // check updates of the runtime-degree kernels are compiled for degrees up to 8 and 16
 };
 
+// One layering of a serial schedule, installed by fgnn_graph_set_layers / _set_bit_layers / _set_qubit_layers or, greedy, by the first
+// decode on a graph without one (fgnn_graph_ensure_*): layer_of per item on the host, the tables of the kernels on the device.
+//   check_layers (fgnn_bp4_decode_layered): layer_of per check, hx checks first, then hz.  The checks of layer l = lay_chk[lay_cptr[l] ..
+//     lay_cptr[l+1]) ascending, and their edges in the same order = lay_edge[lay_eptr[l] .. lay_eptr[l+1]) as (slot, qubit) pairs.
+//   bit_layers (fgnn_bp2_decode_layered, fgnn_relay_decode_layered): side 0 (hx) alone, layer_of per hx check; lay_cptr and lay_chk as above.
+//   qubit_layers (fgnn_mbp4_decode_serial, serial along qubits): layer_of per qubit.  The qubits of layer l = lay_qub[lay_qptr[l] ..
+//     lay_qptr[l+1]) ascending, the slots of their edges = lay_slot[lay_eptr[l] .. lay_eptr[l+1]) in that order (a qubit's hx slots, then
+//     its hz slots), and for every slot e its check and its place in the check's row, slot_cj[e] = (combined check c, j with
+//     cslot[cptr[c] + j] = e).
+enum { LAY_CPTR, LAY_CHK, LAY_EPTR, LAY_EDGE };                  // the tables of check_layers; bit_layers has the first two
+enum { LAY_QPTR, LAY_QUB, LAY_QEPTR, LAY_SLOT, LAY_SLOT_CJ };    // the tables of qubit_layers
+struct fgnn_layering {
+    int num = 0;  // layers; 0: none installed
+    std::vector<int32_t> layer_of;
+    std::vector<void*> dev;
+    template <typename T>
+    const T* table(int slot) const { return static_cast<const T*>(dev[slot]); }
+    void free()  // under the graph's device guard
+    {
+        for (void* p : dev) (void)hipFree(p);  // waits for the launches that read it
+        dev.clear();
+        layer_of.clear();
+        num = 0;
+    }
+};
+
 struct fgnn_graph {
     GraphDev d;
     int device;
@@ -52,6 +78,8 @@ struct fgnn_graph {
     std::vector<void*> allocs;
     // host copies of the canonical edge lists (fgnn_graph_edges)
     std::vector<int32_t> h_chk[2], h_var[2];
+    // host copies of d.cptr / d.cslot / d.cvn and of d.vptr_x / d.vptr_z (h_vptr[1] offset by E_x as on the device), kept on every graph
+    std::vector<int> h_cptr, h_cslot, h_cvn, h_vptr[2];
     // host copies of the uploaded check rows (fgnn_check_rows builds a graph with host_only set to read them back without a device)
     bool host_only = false;
     std::vector<uint32_t> h_cslot32;
@@ -59,26 +87,8 @@ struct fgnn_graph {
     void* row_alloc[6][4];
     void* basis_dev[2] = {nullptr, nullptr};  // pivot rows of hx / hz (fgnn_graph_set_basis, OSD)
     int basis_rank[2] = {0, 0};
-    // layering of the serial schedule (fgnn_graph_set_layers; fgnn_bp4_decode_layered installs the greedy one on a graph without):
-    // layer_of per check (hx checks first, then hz) on the host; on the device the checks of layer l = lay_chk[lay_cptr[l] ..
-    // lay_cptr[l+1]) ascending, and their edges in the same order = lay_edge[lay_eptr[l] .. lay_eptr[l+1]) as (slot, qubit) pairs
-    mutable int num_layers = 0;
-    mutable std::vector<int32_t> h_layer_of;
-    mutable void* layer_alloc[4] = {nullptr, nullptr, nullptr, nullptr};  // lay_cptr, lay_chk, lay_eptr, lay_edge
-    // layering of side 0 (hx) alone for the binary serial schedule (fgnn_graph_set_bit_layers; fgnn_bp2_decode_layered installs the
-    // greedy one on a graph without), kept next to the one above and independent of it: layer_of per hx check on the host; on the
-    // device the checks of layer l = lay_chk[lay_cptr[l] .. lay_cptr[l+1]) ascending
-    mutable int num_bit_layers = 0;
-    mutable std::vector<int32_t> h_bit_layer_of;
-    mutable void* bit_layer_alloc[2] = {nullptr, nullptr};  // lay_cptr, lay_chk
-    // layering of the qubits for the schedule that is serial along qubits (fgnn_graph_set_qubit_layers; fgnn_mbp4_decode_serial installs
-    // the greedy one on a graph without), independent of the two above: layer_of per qubit on the host; on the device the qubits of
-    // layer l = lay_qub[lay_qptr[l] .. lay_qptr[l+1]) ascending, the slots of their edges = lay_slot[lay_eptr[l] .. lay_eptr[l+1]) in
-    // that order (a qubit's hx slots, then its hz slots), and for every slot e its check and its place in the check's row, slot_cj[e]
-    // = (combined check c, j with cslot[cptr[c] + j] = e)
-    mutable int num_qubit_layers = 0;
-    mutable std::vector<int32_t> h_qubit_layer_of;
-    mutable void* qubit_layer_alloc[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // lay_qptr, lay_qub, lay_eptr, lay_slot, slot_cj
+    // the three layerings of the serial schedules, independent of each other (fgnn_layering above; the installer is in fgnn_graph.hip)
+    mutable fgnn_layering check_layers, bit_layers, qubit_layers;
     // solve tables of stabilizer inactivation (fgnn_si_decode builds them on its first call and keeps them): per group j = hz row j
     // the adjacent hx checks adj[aptr[j] .. aptr[j+1]), one 64-bit mask over them per bit of the group (xmask, in the order of the
     // hz edges of cvn) and one per consistency row cons[kptr[j] .. kptr[j+1]).  si_state: 0 not built, 1 uploaded, -1 a group is
@@ -255,7 +265,7 @@ struct LaunchGeom {
 };
 LaunchGeom fgnn_geom(const fgnn_graph* g, int B);
 
-// the greedy layering on a graph that has none (fgnn_bp4_decode_layered takes a const handle: the layer tables are mutable members)
+// the greedy layering on a graph that has none (fgnn_bp4_decode_layered takes a const handle: the layerings are mutable members)
 int fgnn_graph_ensure_layers(const fgnn_graph* g);
 // the same for the layering of side 0 alone (fgnn_bp2_decode_layered)
 int fgnn_graph_ensure_bit_layers(const fgnn_graph* g);

@@ -217,12 +217,12 @@ extern "C" int fgnn_mbp4_decode_serial(const fgnn_graph* g, int cn_type, int num
     FGNN_DEVICE_GUARD(g->device);
     a.m_off = (int)m_off;
     a.d_off = (int)(2 * m_off);
-    a.num_layers = g->num_qubit_layers;
-    a.lay_qptr = static_cast<const int*>(g->qubit_layer_alloc[0]);
-    a.lay_qub = static_cast<const int*>(g->qubit_layer_alloc[1]);
-    a.lay_eptr = static_cast<const int*>(g->qubit_layer_alloc[2]);
-    a.lay_slot = static_cast<const int*>(g->qubit_layer_alloc[3]);
-    a.slot_cj = static_cast<const int2*>(g->qubit_layer_alloc[4]);
+    a.num_layers = g->qubit_layers.num;
+    a.lay_qptr = g->qubit_layers.table<int>(LAY_QPTR);
+    a.lay_qub = g->qubit_layers.table<int>(LAY_QUB);
+    a.lay_eptr = g->qubit_layers.table<int>(LAY_QEPTR);
+    a.lay_slot = g->qubit_layers.table<int>(LAY_SLOT);
+    a.slot_cj = g->qubit_layers.table<int2>(LAY_SLOT_CJ);
     const hipStream_t st = static_cast<hipStream_t>(stream);
     const dim3 grid(L.blocks), block(L.threads);
     switch (cn_type) {

@@ -198,9 +198,9 @@ extern "C" int fgnn_relay_decode_layered(const fgnn_graph* g, float normalizatio
     if (int err = bit_lds_bytes(a, g, L, nullptr, {}, 0, &lds_bytes)) return err;
     if (int err = fgnn_graph_ensure_bit_layers(g)) return err;
     FGNN_DEVICE_GUARD(g->device);
-    a.num_layers = g->num_bit_layers;
-    a.lay_cptr = static_cast<const int*>(g->bit_layer_alloc[0]);
-    a.lay_chk = static_cast<const int*>(g->bit_layer_alloc[1]);
+    a.num_layers = g->bit_layers.num;
+    a.lay_cptr = g->bit_layers.table<int>(LAY_CPTR);
+    a.lay_chk = g->bit_layers.table<int>(LAY_CHK);
     hipStream_t st = static_cast<hipStream_t>(stream);
     return bit_dispatch(g, FGNN_CN_MINSUM, true, [&](auto, auto dv, auto dc) {
         return fgnn_launch(relay_layered_kernel<decltype(dv)::value, decltype(dc)::value>, dim3(L.blocks), dim3(L.threads), lds_bytes, st,

@@ -9,7 +9,7 @@ import types
 import numpy as np
 import torch
 
-from ._frontend import ShardedModel, bsc_logit
+from ._frontend import ShardedModel, bsc_logit, install_layering, schedule_in
 from ._lib import CN_TYPES
 from .graph import TannerGraph
 
@@ -58,10 +58,7 @@ class LDPCBPDecoder:
                  schedule="flooding", layers=None, stop_early=False, **kwargs):
         if cn_type not in CN_TYPES:
             raise ValueError('Unknown node type.')
-        if schedule not in ("flooding", "layered"):
-            raise ValueError(f"schedule must be 'flooding' or 'layered', got {schedule!r}")
-        if layers is not None and schedule != "layered":
-            raise ValueError("layers= belongs to schedule='layered'")
+        schedule_in(schedule, layers, "layered")
         if stop_early and schedule != "layered":
             raise ValueError("stop_early=True belongs to schedule='layered'")
         self._schedule, self._stop_early = schedule, bool(stop_early)
@@ -75,8 +72,7 @@ class LDPCBPDecoder:
         self._cn_type, self._hard_out, self._num_iter = cn_type, bool(hard_out), int(num_iter)
         self._normalization_factor, self._is_syndrome, self._output_dtype = float(normalization_factor), bool(is_syndrome), output_dtype
         self.graph = graph if graph is not None else _binary_graph(pcm, None, device)
-        if schedule == "layered" and (layers is not None or self.graph.bit_layers()[0] == 0):
-            self.graph.set_bit_layers(layers)  # None: the greedy layering; a shared graph keeps the layering it already has
+        install_layering(self.graph, schedule, layers, "layered", "bit_layers", "set_bit_layers")
         self._num_vns, self._num_cns = self.graph.n, self.graph.m_x
         self._pcm = pcm
 

@@ -9,7 +9,7 @@ library's codeword-major layouts.
 import numpy as np
 import torch
 
-from ._frontend import syndrome_in
+from ._frontend import install_layering, schedule_in, syndrome_in
 from ._lib import CN_TYPES
 from .graph import TannerGraph
 
@@ -36,12 +36,9 @@ class QLDPCBPDecoder:
                  stage_two=False, device=None, reference_dtypes=True, graph=None, schedule="flooding", layers=None, **kwargs):
         if cn_type not in CN_TYPES:
             raise ValueError('Unknown node type.')  # decoding_q.py:107
-        if schedule not in ("flooding", "layered"):
-            raise ValueError(f"schedule must be 'flooding' or 'layered', got {schedule!r}")
+        schedule_in(schedule, layers, "layered")
         if schedule == "layered" and (trainable or stage_two):
             raise NotImplementedError("the layered schedule has no per-iteration trace: trainable / stage_two decoders run flooding only")
-        if layers is not None and schedule != "layered":
-            raise ValueError("layers= belongs to schedule='layered'")
         self._schedule = schedule
         self._trainable = bool(trainable)
         self._cn_type = cn_type
@@ -61,8 +58,7 @@ class QLDPCBPDecoder:
             raise ValueError("shared graph was built for a different stage_one/stage_two setting")
         # decoders of one sandwich can share one device graph (``graph=``): the tables are immutable
         self.graph = graph if graph is not None else TannerGraph(code, stage_one=want_stage, device=device)
-        if schedule == "layered" and (layers is not None or self.graph.layers()[0] == 0):
-            self.graph.set_layers(layers)  # None: the greedy layering; a shared graph keeps the layering it already has
+        install_layering(self.graph, schedule, layers, "layered", "layers", "set_layers")
         self._num_vns = self.graph.n
         self._num_cns_x = self.graph.m_x
         self._num_cns_z = self.graph.m_z

@@ -394,22 +394,31 @@ class TannerGraph:
         """Install the layering of `bp4_decode_layered` (fgnn_graph_set_layers): ``layer_of`` [m_x + m_z] gives every check (hx checks
         first, then hz) its layer 0 .. max; None installs the greedy layering.  No layer may be empty and no two checks of a layer may
         share a qubit, across hx and hz: a ValueError names the offender."""
-        if layer_of is None:
-            check(_lib.lib().fgnn_graph_set_layers(self.handle, 0, None))
-            return
-        lay = np.ascontiguousarray(layer_of, dtype=np.int32)
-        if lay.shape != (self.m_x + self.m_z,):
-            raise ValueError(f"layer_of must have shape ({self.m_x + self.m_z},), got {lay.shape}")
-        check(_lib.lib().fgnn_graph_set_layers(self.handle, int(lay.max()) + 1, _np_ptr(lay)))
+        self._set_layering("fgnn_graph_set_layers", self.m_x + self.m_z, layer_of)
 
     def layers(self):
         """(num_layers, layer_of [m_x + m_z] int32) of the installed layering; (0, None) when there is none yet."""
+        return self._get_layering("fgnn_graph_layers", self.m_x + self.m_z)
+
+    def _set_layering(self, symbol, length, layer_of):
+        """The three layerings (checks, bits, qubits) are installed alike: ``layer_of`` [length], or None for the greedy one."""
+        install = getattr(_lib.lib(), symbol)
+        if layer_of is None:
+            check(install(self.handle, 0, None))
+            return
+        lay = np.ascontiguousarray(layer_of, dtype=np.int32)
+        if lay.shape != (length,):
+            raise ValueError(f"layer_of must have shape ({length},), got {lay.shape}")
+        check(install(self.handle, int(lay.max()) + 1, _np_ptr(lay)))
+
+    def _get_layering(self, symbol, length):
+        read = getattr(_lib.lib(), symbol)
         num = C.c_int32(0)
-        check(_lib.lib().fgnn_graph_layers(self.handle, C.byref(num), None))
+        check(read(self.handle, C.byref(num), None))
         if num.value == 0:
             return 0, None
-        lay = np.empty(self.m_x + self.m_z, np.int32)
-        check(_lib.lib().fgnn_graph_layers(self.handle, C.byref(num), _np_ptr(lay)))
+        lay = np.empty(length, np.int32)
+        check(read(self.handle, C.byref(num), _np_ptr(lay)))
         return int(num.value), lay
 
     def bp4_decode_layered(self, synd_x, synd_z, num_iter, cn_type="boxplus-phi", factor=1.0, llr_ch=None, llr_const=0.0,
@@ -853,23 +862,11 @@ class TannerGraph:
         """Install the layering of `bp2_decode_layered` (fgnn_graph_set_bit_layers): ``layer_of`` [m_x] gives every hx check its layer
         0 .. max; None installs the greedy layering.  No layer may be empty and no two checks of a layer may share a bit: a ValueError
         names the offender, and the installed layering stays.  Independent of `set_layers`."""
-        if layer_of is None:
-            check(_lib.lib().fgnn_graph_set_bit_layers(self.handle, 0, None))
-            return
-        lay = np.ascontiguousarray(layer_of, dtype=np.int32)
-        if lay.shape != (self.m_x,):
-            raise ValueError(f"layer_of must have shape ({self.m_x},), got {lay.shape}")
-        check(_lib.lib().fgnn_graph_set_bit_layers(self.handle, int(lay.max()) + 1, _np_ptr(lay)))
+        self._set_layering("fgnn_graph_set_bit_layers", self.m_x, layer_of)
 
     def bit_layers(self):
         """(num_layers, layer_of [m_x] int32) of the installed bit layering; (0, None) when there is none yet."""
-        num = C.c_int32(0)
-        check(_lib.lib().fgnn_graph_bit_layers(self.handle, C.byref(num), None))
-        if num.value == 0:
-            return 0, None
-        lay = np.empty(self.m_x, np.int32)
-        check(_lib.lib().fgnn_graph_bit_layers(self.handle, C.byref(num), _np_ptr(lay)))
-        return int(num.value), lay
+        return self._get_layering("fgnn_graph_bit_layers", self.m_x)
 
     def bp2_decode_layered(self, synd, num_iter, cn_type="boxplus-phi", factor=1.0, llr_ch=None, llr_const=0.0, B=None, want_soft=True,
                            want_hard=True, stop=False, want_stats=False):
@@ -1089,23 +1086,11 @@ class TannerGraph:
         0 .. max; None installs the greedy layering.  No layer may be empty and no two qubits of a layer may share a check, on hx or on
         hz: a ValueError names the offender, and the installed layering stays.  ``np.arange(n)`` is Kuo and Lai's literal order.
         Independent of `set_layers` and `set_bit_layers`."""
-        if layer_of is None:
-            check(_lib.lib().fgnn_graph_set_qubit_layers(self.handle, 0, None))
-            return
-        lay = np.ascontiguousarray(layer_of, dtype=np.int32)
-        if lay.shape != (self.n,):
-            raise ValueError(f"layer_of must have shape ({self.n},), got {lay.shape}")
-        check(_lib.lib().fgnn_graph_set_qubit_layers(self.handle, int(lay.max()) + 1, _np_ptr(lay)))
+        self._set_layering("fgnn_graph_set_qubit_layers", self.n, layer_of)
 
     def qubit_layers(self):
         """(num_layers, layer_of [n] int32) of the installed qubit layering; (0, None) when there is none yet."""
-        num = C.c_int32(0)
-        check(_lib.lib().fgnn_graph_qubit_layers(self.handle, C.byref(num), None))
-        if num.value == 0:
-            return 0, None
-        lay = np.empty(self.n, np.int32)
-        check(_lib.lib().fgnn_graph_qubit_layers(self.handle, C.byref(num), _np_ptr(lay)))
-        return int(num.value), lay
+        return self._get_layering("fgnn_graph_qubit_layers", self.n)
 
     def mbp4_decode_serial(self, synd_x, synd_z, factors, owns, pre_iter, attempt_iter, cn_type="minsum", restart=True, llr_ch=None,
                            llr_const=0.0, B=None):

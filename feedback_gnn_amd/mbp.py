@@ -12,7 +12,7 @@ sent (`fgnn_mbp4_decode_serial`, feedback_gnn_amd/csrc/fgnn_mbp4_serial.hip); a 
 import numpy as np
 import torch
 
-from ._frontend import CodeDecoder, DepolarizingBP4Model, alpha_list
+from ._frontend import CodeDecoder, DepolarizingBP4Model, alpha_list, install_layering, schedule_in
 
 ALPHA_DEFAULTS = (1.0, 0.9, 0.8, 0.7, 0.6, 0.5)
 MAX_ALPHAS = 64
@@ -43,10 +43,7 @@ class AMBP4Decoder(CodeDecoder):
 
     def __init__(self, code, alphas=None, num_iter=64, cn_type="minsum", factor=0.8, restart=True, device=None, graph=None,
                  schedule="flooding", layers=None):
-        if schedule not in ("flooding", "serial"):
-            raise ValueError(f"schedule must be 'flooding' or 'serial', got {schedule!r}")
-        if layers is not None and schedule != "serial":
-            raise ValueError("layers= belongs to schedule='serial'")
+        schedule_in(schedule, layers, "serial")
         alphas = alpha_list(ALPHA_DEFAULTS if alphas is None else alphas, MAX_ALPHAS, num_iter, factor, cn_type)
         self.alphas, self.num_iter, self.cn_type, self.factor, self.restart = alphas, int(num_iter), cn_type, float(factor), bool(restart)
         self.factors, self.owns = mbp4_tables(alphas, factor)
@@ -54,8 +51,7 @@ class AMBP4Decoder(CodeDecoder):
             raise ValueError("factor / alpha must be finite in float32")
         self._attach(code, graph, device)
         self.schedule = schedule
-        if schedule == "serial" and (layers is not None or self.graph.qubit_layers()[0] == 0):
-            self.graph.set_qubit_layers(layers)  # None: the greedy layering; a shared graph keeps the layering it already has
+        install_layering(self.graph, schedule, layers, "serial", "qubit_layers", "set_qubit_layers")
         self.last_alpha = None
 
     def solving_alpha(self, stats):

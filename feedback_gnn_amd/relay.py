@@ -10,7 +10,7 @@ three LLRs, both Tanner graphs of a CSS code in one kernel (`fgnn_relay4_decode`
 import numpy as np
 import torch
 
-from ._frontend import CodeDecoder, DepolarizingBP4Model, ShardedModel, alias, bsc_logit
+from ._frontend import CodeDecoder, DepolarizingBP4Model, ShardedModel, alias, bsc_logit, install_layering, schedule_in
 from .decoding import _adopt_bit_layers, _binary_graph
 
 
@@ -50,17 +50,12 @@ class RelayBPDecoder:
     in the layered (serial) check schedule (`fgnn_relay_decode_layered`), on the bit layering of the graph: ``layers`` [m] gives every
     check its layer and is handed to ``graph.set_bit_layers`` (None: the layering the graph has, or the greedy one)."""
 
-    SCHEDULES = ("flooding", "layered")
-
     def __init__(self, pcm, gamma0=0.125, pre_iter=80, num_sets=60, set_max_iter=60, gamma_dist_interval=(-0.24, 0.66), stop_nconv=1,
                  normalization_factor=1.0, seed=0, device=None, graph=None, schedule="flooding", layers=None):
         pcm = np.asarray(pcm.toarray() if hasattr(pcm, "toarray") else pcm)
         if not np.array_equal(pcm, pcm.astype(bool)):
             raise AssertionError('PC matrix must be binary.')
-        if not isinstance(schedule, str) or schedule not in self.SCHEDULES:
-            raise ValueError(f"schedule must be 'flooding' or 'layered', got {schedule!r}")
-        if layers is not None and schedule != "layered":
-            raise ValueError("layers= belongs to schedule='layered'")
+        schedule_in(schedule, layers, "layered")
         lo, hi = _relay_schedule(pre_iter, num_sets, set_max_iter, gamma_dist_interval, stop_nconv)
         self.schedule = schedule
         self._pcm = pcm
@@ -70,8 +65,7 @@ class RelayBPDecoder:
         self.graph = graph if graph is not None else _binary_graph(pcm, None, device)
         self._num_vns, self._num_cns = self.graph.n, self.graph.m_x
         self.gamma = _draw_gamma(self.gamma0, self.num_sets, self._num_vns, lo, hi, self.seed)
-        if schedule == "layered" and (layers is not None or self.graph.bit_layers()[0] == 0):
-            self.graph.set_bit_layers(layers)  # None: the greedy layering; a shared graph keeps the layering it already has
+        install_layering(self.graph, schedule, layers, "layered", "bit_layers", "set_bit_layers")
         self.last_stats = None
 
     pcm = property(lambda self: self._pcm)
